@@ -13,10 +13,12 @@ timed region (inputs resident in HBM).  The timed loop is the reference's own lo
         env.reset()
 
 `value` = num_envs x env.step() calls per wall-second THROUGH GenesisEnv.step, max over ranks.  Exactly K steps
-are timed per repetition, bracketed by barrier + synchronize; when K steps are too short to time (K = 20 is ~1 ms) the bracketed
-K-step region is REPEATED until >= --min-time seconds have been measured, and `value` is total steps / total bracketed time
-(`repeats` in the line).  `hot_path_rate` is the bare fused launch (task.step_raw: no per-step host hand-over of `terminated`)
-over the same number of steps; its HIP-event time per launch is the kernel duration used by `roofline`.
+are timed per repetition, bracketed by barrier + synchronize; with --min-time S the bracketed K-step region is REPEATED until
+>= S seconds have been measured, and `value` is total steps / total bracketed time (`repeats` in the line); by default (S = 0)
+the region runs once, so exactly K steps are timed.  `ms_per_step` is the bracketed time per timed step.  `hot_path_rate` is the
+bare fused launch (task.step_raw: no per-step host hand-over of `terminated`) over the same number of steps; its HIP-event time
+per launch is the kernel duration used by `roofline`.  --dump-outputs DIR writes what the headline's last timed step returned
+(dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 Env axis sharded across ranks (weak scaling: 4096 envs per GPU); with N > 1 the observation/reward outputs of --gather-every
 consecutive steps are all-gathered over RCCL in one collective, overlapped with the following steps.
@@ -69,6 +71,28 @@ def repeats_for(seconds_per_rep: float, min_time: float, max_reps: int = 2000) -
     if seconds_per_rep <= 0.0:
         return max_reps
     return int(max(1, min(max_reps, -(-min_time // seconds_per_rep))))
+
+
+DUMP_LIMIT = 64 << 20   # bytes written by --dump-outputs at most
+
+
+def dump_outputs(dirname: str, arrays: dict, limit: int = DUMP_LIMIT, seed: int = 0) -> dict:
+    """Write {name: array with the envs on axis 0} as dirname/<name>.npy, float32 (float64 stays float64).  Above `limit` bytes in
+    all, the same fixed, seeded sample of envs is written from every array, sorted, and its indices as env_index.npy (float64)."""
+    import numpy as np
+
+    out = {k: np.ascontiguousarray(v, dtype=np.float64 if np.asarray(v).dtype == np.float64 else np.float32) for k, v in arrays.items()}
+    n = min(len(v) for v in out.values())
+    row = sum(v[0].nbytes for v in out.values()) + 8
+    keep = None
+    if sum(v.nbytes for v in out.values()) > limit:
+        keep = np.sort(np.random.default_rng(seed).choice(n, size=max(1, min(n, limit // row)), replace=False))
+        out = {k: v[keep] for k, v in out.items()}
+        out["env_index"] = keep.astype(np.float64)
+    os.makedirs(dirname, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+    return {"files": sorted(out), "bytes": sum(v.nbytes for v in out.values()), "sampled_envs": None if keep is None else len(keep)}
 
 
 def parse_cpulist(text: str):
@@ -176,7 +200,8 @@ def parse_args(argv=None):
     ap.add_argument("--steps", type=int, default=2000)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
-    ap.add_argument("--min-time", type=float, default=0.5, help="repeat the timed K-step region until this many seconds are measured")
+    ap.add_argument("--min-time", type=float, default=0.0,
+                    help="repeat the timed K-step region until this many seconds are measured (default 0: one region, exactly --steps timed steps)")
     ap.add_argument("--no-gather", action="store_true", help="N>1: skip the RCCL observation gather")
     ap.add_argument("--gather-every", type=int, default=32,
                     help="N>1: all-gather the outputs of this many consecutive steps in one collective (1 = every step)")
@@ -202,6 +227,9 @@ def parse_args(argv=None):
                     help="plumbing check: let several ranks share a GPU (device = LOCAL_RANK %% device_count; use with --dist-backend gloo)")
     ap.add_argument("--cpu-baseline-child", type=float, default=None, metavar="SECONDS",
                     help="internal: run the CPU baseline in this (GPU-free) process for about SECONDS and print its JSON object")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the headline's timed steps, write what its last step returned (agent_pos, environment_state, reward, "
+                         "terminated, truncated) as DIR/<name>.npy in float32; with N > 1 every rank writes its shard to DIR/rank<r>/")
     ap.add_argument("--selftest-launch", action="store_true",
                     help="only spawn the ranks, rendezvous over gloo on CPU and print a line (no GPU, no physics)")
     return ap.parse_args(argv)
@@ -1069,7 +1097,7 @@ def selftest_worker(args) -> int:
 
 
 def worker(args) -> int:
-    import numpy as np  # noqa: F401
+    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -1267,6 +1295,8 @@ def worker(args) -> int:
                 env.reset()
                 state["resets"] += 1
         state["t"] = t
+        if k and dump:
+            state["last"] = (obs, reward, terminated, truncated)   # (what the caller received from the last step)
 
     kill_at = None
     if os.environ.get("MIR_BENCH_KILL_RANK"):
@@ -1345,6 +1375,14 @@ def worker(args) -> int:
             total += w
         return walls, evs
 
+    dump, last_outputs = bool(args.dump_outputs), None
+
+    def host_outputs(obs, reward, terminated, truncated):
+        """--dump-outputs: the arrays a caller of the timed path received from its last step, on the host."""
+        return {"agent_pos": obs["agent_pos"].cpu().numpy(), "environment_state": obs["environment_state"].cpu().numpy(),
+                "reward": reward.cpu().numpy(), "terminated": np.asarray(terminated.cpu() if torch.is_tensor(terminated) else terminated),
+                "truncated": np.asarray(truncated)}
+
     out = None
     rc = 0
     try:
@@ -1353,10 +1391,14 @@ def worker(args) -> int:
             _bare_launches(task)   # (bare launches only: exact contacts off, see below)
             walls, evs = measure(raw_loop)
             api_walls = None
+            if dump:   # (what the bare launches compute: the persistent buffers they write)
+                last_outputs = host_outputs({"agent_pos": task._agent, "environment_state": task._envst}, task._reward, task._term, np.zeros(B, bool))
         else:
             task._mir.early_mask_stats(reset=True)
             api_walls, _ = measure(api_loop)
             walls = api_walls
+            if dump:   # (copied to the host before anything else runs: the output ring of a gather is reused)
+                last_outputs = host_outputs(*state.pop("last"))
             if copy_gather is not None:
                 # one more region, NOT part of the measurement: its last gather is compared with all_gather_into_tensor of the same
                 # block on every rank (a torn or lagging copy path shows here, not only in the start-up verification)
@@ -1417,6 +1459,8 @@ def worker(args) -> int:
             "resets_in_loop": state["resets"],
             "path": "GenesisEnv.step" if api_walls is not None else "task.step_raw (--raw-only)",
         }
+        if last_outputs is not None:
+            out["dump_outputs"] = dump_outputs(os.path.join(args.dump_outputs, f"rank{rank}") if world > 1 else args.dump_outputs, last_outputs)
         # ---- what the observation gather costs: the same loop once more with the gather switched off (all ranks take this branch
         # together: `gather` and the flag are the same everywhere) ---------------------------------------------------------
         if gather and api_walls is not None and not args.no_gather_ab:

@@ -45,6 +45,32 @@ def test_launch_command_is_the_drivers_line():
 def test_defaults_are_one_gpu_and_bounded():
     a = bench.parse_args([])
     assert a.gpus == 1 and a.steps == 2000 and a.warmup == 50
+    assert a.min_time == 0.0 and a.dump_outputs is None   # (one region: --steps is the number of timed steps)
+
+
+def test_dump_outputs_writes_float_arrays_under_the_limit(tmp_path):
+    """--dump-outputs: every array as <name>.npy in float32 (float64 kept); above the limit, the same seeded sample of envs from
+    every array, and their indices."""
+    import numpy as np
+
+    B = 4096
+    rng = np.random.default_rng(3)
+    arrays = {"agent_pos": rng.standard_normal((B, 9)).astype(np.float32), "reward": rng.random(B, dtype=np.float32),
+              "terminated": rng.random(B) < 0.5, "x64": rng.standard_normal(B)}
+    r = bench.dump_outputs(str(tmp_path / "full"), arrays)
+    assert r["files"] == sorted(arrays) and r["sampled_envs"] is None
+    for k, v in arrays.items():
+        got = np.load(tmp_path / "full" / f"{k}.npy")
+        assert got.dtype == (np.float64 if k == "x64" else np.float32) and np.array_equal(got, v.astype(got.dtype))
+    limit = 10000
+    r1 = bench.dump_outputs(str(tmp_path / "a"), arrays, limit=limit)
+    r2 = bench.dump_outputs(str(tmp_path / "b"), arrays, limit=limit)
+    assert r1 == r2 and 0 < r1["sampled_envs"] < B and r1["bytes"] <= limit
+    idx = np.load(tmp_path / "a" / "env_index.npy").astype(np.int64)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "env_index.npy")) and np.all(np.diff(idx) > 0)
+    for k, v in arrays.items():
+        assert np.array_equal(np.load(tmp_path / "a" / f"{k}.npy"), v[idx].astype(np.float64 if k == "x64" else np.float32))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= limit + 128 * len(os.listdir(tmp_path / "a"))
 
 
 def test_gpus_2_without_a_launcher_spawns_two_ranks():

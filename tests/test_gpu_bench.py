@@ -20,7 +20,7 @@ def _run(*flags, timeout=900, raw=False):
 
 
 def test_driver_command_prints_the_contract_line():
-    out, line, _ = _run("--gpus", "1", "--steps", "20", "--warmup", "5", raw=True)
+    out, line, _ = _run("--gpus", "1", "--steps", "20", "--warmup", "5", "--min-time", "0.5", raw=True)
     # the driver keeps 8 KB tails: the line must fit with room to spare, and what its record has to show comes FIRST, in full
     assert len(line) <= 6000, len(line)
     keys = list(out)
@@ -69,6 +69,27 @@ def test_driver_command_prints_the_contract_line():
     assert out["value_median_region"] >= out["value"] * 0.8 and out["config"]["host_thread"].startswith("pinned to cpu")
 
 
+def test_steps_are_the_timed_steps_and_the_dumped_outputs_repeat(tmp_path):
+    """`--steps K` times exactly K steps (one region by default) and `ms_per_step` is their time per step; `--dump-outputs` writes
+    what the last timed step returned, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+
+    runs = []
+    for name in ("a", "b"):
+        out = _run("--gpus", "1", "--steps", "300", "--warmup", "5", "--core-only", "--no-cpu-baseline", "--dump-outputs", str(tmp_path / name))
+        assert out["steps"] == 300 and out["repeats"] == 1 and out["timed_steps_total"] == 300, out
+        assert abs(out["ms_per_step"] * 300 - out["timed_seconds_total"] * 1e3) < 1e-5 * out["timed_seconds_total"] * 1e3   # (the line keeps 7 digits)
+        assert out["dump_outputs"]["sampled_envs"] is None
+        runs.append({f[:-4]: np.load(tmp_path / name / f) for f in sorted(os.listdir(tmp_path / name))})
+    a, b = runs
+    assert sorted(a) == ["agent_pos", "environment_state", "reward", "terminated", "truncated"]
+    assert a["agent_pos"].shape == (4096, 9) and a["environment_state"].shape == (4096, 11) and a["reward"].shape == (4096,)
+    assert all(v.dtype == np.float32 for v in a.values()) and np.isfinite(a["agent_pos"]).all()
+    assert np.array_equal(a["terminated"], (a["reward"] == 1).astype(np.float32))
+    for k in a:
+        assert np.array_equal(a[k], b[k]), k
+
+
 def test_two_ranks_share_the_gpu_over_gloo():
     """N > 1 plumbing on a 1-GPU box: bench.py spawns two ranks itself, both on cuda:0, process group over gloo, the env axis
     sharded, outputs gathered; rank 0 prints n_gpus == 2 with the world size the process group reports."""
@@ -94,7 +115,7 @@ def test_first_rccl_run_one_rank_force_gather():
     gather (all_gather_into_tensor of 8 steps' outputs), barriers and the max-over-ranks all-reduce all execute through RCCL;
     the line reports the world size the group observed and what the gather costs per step against the same loop without it."""
     out = _run("--gpus", "1", "--force-gather", "--dist-backend", "nccl", "--steps", "20", "--warmup", "5", "--no-pixels", "--no-stack",
-               "--no-cpu-baseline")
+               "--no-cpu-baseline", "--min-time", "0.5")
     cfg = out["config"]
     assert out["n_gpus"] == 1 and cfg["world_size_observed"] == 1 and cfg["dist_backend"] == "nccl"
     assert cfg["gather_path"] == "copy" and out["value"] > 1e6
