@@ -498,6 +498,7 @@ int mir_destroy(MirHandle h) {
   if (h->scratch_row) (void)hipFree(h->scratch_row);
   if (h->pre) (void)hipFree(h->pre);
   if (h->pre_big) (void)hipFree(h->pre_big);
+  if (h->xr_stats) (void)hipFree(h->xr_stats);
   if (h->main_event) (void)hipEventDestroy((hipEvent_t)h->main_event);
   if (h->light_event) (void)hipEventDestroy((hipEvent_t)h->light_event);
   if (h->next_host) (void)hipHostFree(h->next_host);
@@ -1172,6 +1173,16 @@ int mir_set_exact_contacts(MirHandle h, const MirSceneSpec* spec, int32_t on) {
     HIPCHK(hipHostGetDevicePointer((void**)&h->next_dev, h->next_host, 0));
   }
   h->rt_ok = 0;
+  if (!h->xr_stats) {  // (mir_rollout_exact's lists and counters: see mir_scene.h)
+    DeviceGuard guard(h->device);
+    const size_t B = (size_t)h->B, bytes = 4 * sizeof(unsigned long long) + 16 * sizeof(int32_t) + 3 * B * sizeof(int32_t);
+    HIPCHK(hipMalloc((void**)&h->xr_stats, bytes));
+    HIPCHK(hipMemset(h->xr_stats, 0, bytes));
+    h->xr_count = reinterpret_cast<int32_t*>(h->xr_stats + 4);
+    h->xr_list = h->xr_count + 16;
+    h->xr_list2 = h->xr_list + B;
+    h->xr_start = h->xr_list2 + B;
+  }
   if (h->big_on && !h->pre_big) {
     DeviceGuard guard(h->device);
     HIPCHK(hipMalloc((void**)&h->pre_big, (size_t)h->B * K48_STRIDE * sizeof(float)));
@@ -1325,6 +1336,129 @@ int mir_rollout(MirHandle h, const float* actions, int32_t n_steps, float* rows,
   o.action = actions; o.rows = rows; o.row_stride = row_stride; o.n_steps = n_steps;
   o.act_step = (long)h->B * h->nu; o.rows_step = (long)h->B * row_stride;
   return launch(h, o, stream);
+}
+
+/* Device-resident K-step rollout that keeps every contact point (mirigid.h: mir_rollout_exact).  A fixed chain on the caller's stream:
+ *   memset of the two list counters;
+ *   the one-wave step loop with hand-off (VARIANT 12) for the whole batch -- an env stays on it until its first step above the
+ *     one-contact-per-lane capacity, then stores its state of that step's start and appends itself to list 1 (exact == 2: every env at
+ *     step 0, the twin route of the tests);
+ *   the three-contacts-per-lane step loop (VARIANT 13) over list 1 -- fixed grid, a workgroup past the list's device count exits at
+ *     once -- each env from its own start step to the end of the call, which hands an env beyond 48 points or 16 candidate pairs on to
+ *     list 2 (scenes whose host-closed route has no list instantiation: list 1 is list 2);
+ *   the wave-per-env kernel in list mode over list 2, each env resuming at its own step (the 16-lane layout in and out);
+ *   a one-thread kernel that folds list 1's count into the statistics.
+ * No host read, no pinned memory, no host wait.  Every kernel of the chain runs the same step body as the route of mir_step_begin /
+ * mir_step_end, so the bits are that route's (see mirigid.h for the one exception). */
+__global__ void k_xr_close(const int32_t* count, unsigned long long* stats) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    const unsigned long long n = (unsigned long long)count[0];
+    if (n > stats[2]) stats[2] = n;
+  }
+}
+
+static int rollout_exact(MirScene* h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, const AutoResetArgs& ar, void* stream, const char* who) {
+  if (h->pending) {  // (a step left open: closed first, as mir_reset does)
+    int rc = mir_step_end(h, nullptr);
+    if (rc != MIR_OK) return rc;
+  }
+  if (int rc = check_mask(h)) return rc;
+  if (!h->xr_stats) return set_err(MIR_E_INVALID, "%s: exact contacts were never switched on", who);
+  if (n_steps >= XR_TIER2) return set_err(MIR_E_INVALID, "%s: n_steps must be below 2^20", who);
+  DeviceGuard guard(h->device);
+  // (the side-stream launches of an earlier host-closed overflow step own the state and the scratch rows until ovf_event: mir_step_begin)
+  if (h->ovf_event_live && h->ovf_waited_stream != stream) {
+    HIPCHK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)h->ovf_event, 0));
+    h->ovf_waited_stream = stream;
+  }
+  h->pre_valid = 0;
+  h->poses_current = 0;
+  h->state_version++;
+  h->xr_calls++;
+  const hipStream_t st = (hipStream_t)stream;
+  HIPCHK(hipMemsetAsync(h->xr_count, 0, 2 * sizeof(int32_t), st));
+  StepArgs a;
+  memset(&a, 0, sizeof a);
+  a.model = h->dm;
+  a.qpos = h->qpos; a.qvel = h->qvel; a.target = h->target; a.qacc_ws = h->qacc_ws;
+  a.diag = h->diag_on ? h->diag : nullptr;
+  a.early_stats = h->early_stats; a.no_early_mask = 1;
+  a.term_wstride = h->term_wstride;
+  a.B = h->B; a.qst = h->hm.qstride; a.nu = h->hm.nu;
+  a.features = (h->hm.has_convex ? 1 : 0) | (h->hm.use_sap ? 3 : 0) | (h->spec_pick ? 4 : 0);
+  a.row_stride = row_stride; a.mode = 0;
+  a.ar = ar;
+  a.exact = h->exact;
+  // (without the list instantiation the hand-off of (1) goes to list 2 directly: the step index it records carries no tier bit, which
+  //  only VARIANT 13 reads)
+  a.xr_list = h->exact_big ? h->xr_list : h->xr_list2; a.xr_count = h->exact_big ? h->xr_count : h->xr_count + 1;
+  a.xr_list2 = h->xr_list2; a.xr_count2 = h->xr_count + 1;
+  a.xr_start = h->xr_start; a.xr_stats = h->xr_stats;
+  const long as = (long)h->B * h->nu, rs = (long)h->B * row_stride;
+  // (1) the whole batch on the one-wave step loop, every env until its hand-off
+  a.phase = 12; a.action = actions; a.rows = rows; a.n_steps = n_steps; a.act_step = as; a.rows_step = rs;
+  int rc = mir_launch_step(&a, h->hm.max_contacts, st);
+  if (rc != 0) return hip_fail((hipError_t)rc, who);
+  // (2) list 1 on the three-contacts-per-lane step loop, each env from its own step (scenes whose host-closed route sends the deferred
+  //     envs to the wave-per-env kernel instead -- no split closing FK, or MIR_EXACT_WAVE -- hand them straight to list 2 in (1))
+  if (h->exact_big) {
+    a.phase = 13; a.env_list = h->xr_list; a.n_steps = n_steps; a.action = actions; a.rows = rows; a.act_step = as; a.rows_step = rs;
+    rc = mir_launch_step(&a, h->hm.max_contacts, st);
+    if (rc != 0) return hip_fail((hipError_t)rc, who);
+  }
+  // (3) list 2 on the wave-per-env kernel, each env from its own step to the end of the call
+  StepArgs64 w;
+  memset(&w, 0, sizeof w);
+  w.model = h->dm64;
+  w.qpos = h->qpos; w.qvel = h->qvel; w.target = h->target; w.qacc_ws = h->qacc_ws;
+  w.diag = h->diag_on ? h->diag : nullptr;
+  w.bad_count = h->early_stats;
+  w.B = h->B; w.nu = h->hm64.nu; w.convex = h->hm64.has_convex;
+  w.action = actions; w.rows = rows; w.row_stride = row_stride; w.act_step = as; w.rows_step = rs; w.ar = ar;
+  w.mode = 0; w.n_steps = n_steps;
+  w.env_list = h->xr_list2; w.lay16_qst = h->hm.qstride;
+  w.list_count = h->xr_count + 1; w.env_start = h->xr_start; w.xr_stats = h->xr_stats;
+  rc = mir_launch_step64(&w, st);
+  if (rc != 0) return hip_fail((hipError_t)rc, who);
+  hipLaunchKernelGGL(k_xr_close, dim3(1), dim3(64), 0, st, h->xr_count, h->xr_stats);
+  HIPCHK(hipGetLastError());
+  return MIR_OK;
+}
+
+int mir_rollout_exact(MirHandle h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, void* stream) {
+  if (check(h) || !actions || !rows) return set_err(MIR_E_INVALID, "mir_rollout_exact: null argument");
+  if (h->kernel != 16) return set_err(MIR_E_INVALID, "mir_rollout_exact: the scene runs on the wave-per-env kernel (48 points, nothing to switch): use mir_rollout");
+  if (row_stride < h->agent_dim + h->env_dim + 2) return set_err(MIR_E_INVALID, "mir_rollout_exact: row_stride too small");
+  if (!h->exact) return mir_rollout(h, actions, n_steps, rows, row_stride, stream);
+  if (n_steps <= 0) return MIR_OK;
+  return rollout_exact(h, actions, n_steps, rows, row_stride, AutoResetArgs{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}, stream, "mir_rollout_exact");
+}
+
+int mir_rollout_autoreset_exact(MirHandle h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, int32_t* episode_len,
+                                int32_t max_len, const float* spawn_pool, int32_t pool_len, int32_t* cursor, const float* obj_quat,
+                                const float* arm_qpos, void* stream) {
+  if (check(h) || !actions || !rows) return set_err(MIR_E_INVALID, "mir_rollout_autoreset_exact: null argument");
+  if (!episode_len || !spawn_pool || !cursor || !obj_quat || !arm_qpos || pool_len <= 0) return set_err(MIR_E_INVALID, "mir_rollout_autoreset_exact: null argument");
+  if (h->kernel != 16) return set_err(MIR_E_INVALID, "mir_rollout_autoreset_exact: the scene runs on the wave-per-env kernel (48 points, nothing to switch): use mir_rollout_autoreset");
+  if (row_stride < h->agent_dim + h->env_dim + 3) return set_err(MIR_E_INVALID, "mir_rollout_autoreset_exact: row_stride too small (needs the truncated column)");
+  if (!h->exact) return mir_rollout_autoreset(h, actions, n_steps, rows, row_stride, episode_len, max_len, spawn_pool, pool_len, cursor, obj_quat, arm_qpos, stream);
+  if (n_steps <= 0) return MIR_OK;
+  return rollout_exact(h, actions, n_steps, rows, row_stride, AutoResetArgs{episode_len, cursor, spawn_pool, obj_quat, arm_qpos, pool_len, max_len}, stream,
+                       "mir_rollout_autoreset_exact");
+}
+
+int mir_get_rollout_exact_stats(MirHandle h, uint64_t* out4, int32_t reset) {
+  if (check(h) || !out4) return set_err(MIR_E_INVALID, "mir_get_rollout_exact_stats: null argument");
+  unsigned long long dev[4] = {0, 0, 0, 0};
+  if (h->xr_stats) {  // (synchronises the device: the counters are written by the launches)
+    DeviceGuard guard(h->device);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(dev, h->xr_stats, sizeof dev, hipMemcpyDeviceToHost));
+    if (reset) HIPCHK(hipMemset(h->xr_stats, 0, sizeof dev));
+  }
+  out4[0] = h->xr_calls; out4[1] = dev[0]; out4[2] = dev[1]; out4[3] = dev[2];
+  if (reset) h->xr_calls = 0;
+  return MIR_OK;
 }
 
 int mir_rollout_autoreset(MirHandle h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, int32_t* episode_len,

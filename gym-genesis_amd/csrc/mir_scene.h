@@ -114,6 +114,13 @@ struct MirScene {
   int rt_ok, rt_perm;       // the first-half launch of the step before wrote them, serving the envs through perm_host[rt_perm] (-1: in order)
   uint32_t rt_tag;          // ... with this tag
   void* light_event;        // hipEvent_t behind the list launch on the side stream: the step's stream waits for it
+  // DEVICE-RESIDENT ROLLOUT THAT KEEPS EVERY CONTACT POINT (mir_rollout_exact; allocated by mir_set_exact_contacts, never by the call):
+  // [stats: 4 x u64 -- list env-steps, wave env-steps, most envs handed off in one call, pad | counts: 16 x i32 -- list 1, list 2 |
+  //  list 1 (B x i32) | list 2 (B x i32) | start step per env (B x i32)], device memory
+  unsigned long long* xr_stats;
+  int32_t* xr_count;
+  int32_t *xr_list, *xr_list2, *xr_start;
+  unsigned long long xr_calls;  // calls that went the device-resident way (host counter)
 };
 
 // library-internal helpers implemented in mir_api.hip

@@ -77,7 +77,26 @@ struct StepArgs {
   // phase 7: device address of pinned host words, one per workgroup -- byte k = term_tag << 1 | (the NEXT step finds the workgroup's env k
   // with more candidate points than over_cap) -- or null
   uint32_t* next_host;
+  // DEVICE-RESIDENT ROLLOUT THAT KEEPS EVERY CONTACT POINT (mir_rollout_exact: phases 12 / 13, VARIANT 12 / 13 of mir_step.hip).  Nothing
+  // of it is read by the host between two steps: the lists and counters stay in device memory.
+  //  phase 12 (the one-wave step loop with hand-off): an env whose step k finds more candidate points than the one-contact-per-lane
+  //    capacity (or saturates the 16 candidate lanes) stores its state of step k's start, xr_start[env] = k, and is appended to
+  //    xr_list (one device-scope atomicAdd on *xr_count); nothing more is stored for it in this launch.
+  //  phase 13 (the three-contacts-per-lane step loop, passes of the whole step): serves xr_list[0 .. *xr_count) -- the grid is fixed, a
+  //    workgroup past the count exits at once -- and steps each env from xr_start[env] to n_steps - 1 (pass s: the actions and rows of
+  //    step s of the call, autoreset inside; xr_step is set per pass).  An env beyond ITS capacity (48 points, 16 candidate pairs)
+  //    stores nothing more, gets xr_start[env] = s | XR_TIER2 and goes on xr_list2 (*xr_count2) for the wave-per-env kernel.
+  int32_t* xr_list;
+  int32_t* xr_count;
+  int32_t* xr_list2;
+  int32_t* xr_count2;
+  int32_t* xr_start;
+  unsigned long long* xr_stats;  // phase 13: [0] += env-steps taken (one device atomic per workgroup and pass)
+  int xr_step;
 };
+#ifndef XR_TIER2
+#define XR_TIER2 (1 << 20) /* xr_start: the env is on the second list (the wave-per-env kernel); the low bits keep its step */
+#endif
 #define K48_HEAD 0    /* ncon, second-tree flags of contacts 16 .. 31, of 32 .. 47 (int bits), pad */
 #define K48_CMETA 4   /* MIR_MAX_CONTACT x 4 */
 #define K48_JB (K48_CMETA + 4 * MIR_MAX_CONTACT) /* MIR_MAX_CONTACT rows of 48 floats (n, t1, t2 x 16 dofs) */

@@ -54,6 +54,16 @@ struct StepArgs64 {
   // entry k goes to term_host[k].  No pose cache (poses / fkvalid null), no dispatch order (cost_in / cost_out null).
   const int32_t* env_list;  // null = the envs 0 .. B of a handle of this kernel
   int lay16_qst;            // list mode: row stride of qpos in the 16-lane layout (> 0); 0 = this kernel's own layout
+  // ... with a DEVICE count and a per-env RESUME (mir_rollout_exact, the wave-kernel tail): the grid is the handle's batch B (B stays
+  // the handle's, the spawn pool is indexed by it), workgroup k serves env_list[k] while k < *list_count and exits at once otherwise;
+  // env e runs the steps (env_start[e] & (XR_TIER2 - 1)) .. n_steps - 1 of the call -- actions, rows and autoreset by the call's step index --
+  // from its stored state in the 16-lane layout, and stores it back.  Null: the list's length is B, every env starts at step 0.
+  const int32_t* list_count;
+  const int32_t* env_start;
+  unsigned long long* xr_stats;  // [1] += env-steps taken (list_count mode only)
 };
+#ifndef XR_TIER2
+#define XR_TIER2 (1 << 20) /* (mir_step.h) env_start: the env is on the wave kernel's list; the low bits keep its step */
+#endif
 
 extern "C" __attribute__((visibility("hidden"))) int mir_launch_step64(const StepArgs64* args, hipStream_t stream);

@@ -496,7 +496,16 @@ void mir_step64_kernel(StepArgs64 a) {
   }
   // list mode (mir_step64.h): the workgroup serves list entry `slot`; state rows in the 16-lane kernel's layout
   const int slot = blockIdx.x;
+  // (with a device count -- mir_rollout_exact's tail: a workgroup past it leaves at once, before any barrier; the env then resumes the
+  //  call at its own step: actions and rows from that step's block on, the step loop for the rest of the call)
+  if (a.list_count && slot >= *a.list_count) return;
   if (a.env_list) env = a.env_list[slot];
+  if (a.list_count) {
+    const int st = a.env_start[env] & (XR_TIER2 - 1);
+    if (a.action) a.action += (size_t)st * a.act_step;
+    if (a.rows) a.rows += (size_t)st * a.rows_step;
+    a.n_steps -= st;
+  }
   const bool lay16 = a.lay16_qst > 0;  // wave-uniform
   // the state rows of the env, from LDS to HBM, in the layout of the handle (called where the step is integrated)
   auto store_state = [&](Env64& Sx, int lane_, int dof16_, bool isdof_) {
@@ -1181,6 +1190,7 @@ void mir_step64_kernel(StepArgs64 a) {
   if (DUAL) __syncthreads();  // (1)
   STAMP(1);
   const int nsteps = SINGLE ? 1 : (a.mode == 0 ? a.n_steps : (a.mode == 1 ? 1 : 0));
+  if (a.list_count && a.xr_stats && threadIdx.x == 0) atomicAdd(&a.xr_stats[1], (unsigned long long)nsteps);
   if (SINGLE) { a.mode = 0; a.act_step = 0; a.rows_step = 0; a.ar.episode_len = nullptr; a.out_M = a.out_bias = a.out_qas = a.out_qacc = a.out_xpos = a.out_xquat = nullptr;
 #ifndef MIR_PROFILE_SINGLE  /* (a profiling build keeps the phase stamps in the single-step instantiation: tools/phase_profile64.py) */
     a.prof = nullptr;

@@ -74,6 +74,12 @@ def load_library() -> C.CDLL:
     lib.mir_rollout.restype = C.c_int
     lib.mir_rollout_autoreset.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp]
     lib.mir_rollout_autoreset.restype = C.c_int
+    lib.mir_rollout_exact.argtypes = [vp, vp, i32, vp, i32, vp]
+    lib.mir_rollout_exact.restype = C.c_int
+    lib.mir_rollout_autoreset_exact.argtypes = [vp, vp, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp]
+    lib.mir_rollout_autoreset_exact.restype = C.c_int
+    lib.mir_get_rollout_exact_stats.argtypes = [vp, C.POINTER(C.c_uint64), i32]
+    lib.mir_get_rollout_exact_stats.restype = C.c_int
     lib.mir_get_obs.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.mir_get_state.argtypes = [vp, vp, vp, vp, vp, vp]
     lib.mir_set_state.argtypes = [vp, vp, vp, vp, vp, vp]
@@ -508,6 +514,34 @@ class MirScene(StepHelpers):
         self._check(self.lib.mir_rollout_autoreset(self.h, _ptr(actions), int(K), _ptr(rows), int(rows.stride(1)), _ptr(episode_len), int(max_len),
                                                    _ptr(spawn_pool), int(spawn_pool.shape[0]), _ptr(cursor), _ptr(obj_quat), _ptr(arm_qpos),
                                                    self._stream()))
+
+    def rollout_exact(self, actions: torch.Tensor, rows: torch.Tensor) -> None:
+        """K env steps that keep every contact point, on the device (mir_rollout_exact): bit-identical to K x (step_begin; step_end)
+        with exact contacts on; rollout() itself when they are off.  actions (K,B,nu), rows (K,B,row_stride) as in rollout()."""
+        K = actions.shape[0]
+        if tuple(actions.shape) != (K, self.num_envs, self.nu) or rows.shape[0] != K or rows.shape[1] != self.num_envs or not (
+                actions.is_contiguous() and rows.is_contiguous()):
+            raise ValueError("rollout_exact: actions (K,B,nu) and rows (K,B,row_stride) must be contiguous device tensors")
+        self._check(self.lib.mir_rollout_exact(self.h, _ptr(actions), int(K), _ptr(rows), int(rows.stride(1)), self._stream()))
+
+    def rollout_autoreset_exact(self, actions: torch.Tensor, rows: torch.Tensor, episode_len, max_len: int, spawn_pool, cursor, obj_quat,
+                                arm_qpos) -> None:
+        """rollout_autoreset() that keeps every contact point (mir_rollout_autoreset_exact): bit-identical to K x (step_begin; step_end;
+        mir_autoreset) with exact contacts on; rollout_autoreset() itself when they are off."""
+        K = actions.shape[0]
+        if tuple(actions.shape) != (K, self.num_envs, self.nu) or rows.shape[0] != K or rows.shape[1] != self.num_envs or not (
+                actions.is_contiguous() and rows.is_contiguous()):
+            raise ValueError("rollout_autoreset_exact: actions (K,B,nu) and rows (K,B,row_stride) must be contiguous device tensors")
+        self._check(self.lib.mir_rollout_autoreset_exact(self.h, _ptr(actions), int(K), _ptr(rows), int(rows.stride(1)), _ptr(episode_len),
+                                                         int(max_len), _ptr(spawn_pool), int(spawn_pool.shape[0]), _ptr(cursor), _ptr(obj_quat),
+                                                         _ptr(arm_qpos), self._stream()))
+
+    def rollout_exact_stats(self, reset: bool = False) -> dict:
+        """mir_get_rollout_exact_stats (synchronises the device): device-resident calls, env-steps on the three-contacts-per-lane
+        instantiation, env-steps on the wave-per-env kernel, most envs handed off in one call."""
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.mir_get_rollout_exact_stats(self.h, out, 1 if reset else 0))
+        return {"calls": int(out[0]), "list_env_steps": int(out[1]), "wave_env_steps": int(out[2]), "max_handed": int(out[3])}
 
     def get_obs(self):
         agent, env = self.empty(self.agent_dim), self.empty(self.env_dim)

@@ -163,14 +163,18 @@ class FrankaCubePickBatch:
         return self.get_obs()
 
     # ---- device-resident episode loop --------------------------------------
-    def enable_autoreset(self, max_episode_steps: int = 200, pool_len: int = 64):
+    def enable_autoreset(self, max_episode_steps: int = 200, pool_len: int = 64, keep_exact_contacts: bool = False):
         """Keep the whole episode loop on the device: after every step_autoreset() the envs whose episode
         ended (terminated, or `max_episode_steps` reached) are re-spawned by one small kernel, without the
         D->H read of `terminated` and the reset-all the reference's loop needs (README.md:41-43).
         Spawn positions come from the task RandomState as in reset() (x block then y block per draw),
-        `pool_len` draws ahead; env e's k-th re-spawn uses draw k % pool_len."""
+        `pool_len` draws ahead; env e's k-th re-spawn uses draw k % pool_len.
+        keep_exact_contacts=True (with exact contacts on): the loop keeps every contact point -- rollout_autoreset() goes through
+        mir_rollout_autoreset_exact, still without the host between the steps; step_autoreset() closes each step on the host anyway.
+        The default switches exact contacts off (with a warning) and runs the loop on thinned manifolds, as before."""
         B, dev = self.num_envs, self.device
-        if getattr(self._mir, "exact_contacts", False):
+        self._keep_exact = bool(keep_exact_contacts) and bool(getattr(self._mir, "exact_contacts", False))
+        if getattr(self._mir, "exact_contacts", False) and not self._keep_exact:
             # (exact contacts close every step on the host -- that is where the envs with more than 16 contact points are handed on;
             #  this loop has no host in it: it runs with the manifolds thinned to the 16-lane kernel's 16 points)
             import warnings
@@ -201,8 +205,8 @@ class FrankaCubePickBatch:
     def rollout_autoreset(self, actions_dev: torch.Tensor, rows: torch.Tensor) -> torch.Tensor:
         """K steps of the device-resident episode loop in ONE launch (after enable_autoreset()): actions (K,B,9), rows
         (K,B,>=23) <- [agent_pos 9 | environment_state 11 | reward | terminated | truncated] per step and env."""
-        self._mir.rollout_autoreset(actions_dev, rows, self._episode_len, self._max_episode_steps, self._spawn_pool, self._cursor,
-                                    self._quat, self._home)
+        go = self._mir.rollout_autoreset_exact if getattr(self, "_keep_exact", False) else self._mir.rollout_autoreset
+        go(actions_dev, rows, self._episode_len, self._max_episode_steps, self._spawn_pool, self._cursor, self._quat, self._home)
         return rows
 
     def step(self, action):

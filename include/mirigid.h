@@ -306,7 +306,8 @@ int mir_step_go(MirHandle h, const float* action, void* stream);
  * only once mir_step_end has returned: anything queued between mir_step_begin and mir_step_end -- a mir_render of the observation's
  * images, say -- sees its OLD rows (the task classes close the step before they draw).  `spec`: the spec the scene was created from (compiled once more, for the wave
  * kernel; may be NULL when switching back on).  While the switch is on, mir_step and mir_step_fused run as begin + end (they wait for the
- * step), and mir_step_packed / mir_rollout / mir_rollout_autoreset return MIR_E_INVALID (their steps are never closed on the host).
+ * step), and mir_step_packed / mir_rollout / mir_rollout_autoreset return MIR_E_INVALID (their steps are never closed on the host);
+ * mir_rollout_exact / mir_rollout_autoreset_exact are the K-step rollouts that keep every contact point without the host (below).
  * MIR_E_INVALID for scenes of the wave kernel (nothing to do) and for sync modes other than 3.
  * mir_get_exact_stats: out4 = {steps closed by mir_step_end, steps that had deferred envs, deferred env-steps, most deferred envs in one
  * step} since the last reset of the counters (reset != 0 clears them).  mir_get_exact_route: out4 = {deferred env-steps handed to the
@@ -350,6 +351,30 @@ int mir_rollout(MirHandle h, const float* actions, int32_t n_steps, float* rows,
 int mir_rollout_autoreset(MirHandle h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, int32_t* episode_len,
                           int32_t max_len, const float* spawn_pool, int32_t pool_len, int32_t* cursor, const float* obj_quat,
                           const float* arm_qpos, void* stream);
+
+/* K-step rollouts that KEEP EVERY CONTACT POINT (exact contacts on) without the host between the steps: arguments and rows as
+ * mir_rollout / mir_rollout_autoreset, results bit-identical to n_steps x (mir_step_begin; mir_step_end) -- with mir_autoreset behind
+ * each step for the second call -- under the same switch.  With the switch off they ARE mir_rollout / mir_rollout_autoreset.  The call
+ * queues a fixed chain on `stream` (no host read, no pinned memory, no host wait): a memset of two device counters; the one-wave step
+ * loop for the whole batch, which hands an env off to a device list at its first step above the one-contact-per-lane capacity (more
+ * candidate points than 16 lanes, or more than 16 candidate pairs; on = 2: every env at step 0); one launch of the
+ * three-contacts-per-lane instantiation (48 points) whose step loop takes each env of that list from its own step -- an env that comes back to
+ * 16 points or fewer stays there for the rest of the call, which is the same bits (an env within 16 points is computed there bit for
+ * bit as by the one-contact-per-lane kernel); the wave-per-env kernel (48 points, 64 candidate pairs) for an env beyond THAT
+ * capacity, from that step to the end of the call; and a one-thread statistics kernel.  The bits are the host-closed route's for every
+ * env that stays within 48 points and 16 candidate pairs, or that once beyond them stays beyond them for the rest of the call: an env
+ * that comes back under that capacity after the wave kernel has taken it finishes the call on the wave kernel -- the same contact
+ * model (48 points, 64 candidates), other bits.  A scene without the split closing forward kinematics (or with MIR_EXACT_WAVE set),
+ * whose host-closed route sends every deferred env to the wave kernel, hands them to the wave kernel here too.  n_steps < 2^20.  A pending step is closed first; `stream` waits for the side-stream launches of an
+ * earlier host-closed step.  MIR_E_INVALID: null arguments, a short row_stride, a scene of the wave kernel (nothing to switch).
+ * mir_get_rollout_exact_stats: out4 = {calls that went the device-resident way, env-steps on the three-contacts-per-lane
+ * instantiation, env-steps on the wave kernel, most envs handed off in one call} since the last reset (reset != 0 clears them).  It
+ * reads device counters: it synchronises the device. */
+int mir_rollout_exact(MirHandle h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, void* stream);
+int mir_rollout_autoreset_exact(MirHandle h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, int32_t* episode_len,
+                                int32_t max_len, const float* spawn_pool, int32_t pool_len, int32_t* cursor, const float* obj_quat,
+                                const float* arm_qpos, void* stream);
+int mir_get_rollout_exact_stats(MirHandle h, uint64_t* out4, int32_t reset);
 
 /* get_obs() without stepping */
 int mir_get_obs(MirHandle h, float* agent_pos, float* env_state, float* reward, uint8_t* terminated,
