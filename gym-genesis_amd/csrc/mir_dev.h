@@ -40,6 +40,13 @@ __device__ __forceinline__ void st3(float* p, V3 a) { p[0] = a.x; p[1] = a.y; p[
 __device__ __forceinline__ f4 ldv(const float* p) { return *reinterpret_cast<const f4*>(p); }
 __device__ __forceinline__ void stv(float* p, f4 v) { *reinterpret_cast<f4*>(p) = v; }
 __device__ __forceinline__ V3 ld3v(const float* p) { f4 v = ldv(p); return {v.x, v.y, v.z}; }
+// the leading three / two floats of a 16-byte record as ONE read of only those (ds_read_b96 / ds_read_b64), for the batched reads of
+// the Newton loop: an ldv() whose trailing floats are dead leaves their registers free, the allocator hands them to a later read of
+// the same batch, and that write-after-write costs an lgkmcnt(0) wait -- a whole LDS round trip -- in the middle of the batch
+typedef float f3 __attribute__((ext_vector_type(3)));
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f3 ldv3(const float* p) { return *reinterpret_cast<const f3*>(p); }
+__device__ __forceinline__ f2 ldv2(const float* p) { return *reinterpret_cast<const f2*>(p); }
 __device__ __forceinline__ void st3v(float* p, V3 a, float w = 0.0f) { stv(p, f4{a.x, a.y, a.z, w}); }
 
 // sin and cos of one argument without the library routine's large-argument path: Cody-Waite reduction by pi/2 (exact for the
@@ -99,13 +106,16 @@ __device__ __forceinline__ V3 mmul(const M3& R, V3 v) { return {dot(R.r0, v), do
 
 // ---- DPP cross-lane primitives over one 16-lane row (= one env group).  Must be executed with all
 // lanes of the wave active (convergent code): an inactive source lane would feed garbage.
+// (row_ror, row_bcast, row_dpp: every source lane lies inside the row, so the result does not depend on bound_ctrl -- a source lane
+//  that is off would give 0 either way, the old value being 0; with it set the old value is never read, and the compiler does not
+//  have to put a 0 into the destination first: one v_mov_b32 less per broadcast or reduction stage that stays a v_mov_b32_dpp)
 template <int N>
 __device__ __forceinline__ float row_ror(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, false));
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x120 + N, 0xf, 0xf, true));
 }
 template <int K>
 __device__ __forceinline__ float row_bcast(float v) {  // value of lane K of the row, in every lane of the row
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + K, 0xf, 0xf, false));
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x150 + K, 0xf, 0xf, true));
 }
 template <int N>
 __device__ __forceinline__ float row_shr(float v) {  // lane i reads lane i-N of its row, 0 shifted in
@@ -136,7 +146,7 @@ __device__ __forceinline__ int lane_gather(int src4, int v) { return __builtin_a
 // state-parity check of tests/test_gpu_exact_contacts.py; tools/solver_trace.py shows it lane by lane).  Same four DPP adds as before.
 template <int CTRL>
 __device__ __forceinline__ float row_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, true));
 }
 __device__ __forceinline__ float gsum(float v) {
   v += row_dpp<0x140>(v);  // row_mirror: lane i <-> 15 - i

@@ -735,7 +735,7 @@
     for (int c = 0; c < ncon; c++) {
       const float* jb = JBROW(S, c);
       const float jn = jb[lane], j1 = jb[16 + lane], j2 = jb[32 + lane];
-      const f4 mt = ldv(S.con.cmeta[c]);
+      const f2 mt = ldv2(S.con.cmeta[c]);
       f4 xn[4], x1[4], x2[4];
 #pragma unroll
       for (int q = 0; q < 4; q++) { xn[q] = ldv(jb + 4 * q); x1[q] = ldv(jb + 16 + 4 * q); x2[q] = ldv(jb + 32 + 4 * q); }
@@ -756,14 +756,14 @@
   // above the first)
   auto hess_flip = [&](float (&hk)[G], int c, bool first_it) __attribute__((always_inline)) {
     const float* jb = JBROW(S, c);
-    const f4 fb = ldv(CFB(S, c));
+    const float fbw = CFB(S, c)[3];  // (the flags word alone: see ldv3)
     const float jn = jb[lane], j1 = jb[16 + lane], j2 = jb[32 + lane];
-    const f4 mt = ldv(S.con.cmeta[c]);
+    const f2 mt = ldv2(S.con.cmeta[c]);
     f4 xn[4], x1[4], x2[4];
 #pragma unroll
     for (int q = 0; q < 4; q++) { xn[q] = ldv(jb + 4 * q); x1[q] = ldv(jb + 16 + 4 * q); x2[q] = ldv(jb + 32 + 4 * q); }
     __builtin_amdgcn_sched_barrier(0);
-    const unsigned both = (unsigned)fb.w;
+    const unsigned both = (unsigned)fbw;
     const unsigned bits = both & 15u, old = first_it ? 15u : both >> 4;
     const float mu = mt.x, D = mt.y;
     const float a0 = D * (float)((int)(bits & 1u) - (int)(old & 1u)), a1 = D * (float)((int)(bits >> 1 & 1u) - (int)(old >> 1 & 1u));
@@ -797,13 +797,13 @@
           float gp = 0.0f;
           for (int c0 = G; c0 < ncon; c0 += 4) {
             float jn[4], j1[4], j2[4];
-            f4 fb[4];
+            f3 fb[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
               const int c = c0 + u < ncon ? c0 + u : c0;
               const float* jb = JBROW(S, c);
               jn[u] = jb[lane]; j1[u] = jb[16 + lane]; j2[u] = jb[32 + lane];
-              fb[u] = ldv(CFB(S, c));
+              fb[u] = ldv3(CFB(S, c));
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1752,13 +1752,13 @@
       const int ncon_g = (CPL > 1 && use_help && it > 0 && ncon > G) ? G : ncon;  // (three contacts per lane, from the second iteration on: the contacts above 16 are the helper wave's)
       for (int c0 = 0; c0 < ncon_g; c0 += 4) {  // four contacts per trip: one batch of reads, then the sums in contact order
         float jn[4], j1[4], j2[4];
-        f4 fb[4];
+        f3 fb[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) {
           const int c = c0 + u < ncon_g ? c0 + u : c0;
           const float* jb = JBROW(S, c);
           jn[u] = jb[lane]; j1[u] = jb[16 + lane]; j2[u] = jb[32 + lane];
-          fb[u] = ldv(CFB(S, c));
+          fb[u] = ldv3(CFB(S, c));
         }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -1849,14 +1849,16 @@
         const int c = __ffs(fm) - 1 + G * sl;
         const float* jb = JBROW(S, c);
         // every read of this contact in one batch, before any arithmetic (one LDS round trip)
-        const f4 fb = ldv(CFB(S, c));
+        const float fbw = CFB(S, c)[3];  // (the flags word alone: see ldv3)
         const float jn = jb[lane], j1 = jb[16 + lane], j2 = jb[32 + lane];
-        const f4 mt = ldv(S.con.cmeta[c]);
-        f4 xn[4], x1[4], x2[4];
+        const f2 mt = ldv2(S.con.cmeta[c]);
+        // (column 15 is the padding column: no solve reads entry 15 of a Hessian row, so the last quad is read as three floats -- see ldv3)
+        f4 xn[3], x1[3], x2[3];
 #pragma unroll
-        for (int q = 0; q < 4; q++) { xn[q] = ldv(jb + 4 * q); x1[q] = ldv(jb + 16 + 4 * q); x2[q] = ldv(jb + 32 + 4 * q); }
+        for (int q = 0; q < 3; q++) { xn[q] = ldv(jb + 4 * q); x1[q] = ldv(jb + 16 + 4 * q); x2[q] = ldv(jb + 32 + 4 * q); }
+        const f3 xn3 = ldv3(jb + 12), x13 = ldv3(jb + 28), x23 = ldv3(jb + 44);
         __builtin_amdgcn_sched_barrier(0);
-        const unsigned both = (unsigned)fb.w;
+        const unsigned both = (unsigned)fbw;
         const unsigned bits = both & 15u, old = it == 0 ? 15u : both >> 4;  // (first iteration: relative to all rows active)
         const float mu = mt.x, D = mt.y;
         const float a0 = D * (float)((int)(bits & 1u) - (int)(old & 1u)), a1 = D * (float)((int)(bits >> 1 & 1u) - (int)(old >> 1 & 1u));
@@ -1864,12 +1866,15 @@
         const float w0 = a0 + a1 + a2 + a3, w1 = mu * (a0 - a1), w2 = mu * (a2 - a3), w3 = mu * mu * (a0 + a1), w4 = mu * mu * (a2 + a3);
         const float tn = jn * w0 + j1 * w1 + j2 * w2, t1 = jn * w1 + j1 * w3, t2 = jn * w2 + j2 * w4;
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
+        for (int q = 0; q < 3; q++) {
           hkeep[4 * q + 0] += tn * xn[q].x + t1 * x1[q].x + t2 * x2[q].x;
           hkeep[4 * q + 1] += tn * xn[q].y + t1 * x1[q].y + t2 * x2[q].y;
           hkeep[4 * q + 2] += tn * xn[q].z + t1 * x1[q].z + t2 * x2[q].z;
           hkeep[4 * q + 3] += tn * xn[q].w + t1 * x1[q].w + t2 * x2[q].w;
         }
+        hkeep[12] += tn * xn3.x + t1 * x13.x + t2 * x23.x;
+        hkeep[13] += tn * xn3.y + t1 * x13.y + t2 * x23.y;
+        hkeep[14] += tn * xn3.z + t1 * x13.z + t2 * x23.z;
       }
       } else {
         // (three contacts per lane: this wave takes the flipped contacts of the first slot, the helper wave those of the others --
