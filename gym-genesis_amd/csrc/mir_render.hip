@@ -130,7 +130,11 @@ __device__ __forceinline__ float pack_rgb(const float* alb, float shade) {
 //         coordinate u/2 = (Nu0 + x NuX + y NuY) / d'z  (perspective-correct ratio of two affine functions)
 // BIN: one WAVE per env (lane = geom, ngeom <= 63) and the per-strip lists of the binned pixel kernel are written here as well
 // (see below); otherwise one thread per (env, geom).
-template <bool BIN>
+// AUX 1 / 2: the auxiliary record of mir_render_outputs -- every packed colour word (a box's entry faces, both checker colours of a plane)
+// is replaced by the AUX WORD of that face: its unit outward world-frame normal as RGB8 ((n + 1) / 2, clamped and rounded like the
+// colours) in bits 0-23 and the segmentation id in bits 24-31 (AUX 1: the geom's body, 2: the geom; < MIR_MAX_GEOM, so no aux
+// word equals NOHIT or AUX_SKY).  The pixel kernels draw with these words exactly as with colours.
+template <bool BIN, int AUX = 0>
 __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
   const int gi = blockIdx.x * blockDim.x + threadIdx.x;
   const int e = BIN ? gi >> 6 : gi / a.ngeom;
@@ -172,6 +176,10 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
     cu = cross(cr, cf);
   }
   const V3 L = {a.light[0], a.light[1], a.light[2]};
+  const unsigned aux_id = (unsigned)(AUX == 2 ? g : b) << 24;
+  auto aux_word = [&](V3 n) {
+    return __uint_as_float(to_u8((n.x + 1.0f) * 0.5f) | to_u8((n.y + 1.0f) * 0.5f) << 8 | to_u8((n.z + 1.0f) * 0.5f) << 16 | aux_id);
+  };
   const V3 rel = cp - c;
   const float* gs = m->g_size[g];
   const V3 h = gtype == MIR_GEOM_SPHERE ? V3{gs[0], gs[0], gs[0]} : (gtype == MIR_GEOM_CAPSULE ? V3{gs[0], gs[0], gs[0] + gs[1]} : V3{gs[0], gs[1], gs[2]});
@@ -257,7 +265,8 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
       const float f1 = hi ? c1 : c2, f2 = hi ? c2 : c1;
       a1[k][0] = f1 * d0[k]; a1[k][1] = f1 * dX[k]; a1[k][2] = f1 * dY[k];
       a2[k][0] = f2 * d0[k]; a2[k][1] = f2 * dX[k]; a2[k][2] = f2 * dY[k];
-      acol[k] = pack_rgb(alb, a.amb + a.dif * fmaxf(hi ? lk[k] : -lk[k], 0.0f));
+      if constexpr (AUX) acol[k] = aux_word(hi ? ax[k] : -1.0f * ax[k]);  // (the entry face: +k beyond it, -k otherwise)
+      else acol[k] = pack_rgb(alb, a.amb + a.dif * fmaxf(hi ? lk[k] : -lk[k], 0.0f));
       outm |= (hi || dp < 0.0f) ? 1u << k : 0u;
     }
     // the axes with the camera outside their slab first (a stable partition of x, y, z; six bits per case, no indexed memory)
@@ -283,8 +292,10 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
     const float nl = o.z < 0.0f ? -lk[2] : lk[2];  // the side of the plane the camera is on
     const float sh = a.amb + a.dif * fmaxf(nl, 0.0f);
     const float s = 0.5f * a.inv_chk;
-    q5 = f4{s * (o.x * F.z - o.z * F.x), s * (o.x * R.z - o.z * R.x), s * (o.x * U.z - o.z * U.x), pack_rgb(a.chk[0], sh)};
-    q6 = f4{s * (o.y * F.z - o.z * F.y), s * (o.y * R.z - o.z * R.y), s * (o.y * U.z - o.z * U.y), pack_rgb(a.chk[1], sh)};
+    float pw = 0.0f;  // (AUX: one word for the plane, the normal facing the camera; no checker)
+    if constexpr (AUX != 0) pw = aux_word(o.z < 0.0f ? -1.0f * ax[2] : ax[2]);
+    q5 = f4{s * (o.x * F.z - o.z * F.x), s * (o.x * R.z - o.z * R.x), s * (o.x * U.z - o.z * U.x), AUX ? pw : pack_rgb(a.chk[0], sh)};
+    q6 = f4{s * (o.y * F.z - o.z * F.y), s * (o.y * R.z - o.z * R.y), s * (o.y * U.z - o.z * U.y), AUX ? pw : pack_rgb(a.chk[1], sh)};
   }
   if (valid) {
     f4* o4 = reinterpret_cast<f4*>(a.prims + (size_t)i * PREC);
@@ -412,6 +423,44 @@ __device__ __forceinline__ void plane_region(const f4 ro, const f4 rf, const f4 
   }
 }
 
+// ---- auxiliary channels (mir_render_outputs) ------------------------------------------------------
+// The aux pixel paths draw with the aux record (k_render_setup<., 1 or 2>) and write, per pixel, from the winning reciprocal depth w and aux
+// word: depth = 1 / w (planar camera-z metres; 0 = sky), segmentation = the word's top byte as a signed id (AUX_SKY -> -1), normal =
+// the word's RGB8 (sky: 0 0 0).  Each channel is nullable (a wave-uniform branch).  4 consecutive pixels per call: one 16-byte store
+// for depth and for segmentation, 12 bytes for the normal (n < 4: the last pixels of a row whose width is not a multiple of 4).
+#define AUX_SKY 0xff000000u /* the aux word of a pixel that hit nothing: id -1, normal 0 0 0 */
+struct AuxOut {
+  float* depth;     // (.., H, W) or null
+  int* seg;         // (.., H, W) or null
+  uint8_t* normal;  // (.., H, W, 3) or null
+};
+__device__ __forceinline__ void store_aux(const AuxOut& o, size_t pix, const float (&w)[4], const unsigned (&wd)[4], int n) {
+  if (o.depth) {
+    float d[4];
+#pragma unroll
+    for (int p = 0; p < 4; p++) d[p] = w[p] > 0.0f ? 1.0f / w[p] : 0.0f;
+    if (n == 4) *reinterpret_cast<f4*>(o.depth + pix) = f4{d[0], d[1], d[2], d[3]};
+    else
+      for (int p = 0; p < n; p++) o.depth[pix + p] = d[p];
+  }
+  if (o.seg) {
+    if (n == 4) *reinterpret_cast<int4*>(o.seg + pix) = make_int4((int)wd[0] >> 24, (int)wd[1] >> 24, (int)wd[2] >> 24, (int)wd[3] >> 24);
+    else
+      for (int p = 0; p < n; p++) o.seg[pix + p] = (int)wd[p] >> 24;
+  }
+  if (o.normal) {
+    uint8_t* dst = o.normal + pix * 3;
+    if (n == 4) {
+      u3 v;
+      v.x = (wd[0] & 0xffffffu) | wd[1] << 24;
+      v.y = (wd[1] & 0xffffffu) >> 8 | wd[2] << 16;
+      v.z = (wd[2] & 0xffffffu) >> 16 | wd[3] << 8;
+      *reinterpret_cast<u3*>(dst) = v;
+    } else
+      for (int p = 0; p < n; p++) { dst[3 * p] = (uint8_t)wd[p]; dst[3 * p + 1] = (uint8_t)(wd[p] >> 8); dst[3 * p + 2] = (uint8_t)(wd[p] >> 16); }
+  }
+}
+
 // ---- pixels --------------------------------------------------------------------------------------
 // 256 threads = 4 waves stacked; a workgroup walks a 128-pixel-wide strip of `th` rows in 128 x 32 sub-tiles.
 // Per sub-tile: the image's primitives are culled against it (ordered ballot compaction into an LDS id list), then
@@ -422,7 +471,9 @@ __device__ __forceinline__ void plane_region(const f4 ro, const f4 rf, const f4 
 // of one sub-tile drains under the arithmetic of the next (a workgroup per sub-tile serialises the two: measured
 // 240 us of arithmetic + 150 us of stores = 390 us).  Primitive records are read with wave-uniform addresses
 // straight from global memory (scalar loads, amortised over 16 pixels per lane); LDS holds only the id list.
-__global__ __launch_bounds__(256) void mir_render_kernel(PixArgs a) {
+// (AUX: the aux pass of mir_render_outputs -- same drawing, the store writes the aux channels; see store_aux)
+template <bool AUX>
+__device__ __forceinline__ void render_generic(const PixArgs& a, const AuxOut& o) {
   __shared__ int s_ids[256];
   __shared__ int s_wcnt[4];
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -549,6 +600,17 @@ __global__ __launch_bounds__(256) void mir_render_kernel(PixArgs a) {
         }
       }
     }
+    if constexpr (AUX) {
+      const size_t ipix = (size_t)img * a.H * a.W;
+#pragma unroll
+      for (int r = 0; r < 4; r++) {
+        const int y = prow + 2 * r;
+        if (y > symax || px >= a.W) continue;
+        const float w[4] = {best[r][0][0], best[r][0][1], best[r][1][0], best[r][1][1]};
+        store_aux(o, ipix + (unsigned)y * (unsigned)a.W + (unsigned)px, w, col[r], fast ? 4 : min(4, a.W - px));
+      }
+      continue;
+    }
     // ---- packed RGB8 store: 4 pixels = 3 dwords per lane and region; not waited for.  The address is a uniform
     // 64-bit image base plus a 32-bit per-lane byte offset (saddr + voffset form, no 64-bit multiplies per store)
     uint8_t* __restrict__ ibase = a.pixels + (size_t)img * a.H * a.W * 3;
@@ -578,6 +640,8 @@ __global__ __launch_bounds__(256) void mir_render_kernel(PixArgs a) {
     }
   }
 }
+__global__ __launch_bounds__(256) void mir_render_kernel(PixArgs a) { render_generic<false>(a, AuxOut{}); }
+__global__ __launch_bounds__(256) void mir_render_kernel_aux(PixArgs a, AuxOut o) { render_generic<true>(a, o); }
 
 
 // The binned pixel kernel.  Same tiling (workgroup = 4 waves stacked on a 128-pixel-wide strip, walked in 128 x 32 sub-tiles, a
@@ -727,6 +791,80 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
   }
 }
 
+// The aux pass of the binned kernel (mir_render_outputs, per-env images): the same strips, lists, XCD-contiguous walk, box regions and
+// floor row expressions as mir_render_binned -- so it agrees with mir_render_kernel_aux bit for bit -- but everything is stored from the
+// BOX layout.  At 4 bytes per pixel a lane's 4 pixels are 16 bytes and the 8 lanes of one row of a 32-pixel column are one whole
+// 128-byte line, so the transpose through LDS that the 3-byte RGB pixels need is not needed here: no LDS, and the winning w never has
+// to leave its registers.  The floor is a row constant here in both w and word (one aux word per plane), so it costs one reciprocal
+// pair per lane and band; untouched columns store it directly.  (The normal channel, 3 bytes per pixel, goes out as 96-byte row pieces
+// per store instruction; the four columns of a band complete its 384-byte rows.)
+__global__ __launch_bounds__(256) void mir_render_binned_aux(PixArgs a, AuxOut o) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const unsigned wid = blockIdx.x, wseq = (wid & 7u) * (gridDim.x >> 3) + (wid >> 3);
+  if (wseq >= (unsigned)a.nwg) return;
+  const unsigned nst = (unsigned)(a.nsx * a.nsy), uimg = wseq / nst, st = (wseq % nst + 7u * uimg) % nst;
+  const unsigned ssx = st % (unsigned)a.nsx, ssy = st / (unsigned)a.nsx;
+  const int tx0 = ssx * TW, sy0 = ssy * a.th, img = uimg;
+  const int* bin = a.bins + ((size_t)uimg * nst + st) * BINW;
+  const int ent = bin[lane];
+  const int pxa = tx0 + 4 * (lane & 7);         // box layout: 4 pixels of row wy0 + lane / 8, in the columns pxa + 32r
+  const float* __restrict__ prims = a.prims + (size_t)img * a.nprim * PREC;
+  const int symax = min(sy0 + a.th, a.H) - 1;
+  const int hdr = __builtin_amdgcn_readfirstlane(ent);
+  const int cnt = hdr & 255;
+  const bool floor = (hdr >> 8) & 1;
+  const cf4* frec = (const cf4*)(uintptr_t)prims;
+  const float f_oz = frec[0].z, f_fz = frec[1].z, f_uz = frec[3].z;
+  const unsigned fword = __float_as_uint(frec[5].w);
+  const size_t ipix = (size_t)img * a.H * a.W;
+
+  for (int ty0 = sy0; ty0 <= symax; ty0 += 32) {
+    const int wy0 = ty0 + 8 * wv;
+    if (wy0 > symax) break;
+    unsigned long long cm[4];
+    {
+      const int ymin = (ent >> 6) & 0x7ff, ymax = (ent >> 17) & 0x7ff;
+      const bool on = lane >= 1 && lane <= cnt && !(ymax < wy0 || ymin > wy0 + 7);
+#pragma unroll
+      for (int r = 0; r < 4; r++) cm[r] = __ballot(on && ((ent >> (28 + r)) & 1));
+    }
+    const int row = wy0 + (lane >> 3);
+    const float ya = a.y0 + (float)row * a.dy;
+    float tb = 0.0f;  // the floor on this lane's row (reciprocal depth, 0 = nothing) and its word
+    unsigned fw = a.sky;
+    if (floor) {
+      const float t1 = __builtin_amdgcn_rcpf(fmaf(ya, f_uz, f_fz)) * (-f_oz);
+      tb = t1 > 1e-6f ? __builtin_amdgcn_rcpf(t1) : 0.0f;
+      fw = t1 > 1e-6f ? fword : a.sky;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+      float w[4] = {tb, tb, tb, tb};
+      unsigned wd[4] = {fw, fw, fw, fw};
+      const int x = pxa + 32 * r;
+      if (cm[r]) {
+        const f2 xsa[2] = {f2{a.x0 + (float)x * a.dx, a.x0 + (float)(x + 1) * a.dx}, f2{a.x0 + (float)(x + 2) * a.dx, a.x0 + (float)(x + 3) * a.dx}};
+        f2 best[2] = {f2{tb, tb}, f2{tb, tb}};
+        unsigned ca[4] = {NOHIT, NOHIT, NOHIT, NOHIT};
+        for (unsigned long long m = cm[r]; m; m &= m - 1) {
+          const int e = __builtin_amdgcn_readlane(ent, __builtin_ctzll(m));
+          const cf4* rec = (const cf4*)(uintptr_t)(prims + (size_t)(e & 63) * PREC);
+          const f4 ro = rec[0], rf = rec[1], rr = rec[2], ru = rec[3], q5 = rec[5], q6 = rec[6];
+          if ((__float_as_int(ro.w) & 255) == MIR_GEOM_BOX) box_region(ro, rf, rr, ru, rec[4], rec[7], q5, ya, xsa, best, ca);
+          else plane_region(ro, rf, rr, ru, q5, q6, ya, xsa, best, ca);
+        }
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+          const bool hit = ca[p] != NOHIT;
+          wd[p] = hit ? ca[p] : wd[p];
+          w[p] = hit ? best[p >> 1][p & 1] : w[p];
+        }
+      }
+      if (row <= symax && x < a.W) store_aux(o, ipix + (unsigned)row * (unsigned)a.W + (unsigned)x, w, wd, 4);
+    }
+  }
+}
+
 // ---- the global view of MANY envs (camera_capture_mode="global", the registry's default; GenesisEnv.render()) ------------------------
 // One image, B x ngeom primitives, each a few hundred pixels of it.  The tiled kernels walk a tile's whole primitive list: 25 workgroups
 // of a 480 x 640 image each cull 82 000 records of 4096 envs -- 17.8 ms.  Here k_render_setup lists the boxes that can be on screen as work
@@ -744,6 +882,7 @@ struct SplatArgs {
   int W, H, nprim, ngeom;
   float x0, dx, y0, dy;
   unsigned sky;
+  AuxOut aux;                // k_global_resolve<true>: the aux channels (mir_render_outputs)
 };
 
 // one box, the 32 x 8 blocks b = first, first + stride, ... of its rectangle (row-major), lane = pixel
@@ -794,6 +933,8 @@ __global__ __launch_bounds__(256) void k_global_splat(SplatArgs a) {
 }
 
 // lane = 4 consecutive pixels of one row (one dwordx3 store when the width allows)
+// (AUX: the aux pass of mir_render_outputs; the keys carry aux words, the store writes the aux channels)
+template <bool AUX = false>
 __global__ __launch_bounds__(256) void k_global_resolve(SplatArgs a) {
   // The buffer is handed back CLEAN: every key read here is zeroed again (the few that were written: most pixels show the floor), and
   // the work-item count goes back to zero -- the next render starts without a memset of 2.4 MB (a launch of 5 us).
@@ -849,6 +990,10 @@ __global__ __launch_bounds__(256) void k_global_resolve(SplatArgs a) {
       }
     }
   }
+  if constexpr (AUX) {
+    store_aux(a.aux, (size_t)py * a.W + px, best, col, (a.W & 3) == 0 ? 4 : min(4, a.W - px));
+    return;
+  }
   uint8_t* dst = a.pixels + ((size_t)py * a.W + px) * 3;
   if ((a.W & 3) == 0) {
     u3 v;
@@ -862,6 +1007,7 @@ __global__ __launch_bounds__(256) void k_global_resolve(SplatArgs a) {
       if (px + p < a.W) { dst[3 * p] = (uint8_t)col[p]; dst[3 * p + 1] = (uint8_t)(col[p] >> 8); dst[3 * p + 2] = (uint8_t)(col[p] >> 16); }
   }
 }
+
 
 void norm3(const double* v, double* o) {
   const double n = std::sqrt(v[0] * v[0] + v[1] * v[1] + v[2] * v[2]);
@@ -877,10 +1023,12 @@ void cross3(const double* a, const double* b, double* o) {
 
 extern "C" int mir_visual_sizeof(void) { return (int)sizeof(MirVisualSpec); }
 
-// shared body of mir_render / mir_render_cams: cam_pos == null -> one camera (cam->pos / lookat / up) for all images
+// shared body of mir_render / mir_render_cams / mir_render_outputs: cam_pos == null -> one camera (cam->pos / lookat / up) for all
+// images; aux != null -> the aux pass of mir_render_outputs (aux record, aux pixel kernels; `pixels` unused)
 static int render_impl(MirHandle h, const MirCameraSpec* cam, const MirVisualSpec* vis, int32_t mode, const float* env_offset,
-                       const float* cam_pos, const float* cam_look, const float* cam_up, uint8_t* pixels, void* stream) {
-  if (!h || !cam || !vis || !pixels) return mir_set_error(MIR_E_INVALID, "mir_render: null argument");
+                       const float* cam_pos, const float* cam_look, const float* cam_up, uint8_t* pixels, void* stream,
+                       const AuxOut* aux = nullptr, int seg_level = 0) {
+  if (!h || !cam || !vis || (!pixels && !aux)) return mir_set_error(MIR_E_INVALID, "mir_render: null argument");
   if (vis->struct_size != (int)sizeof(MirVisualSpec)) return mir_set_error(MIR_E_INVALID, "mir_render: MirVisualSpec size mismatch");
   if (cam->width <= 0 || cam->height <= 0 || !(cam->fov_deg > 0.0 && cam->fov_deg < 180.0))
     return mir_set_error(MIR_E_INVALID, "mir_render: bad camera (res / fov)");
@@ -891,6 +1039,8 @@ static int render_impl(MirHandle h, const MirCameraSpec* cam, const MirVisualSpe
   // renders 2400 x 480 x 640 x 3 = 3.3 GB)
   if ((unsigned long long)cam->width * (unsigned long long)cam->height * 3ull >= (1ull << 32))
     return mir_set_error(MIR_E_CAPACITY, "mir_render: one image must stay below 2^32 bytes (width x height x 3)");
+  if (aux && (unsigned long long)cam->width * (unsigned long long)cam->height * 4ull >= (1ull << 32))
+    return mir_set_error(MIR_E_CAPACITY, "mir_render_outputs: one depth / segmentation image must stay below 2^32 bytes (width x height x 4)");
   if (mode == MIR_RENDER_PER_ENV && h->B > 65535) return mir_set_error(MIR_E_CAPACITY, "mir_render: at most 65535 per-env images per call");
   double f[3] = {1, 0, 0}, r[3] = {0, 1, 0}, u[3] = {0, 0, 1};
   if (!cam_pos) {
@@ -944,8 +1094,9 @@ static int render_impl(MirHandle h, const MirCameraSpec* cam, const MirVisualSpe
     pa.dy = (float)(-2.0 * ty / cam->height); pa.y0 = (float)(ty - ty / cam->height);
     {
       auto u8 = [](double c) { return (unsigned)(std::fmin(std::fmax(c, 0.0), 1.0) * 255.0 + 0.5); };
-      pa.sky = u8(vis->sky_rgb[0]) | u8(vis->sky_rgb[1]) << 8 | u8(vis->sky_rgb[2]) << 16;
+      pa.sky = aux ? AUX_SKY : u8(vis->sky_rgb[0]) | u8(vis->sky_rgb[1]) << 8 | u8(vis->sky_rgb[2]) << 16;
     }
+    const AuxOut ao = aux ? *aux : AuxOut{};
     pa.th = h->render_th > 0 ? h->render_th : TH;
     const int nimg = mode == MIR_RENDER_GLOBAL ? 1 : B;
     // Per-env images (short primitive lists) take the binned kernel; the global view of all envs (one long list), widths
@@ -965,10 +1116,12 @@ static int render_impl(MirHandle h, const MirCameraSpec* cam, const MirVisualSpe
       BinArgs ba;
       ba.prims = h->prims; ba.bins = h->bins; ba.W = cam->width; ba.H = cam->height; ba.nprim = pa.nprim; ba.th = pa.th;
       ba.nsx = nsx; ba.nsy = nsy; ba.nimg = nimg;
-      hipLaunchKernelGGL(k_render_setup<true>, dim3((B * 64 + 255) / 256), dim3(256), 0, st, sa, ba);
+      if (aux) hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_level ? k_render_setup<true, 2> : k_render_setup<true, 1>), dim3((B * 64 + 255) / 256), dim3(256), 0, st, sa, ba);
+      else hipLaunchKernelGGL(k_render_setup<true>, dim3((B * 64 + 255) / 256), dim3(256), 0, st, sa, ba);
       pa.bins = h->bins;
       pa.nsx = nsx; pa.nsy = nsy; pa.nwg = nimg * nsx * nsy;
-      hipLaunchKernelGGL(mir_render_binned, dim3((unsigned)((pa.nwg + 7) & ~7)), dim3(256), 0, st, pa);
+      if (aux) hipLaunchKernelGGL(mir_render_binned_aux, dim3((unsigned)((pa.nwg + 7) & ~7)), dim3(256), 0, st, pa, ao);
+      else hipLaunchKernelGGL(mir_render_binned, dim3((unsigned)((pa.nwg + 7) & ~7)), dim3(256), 0, st, pa);
     } else if (mode == MIR_RENDER_GLOBAL && pa.nprim > 512 && !h->render_generic) {
       // the global view of many envs: one workgroup per box into a depth / colour buffer, then a resolve pass (see k_global_splat)
       const size_t npix = (size_t)cam->width * cam->height, need = npix;
@@ -995,15 +1148,23 @@ static int render_impl(MirHandle h, const MirCameraSpec* cam, const MirVisualSpe
         (void)hipMemsetAsync(h->vis, 0, VIS_HDR * sizeof(unsigned), st);
       }
       sa.vis = h->vis;
-      hipLaunchKernelGGL(k_render_setup<false>, dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
+      if (aux) hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_level ? k_render_setup<false, 2> : k_render_setup<false, 1>), dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
+      else hipLaunchKernelGGL(k_render_setup<false>, dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
       SplatArgs sp;
       sp.prims = h->prims; sp.zbuf = h->zbuf; sp.vis = h->vis; sp.pixels = pixels; sp.W = cam->width; sp.H = cam->height; sp.nprim = pa.nprim; sp.ngeom = ng;
-      sp.x0 = pa.x0; sp.dx = pa.dx; sp.y0 = pa.y0; sp.dy = pa.dy; sp.sky = pa.sky;
+      sp.x0 = pa.x0; sp.dx = pa.dx; sp.y0 = pa.y0; sp.dy = pa.dy; sp.sky = pa.sky; sp.aux = ao;
       hipLaunchKernelGGL(k_global_splat, dim3(GLOBAL_SPLAT_GRID), dim3(256), 0, st, sp);
-      hipLaunchKernelGGL(k_global_resolve, dim3((cam->width + 255) / 256, (cam->height + 3) / 4), dim3(256), 0, st, sp);
+      if (aux) hipLaunchKernelGGL(k_global_resolve<true>, dim3((cam->width + 255) / 256, (cam->height + 3) / 4), dim3(256), 0, st, sp);
+      else hipLaunchKernelGGL(k_global_resolve<false>, dim3((cam->width + 255) / 256, (cam->height + 3) / 4), dim3(256), 0, st, sp);
     } else {
-      hipLaunchKernelGGL(k_render_setup<false>, dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
-      hipLaunchKernelGGL(mir_render_kernel, dim3((cam->width + TW - 1) / TW, (cam->height + pa.th - 1) / pa.th, nimg), dim3(256), 0, st, pa);
+      const dim3 grid((cam->width + TW - 1) / TW, (cam->height + pa.th - 1) / pa.th, nimg);
+      if (aux) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_level ? k_render_setup<false, 2> : k_render_setup<false, 1>), dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
+        hipLaunchKernelGGL(mir_render_kernel_aux, grid, dim3(256), 0, st, pa, ao);
+      } else {
+        hipLaunchKernelGGL(k_render_setup<false>, dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
+        hipLaunchKernelGGL(mir_render_kernel, grid, dim3(256), 0, st, pa);
+      }
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = mir_set_error(MIR_E_HIP, hipGetErrorString(e));
@@ -1028,4 +1189,28 @@ extern "C" int mir_render_cams(MirHandle h, const MirCameraSpec* cam, const MirV
                                const float* cam_up, uint8_t* pixels, void* stream) {
   if (!cam_pos || !cam_lookat) return mir_set_error(MIR_E_INVALID, "mir_render_cams: null camera arrays");
   return render_impl(h, cam, vis, MIR_RENDER_PER_ENV, nullptr, cam_pos, cam_lookat, cam_up, pixels, stream);
+}
+
+extern "C" int mir_render_outputs(MirHandle h, const MirCameraSpec* cam, const MirVisualSpec* vis, int32_t mode, const float* env_offset,
+                                  const float* cam_pos, const float* cam_lookat, const float* cam_up, const MirRenderOutputs* out, void* stream) {
+  if (!out) return mir_set_error(MIR_E_INVALID, "mir_render_outputs: null outputs");
+  if (out->struct_size != (int)sizeof(MirRenderOutputs)) return mir_set_error(MIR_E_INVALID, "mir_render_outputs: MirRenderOutputs size mismatch");
+  if (out->seg_level != 0 && out->seg_level != 1) return mir_set_error(MIR_E_INVALID, "mir_render_outputs: seg_level must be 0 (link) or 1 (geom)");
+  const bool want_aux = out->depth || out->segmentation || out->normal;
+  if (!out->rgb && !want_aux) return mir_set_error(MIR_E_INVALID, "mir_render_outputs: every channel is null");
+  if ((cam_pos != nullptr) != (cam_lookat != nullptr)) return mir_set_error(MIR_E_INVALID, "mir_render_outputs: cam_pos and cam_lookat go together");
+  if (cam_pos && mode != MIR_RENDER_PER_ENV) return mir_set_error(MIR_E_INVALID, "mir_render_outputs: per-env cameras need mode PER_ENV");
+  if (((uintptr_t)out->depth | (uintptr_t)out->segmentation | (uintptr_t)out->normal) & 15u)
+    return mir_set_error(MIR_E_INVALID, "mir_render_outputs: depth / segmentation / normal must be 16-byte aligned");
+  // (the 4-byte limit first: a call that cannot draw its aux channels draws nothing)
+  if (want_aux && cam && (unsigned long long)cam->width * (unsigned long long)cam->height * 4ull >= (1ull << 32))
+    return mir_set_error(MIR_E_CAPACITY, "mir_render_outputs: one depth / segmentation image must stay below 2^32 bytes (width x height x 4)");
+  const float* off = cam_pos ? nullptr : env_offset;
+  int rc = MIR_OK;
+  if (out->rgb) rc = render_impl(h, cam, vis, mode, off, cam_pos, cam_lookat, cam_up, out->rgb, stream);
+  if (rc == MIR_OK && want_aux) {
+    const AuxOut ao{out->depth, out->segmentation, out->normal};
+    rc = render_impl(h, cam, vis, mode, off, cam_pos, cam_lookat, cam_up, nullptr, stream, &ao, out->seg_level);
+  }
+  return rc;
 }

@@ -117,6 +117,8 @@ def load_library() -> C.CDLL:
     lib.mir_visual_sizeof.restype = C.c_int
     lib.mir_render_cams.argtypes = [vp, C.POINTER(MirCameraSpec), C.POINTER(MirVisualSpec), vp, vp, vp, vp, vp]
     lib.mir_render_cams.restype = C.c_int
+    lib.mir_render_outputs.argtypes = [vp, C.POINTER(MirCameraSpec), C.POINTER(MirVisualSpec), i32, vp, vp, vp, vp, C.POINTER(MirRenderOutputs), vp]
+    lib.mir_render_outputs.restype = C.c_int
     lib.mir_inverse_kinematics.argtypes = [vp, i32, vp, vp, vp, C.POINTER(MirIkOptions), vp, vp, vp]
     lib.mir_inverse_kinematics.restype = C.c_int
     lib.mir_inverse_kinematics_rows.argtypes = [vp, i32, C.POINTER(MirIkRows), vp, vp, vp, C.POINTER(MirIkOptions), vp, vp, vp]
@@ -150,6 +152,15 @@ def _bind_fast(lib) -> None:
     addr = lambda f: C.cast(f, C.c_void_p).value  # noqa: E731
     _mirfast.bind(addr(lib.mir_step_prepare), addr(lib.mir_step_go), addr(lib.mir_step_end))
     _fast = _mirfast
+
+
+class MirRenderOutputs(C.Structure):
+    """mir_render_outputs' channel table (include/mirigid.h): device pointers, each nullable."""
+    _fields_ = [("struct_size", C.c_int32), ("seg_level", C.c_int32), ("rgb", C.c_void_p), ("depth", C.c_void_p),
+                ("segmentation", C.c_void_p), ("normal", C.c_void_p)]
+
+
+SEG_LEVELS = {"link": 0, "geom": 1}
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -670,6 +681,50 @@ class MirScene(StepHelpers):
         u = None if cam_up is None else self._f32(cam_up, 3)
         self._check(self.lib.mir_render_cams(self.h, C.byref(cam), C.byref(vis), _ptr(p), _ptr(l), _ptr(u), _ptr(out), self._stream()))
         return out
+
+    def render_outputs(self, cam: MirCameraSpec, vis: MirVisualSpec, mode: int = 0, env_offset: Optional[torch.Tensor] = None,
+                       cam_pos=None, cam_lookat=None, cam_up=None, rgb: bool = True, depth: bool = False, segmentation: bool = False,
+                       normal: bool = False, seg_level: str = "link", out=None):
+        """(rgb, depth, segmentation, normal) device tensors of the current state, Genesis's order (mir_render_outputs); None for a
+        channel not asked for.  Shapes (B,H,W[,3]) per env, (H,W[,3]) with mode=1.  rgb: uint8, what render() / render_cams() draw;
+        depth: float32 planar camera-z metres, 0 = sky; segmentation: int32 body ("link") or geom ("geom") index, -1 = sky; normal:
+        uint8 world-frame normal as round((n + 1) / 2 * 255), sky 0 0 0.  cam_pos / cam_lookat (B,3): per-env cameras as in
+        render_cams() (mode 0 only).  out: optional 4-tuple of tensors (or None) to write into."""
+        if seg_level not in SEG_LEVELS:
+            raise ValueError(f"seg_level must be one of {sorted(SEG_LEVELS)}, got {seg_level!r}")
+        if cam_pos is not None and mode != 0:
+            raise ValueError("per-env cameras (cam_pos) need mode=0")
+        if (cam_pos is None) != (cam_lookat is None):
+            raise ValueError("cam_pos and cam_lookat go together")
+        base = (cam.height, cam.width) if mode == 1 else (self.num_envs, cam.height, cam.width)
+        given = tuple(out) if out is not None else (None,) * 4
+        if len(given) != 4:
+            raise ValueError("out must be a 4-tuple (rgb, depth, segmentation, normal)")
+
+        def buf(k, want, shape, dtype):
+            if not want:
+                return None
+            t = given[k]
+            if t is None:
+                return torch.empty(shape, dtype=dtype, device=self.device)
+            if tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous():
+                raise ValueError(f"out[{k}] must be a contiguous {dtype} tensor of shape {shape}")
+            return t
+
+        r = buf(0, rgb, base + (3,), torch.uint8)
+        d = buf(1, depth, base, torch.float32)
+        sg = buf(2, segmentation, base, torch.int32)
+        n = buf(3, normal, base + (3,), torch.uint8)
+        if r is None and d is None and sg is None and n is None:
+            raise ValueError("render_outputs: no channel asked for")
+        off = None if env_offset is None or cam_pos is not None else self._f32(env_offset, 3)
+        p = None if cam_pos is None else self._f32(cam_pos, 3)
+        l = None if cam_lookat is None else self._f32(cam_lookat, 3)
+        u = None if cam_up is None else self._f32(cam_up, 3)
+        o = MirRenderOutputs(C.sizeof(MirRenderOutputs), SEG_LEVELS[seg_level], _ptr(r), _ptr(d), _ptr(sg), _ptr(n))
+        self._check(self.lib.mir_render_outputs(self.h, C.byref(cam), C.byref(vis), int(mode), _ptr(off), _ptr(p), _ptr(l), _ptr(u),
+                                                C.byref(o), self._stream()))
+        return r, d, sg, n
 
     def inverse_kinematics(self, link_body: int, pos, quat=None, init_qpos=None, return_error: bool = False, **opts):
         """Batched damped-least-squares IK (mir_inverse_kinematics): (B, n_arm) joint positions that bring body

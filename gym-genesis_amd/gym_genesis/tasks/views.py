@@ -189,7 +189,7 @@ class CameraView:
     (/root/reference/gym_genesis/tasks/franka/cube_pick.py:56-63,166-176; /root/reference/gym_genesis/env.py:97-98).
     ``render()`` draws ALL envs of this process at their grid offsets from the camera's current pose, like the
     reference's single shared scene, and returns ``(rgb, None, None, None)`` with ``rgb`` a NumPy uint8 (H, W, 3)
-    array (Genesis returns rgb, depth, segmentation, normal).  ``render_envs()`` is the batched per-env image
+    array; depth, segmentation and normal images on request (Genesis returns rgb, depth, segmentation, normal).  ``render_envs()`` is the batched per-env image
     tensor used for the ``pixels`` observation: one launch instead of the reference's B renders."""
 
     def __init__(self, mir, builder, scene, res, pos, lookat, fov, up=(0.0, 0.0, 1.0)):
@@ -243,9 +243,33 @@ class CameraView:
         frame; the link-mounted wrist cameras)."""
         return self._mir.render_cams(self._spec(self._home[0], self._home[1]), self._vis, pos, lookat, up)
 
-    def render(self, rgb=True, depth=False, segmentation=False, normal=False):
-        if depth or segmentation or normal:
-            raise NotImplementedError("only the rgb output of cam.render() is on the reference's path (env.py:98)")
+    def render(self, rgb=True, depth=False, segmentation=False, normal=False, segmentation_level="link"):
+        """Genesis's ``cam.render(rgb, depth, segmentation, normal)`` of the global view: NumPy arrays (rgb (H,W,3) uint8, depth (H,W)
+        float32 planar camera-z metres with 0 for sky, segmentation (H,W) int32 body ("link") or geom ("geom") index with -1 for sky,
+        normal (H,W,3) uint8), None for a channel not asked for.  The rgb image is the one of an rgb-only call (reused and recorded
+        alike); the other channels come from one further pass (mir_render_outputs) and are never recorded."""
+        if not (depth or segmentation or normal):
+            return self._to_host(self._global_rgb()), None, None, None
+        img = self._global_rgb() if rgb else None
+        _, d, sg, n = self._mir.render_outputs(self._spec(self.pos, self.lookat), self._vis, mode=1, env_offset=self._offsets, rgb=False,
+                                               depth=depth, segmentation=segmentation, normal=normal, seg_level=segmentation_level)
+        return tuple(None if t is None else self._to_host(t, slot=k) for k, t in enumerate((img, d, sg, n)))
+
+    def render_batch(self, rgb=True, depth=False, segmentation=False, normal=False, pos=None, lookat=None, cam_pos=None, cam_lookat=None,
+                     cam_up=None, segmentation_level="link"):
+        """Per-env images as device tensors, (rgb, depth, segmentation, normal) with the channels of render(), each (B,H,W[,3]) or None.
+        Env i alone, seen from `pos` -> `lookat` relative to its origin (defaults: the creation pose, as render_envs()), or -- with
+        cam_pos / cam_lookat (B,3), cam_up optional -- from its OWN camera, as render_cams() (the wrist cameras)."""
+        if cam_pos is not None:
+            if cam_lookat is None:
+                raise ValueError("render_batch: cam_pos needs cam_lookat")
+            spec = self._spec(self._home[0], self._home[1])
+        else:
+            spec = self._spec(self._home[0] if pos is None else pos, self._home[1] if lookat is None else lookat)
+        return self._mir.render_outputs(spec, self._vis, mode=0, cam_pos=cam_pos, cam_lookat=cam_lookat, cam_up=cam_up, rgb=rgb, depth=depth,
+                                        segmentation=segmentation, normal=normal, seg_level=segmentation_level)
+
+    def _global_rgb(self):
         # (the reference's README loop calls env.render() right behind an env.step() whose pixels observation IS this image: nothing has
         #  moved since -- mir_get_state_version -- so it is copied out, not drawn again; the caller gets a fresh array either way)
         last = self.__dict__.get("_last_global")
@@ -257,22 +281,23 @@ class CameraView:
             self._record(img)  # (a frame per call, as in Genesis)
         else:
             img = self.render_global()
-        return self._to_host(img), None, None, None
+        return img
 
     _PIN_MAX = 8  # pinned image buffers a camera lends out at a time
 
-    def _to_host(self, img) -> np.ndarray:
+    def _to_host(self, img, slot=0) -> np.ndarray:
         """A fresh NumPy array of a device image.  The array IS a pinned buffer the device copies into (27 us for 480 x 640): the camera
         lends out up to `_PIN_MAX` of them and takes one back when its array is garbage-collected (`weakref.finalize`; a view keeps its
         base alive, so nothing the caller still holds is ever reused) -- the README loop drops each frame before it asks for the next and
         never pays a host memcpy.  A caller that keeps more frames than that gets copies from a staging buffer (60 - 74 us; `img.cpu()`,
         which this replaces, copies into pageable memory: 67 us per image when the frames are dropped, 224 us when they are kept and
-        every array is new pages the driver has to fault in and pin)."""
+        every array is new pages the driver has to fault in and pin).  `slot` k > 0: the k-th channel of render() (depth,
+        segmentation, normal), lent from a pool of its own."""
         if not img.is_cuda:
             return img.cpu().numpy()
         import weakref
 
-        d = self.__dict__
+        d = self.__dict__ if slot == 0 else self.__dict__.setdefault("_pin_slots", {}).setdefault(slot, {})
         key = (tuple(img.shape), img.dtype)
         if d.get("_pin_key") != key:
             d["_pin_key"], d["_pin_pool"], d["_pin_stage"] = key, [], None   # (buffers of another size still out die with their arrays)
@@ -289,11 +314,11 @@ class CameraView:
         torch.cuda.current_stream(img.device).synchronize()
         arr = buf.numpy()
         d["_pin_out"] = d.get("_pin_out", 0) + 1
-        weakref.finalize(arr, self._pin_back, buf, key)
+        weakref.finalize(arr, self._pin_back, buf, key, slot)
         return arr
 
-    def _pin_back(self, buf, key) -> None:
-        d = self.__dict__
+    def _pin_back(self, buf, key, slot=0) -> None:
+        d = self.__dict__ if slot == 0 else self.__dict__["_pin_slots"][slot]
         d["_pin_out"] = d.get("_pin_out", 1) - 1
         if d.get("_pin_key") == key and len(d["_pin_pool"]) < self._PIN_MAX:
             d["_pin_pool"].append(buf)

@@ -467,6 +467,32 @@ int mir_render(MirHandle h, const MirCameraSpec* cam, const MirVisualSpec* vis, 
 int mir_render_cams(MirHandle h, const MirCameraSpec* cam, const MirVisualSpec* vis, const float* cam_pos, const float* cam_lookat,
                     const float* cam_up, uint8_t* pixels, void* stream);
 
+/* The four images of Genesis's cam.render(rgb, depth, segmentation, normal) in one call.  Every pointer is a device pointer and
+ * nullable; the shapes are those of mir_render: (B,H,W[,3]) per env, (H,W[,3]) in mode GLOBAL.
+ *   rgb:          uint8 (..,3), exactly what mir_render / mir_render_cams write (the same kernels).
+ *   depth:        float32, metres along the camera's forward axis (planar z-depth, not the distance along the ray); sky = 0.0.
+ *   segmentation: int32, sky = -1, else the id of the visible surface: seg_level 0 ("link") = the geom's body index in the scene
+ *                 (static world geoms, floor and slab, are body 0), seg_level 1 ("geom") = the geom's index in the scene's geom table.
+ *                 In mode GLOBAL the id carries no env index.
+ *   normal:       uint8 (..,3), the unit outward world-frame normal of the visible face as round((n + 1) / 2 * 255), clamped like the
+ *                 colours; a plane's normal is the one facing the camera; sky = 0 0 0.
+ * Spheres and capsules are drawn as their bounding boxes, as in RGB, so their depth and normals are those of the box.
+ * rgb goes through the kernels of mir_render; depth / segmentation / normal through ONE further pass that writes any subset of them.
+ * mode, env_offset and cam_pos / cam_lookat / cam_up mean what they mean for mir_render and mir_render_cams (per-env cameras: cam_pos
+ * and cam_lookat non-null, mode PER_ENV).  MIR_E_INVALID: struct_size != sizeof(MirRenderOutputs), seg_level not 0 / 1, every
+ * channel null, depth / segmentation / normal not 16-byte aligned, and what mir_render refuses; MIR_E_CAPACITY: width x height x 4
+ * reaches 2^32 bytes while an aux channel is asked for (checked before anything is drawn), and what mir_render refuses. */
+typedef struct MirRenderOutputs {
+  int32_t struct_size;   /* = sizeof(MirRenderOutputs) */
+  int32_t seg_level;     /* 0 = link, 1 = geom */
+  uint8_t* rgb;          /* nullable: exactly what mir_render / mir_render_cams write */
+  float* depth;          /* nullable */
+  int32_t* segmentation; /* nullable */
+  uint8_t* normal;       /* nullable */
+} MirRenderOutputs;
+int mir_render_outputs(MirHandle h, const MirCameraSpec* cam, const MirVisualSpec* vis, int32_t mode, const float* env_offset,
+                       const float* cam_pos, const float* cam_lookat, const float* cam_up, const MirRenderOutputs* out, void* stream);
+
 /* ---- batched inverse kinematics ---------------------------------------------------
  * robot.inverse_kinematics(link=eef, pos=(B,3), quat=(B,4), init_qpos=..., envs_idx=...) -> (B, n_dofs)
  *      examples/franka/pick_cube_state.py:46-51, examples/franka/stack_cube_state.py:78-83
