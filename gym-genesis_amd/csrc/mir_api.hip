@@ -341,6 +341,7 @@ int create_device_state(MirScene* h, const GeomTab& gt, const float* row, size_t
   HIPCHK(hipMemcpy(h->dm64, &h->hm64, sizeof(DevModel64), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->dpt, &h->pt, sizeof(PlumbTab), hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(h->dgeom, &gt, sizeof(GeomTab), hipMemcpyHostToDevice));
+  for (int g = 0; g < gt.ngeom; g++) h->render_round |= gt.g_type[g] == MIR_GEOM_SPHERE || gt.g_type[g] == MIR_GEOM_CAPSULE;
   HIPCHK(hipMemcpy(h->scratch_row, row, row_bytes, hipMemcpyHostToDevice));
   hipLaunchKernelGGL(k_fill_rows, dim3(nblk((long)B * qst)), dim3(TPB), 0, 0, h->qpos, h->scratch_row, (int)qst, h->B);
   HIPCHK(hipGetLastError());

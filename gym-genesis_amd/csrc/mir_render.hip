@@ -134,7 +134,14 @@ __device__ __forceinline__ float pack_rgb(const float* alb, float shade) {
 // is replaced by the AUX WORD of that face: its unit outward world-frame normal as RGB8 ((n + 1) / 2, clamped and rounded like the
 // colours) in bits 0-23 and the segmentation id in bits 24-31 (AUX 1: the geom's body, 2: the geom; < MIR_MAX_GEOM, so no aux
 // word equals NOHIT or AUX_SKY).  The pixel kernels draw with these words exactly as with colours.
-template <bool BIN, int AUX = 0>
+// ROUND (MIR_VIS_ROUND_GEOMS, chosen by render_impl only for scenes that have a sphere or capsule): spheres and capsules get a ROUND record
+// instead of their bounding box's (type word MIR_GEOM_SPHERE / MIR_GEOM_CAPSULE; everything in the geom frame, capsule axis z, a sphere is
+// a capsule with hl = 0):
+//   q0 o' | type   q1 F' | xmin   q2 R' | xmax   q3 U' | ymin   q4 r^2, hl, 1/A_c | ymax   q5 1/A_+, 1/A_-, s0, s1   q6 s2..s5   q7 s6..s9
+//   A_c = o'x^2 + o'y^2 - r^2 (0 stored when <= 0: no lateral entry), A_+- = |o' -+ hl z|^2 - r^2 (the end spheres);
+//   RGB: s0 s1 = ambient, diffuse, s2..s4 = light / r, s6..s8 = albedo;  AUX: s0..s8 = the geom's world axes / r (x, y, z), s9 = the id.
+// The screen rectangle is the bounding box's; a camera inside the capsule (distance to the axis segment <= r) gets an empty one.
+template <bool BIN, int AUX = 0, bool ROUND = false>
 __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
   const int gi = blockIdx.x * blockDim.x + threadIdx.x;
   const int e = BIN ? gi >> 6 : gi / a.ngeom;
@@ -144,8 +151,11 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
   const int i = e * a.ngeom + g;
   const GeomTab* __restrict__ m = a.geom;
   const int b = m->g_body[g], gtype = m->g_type[g];
-  // round geoms are drawn as their bounding boxes (sphere: r r r; capsule: r r half+r): the rasteriser knows boxes and planes
-  const int type = (gtype == MIR_GEOM_SPHERE || gtype == MIR_GEOM_CAPSULE) ? MIR_GEOM_BOX : gtype;
+  // round geoms are drawn as their bounding boxes (sphere: r r r; capsule: r r half+r), unless ROUND: then as themselves.  (New conditions
+  // are spelt `ROUND ? new : old` and `ROUND && ..`, which the front end folds: the other instantiations compile exactly as before.)
+  const bool rnd = ROUND && (gtype == MIR_GEOM_SPHERE || gtype == MIR_GEOM_CAPSULE);
+  const int type = (gtype == MIR_GEOM_SPHERE || gtype == MIR_GEOM_CAPSULE) ? (ROUND ? gtype : MIR_GEOM_BOX) : gtype;
+  const bool solid = type == MIR_GEOM_BOX || rnd;  // (ROUND) a bounded solid: listed, culled and rectangle-bound like a box
   const float* pp = a.poses + ((size_t)e * 2 * a.pst + b) * 4;
   const V3 xp = {pp[0], pp[1], pp[2]};
   const float* qq = pp + 4 * a.pst;
@@ -188,7 +198,7 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
     // behind it).  A box whose bounding sphere lies outside the view pyramid is dropped HERE, before its corners and bounds are worked
     // out and without a record: the splat kernel walks the list of the others (a.vis), nobody reads the records of these.  Conservative:
     // every point p of the sphere has |p_x| >= |x_c| - r and p_z <= z_c + r.
-    if (a.vis && type == MIR_GEOM_BOX) {
+    if (a.vis && (ROUND ? solid : type == MIR_GEOM_BOX)) {
       const float r = sqrtf(dot(h, h));
       const float zc = -dot(rel, cf), xc = fabsf(dot(rel, cr)), yc = fabsf(dot(rel, cu));
       if (zc + r <= 1e-3f || xc - r > (zc + r) * a.cam.tanx || yc - r > (zc + r) * a.cam.tany) return;
@@ -199,10 +209,10 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
   const V3 U = {dot(ax[0], cu), dot(ax[1], cu), dot(ax[2], cu)};
   const float lk[3] = {dot(ax[0], L), dot(ax[1], L), dot(ax[2], L)};
   int xmin = 0, xmax = a.cam.W - 1, ymin = 0, ymax = a.cam.H - 1;
-  f4 q5, q6;
+  f4 q5, q6, q4r, q7r;  // (q4r, q7r: round records)
   float bA0[6], bAX[6], bAY[6], ucol[3] = {0, 0, 0};  // boxes: the six bounds, see below
   int nup = 0;
-  if (type == MIR_GEOM_BOX) {
+  if (ROUND ? solid : type == MIR_GEOM_BOX) {
     float pxmin = 3e38f, pxmax = -3e38f, pymin = 3e38f, pymax = -3e38f;
     int behind = 0;
 #pragma unroll
@@ -283,7 +293,7 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
       }
       ucol[j] = k == 0 ? acol[0] : (k == 1 ? acol[1] : acol[2]);
     }
-    if (nup == 0) { xmin = 1; xmax = 0; ymin = 1; ymax = 0; }
+    if (nup == 0 && !(ROUND && rnd)) { xmin = 1; xmax = 0; ymin = 1; ymax = 0; }  // (ROUND: a round geom's box bounds are not used)
     q5 = f4{ucol[0], ucol[1], ucol[2], 0.0f};
     q6 = f4{0.0f, 0.0f, 0.0f, 0.0f};
   } else {
@@ -296,6 +306,27 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
     if constexpr (AUX != 0) pw = aux_word(o.z < 0.0f ? -1.0f * ax[2] : ax[2]);
     q5 = f4{s * (o.x * F.z - o.z * F.x), s * (o.x * R.z - o.z * R.x), s * (o.x * U.z - o.z * U.x), AUX ? pw : pack_rgb(a.chk[0], sh)};
     q6 = f4{s * (o.y * F.z - o.z * F.y), s * (o.y * R.z - o.z * R.y), s * (o.y * U.z - o.z * U.y), AUX ? pw : pack_rgb(a.chk[1], sh)};
+  }
+  if constexpr (ROUND) {
+    if (rnd) {
+      // the round record (see above): the pixel kernels solve the ray / sphere and ray / infinite cylinder quadratics in w = 1 / t
+      const float r = gs[0], hl = gtype == MIR_GEOM_CAPSULE ? gs[1] : 0.0f, r2 = r * r, ir = 1.0f / r;
+      const float oxy = o.x * o.x + o.y * o.y, zs = o.z - fminf(fmaxf(o.z, -hl), hl);
+      if (oxy + zs * zs <= r2) { xmin = 1; xmax = 0; ymin = 1; ymax = 0; }  // the camera inside: never drawn (as a box with nup = 0)
+      const float ac = oxy - r2, ap = oxy + (o.z - hl) * (o.z - hl) - r2, am = oxy + (o.z + hl) * (o.z + hl) - r2;
+      const float iap = ap > 0.0f ? 1.0f / ap : 0.0f, iam = am > 0.0f ? 1.0f / am : 0.0f;
+      q4r = f4{r2, hl, ac > 0.0f ? 1.0f / ac : 0.0f, 0.0f};
+      if constexpr (AUX != 0) {
+        q5 = f4{iap, iam, ir * ax[0].x, ir * ax[0].y};
+        q6 = f4{ir * ax[0].z, ir * ax[1].x, ir * ax[1].y, ir * ax[1].z};
+        q7r = f4{ir * ax[2].x, ir * ax[2].y, ir * ax[2].z, __uint_as_float(aux_id)};
+      } else {
+        const float* alb = a.rgb[g];
+        q5 = f4{iap, iam, a.amb, a.dif};
+        q6 = f4{ir * lk[0], ir * lk[1], ir * lk[2], 0.0f};
+        q7r = f4{alb[0], alb[1], alb[2], 0.0f};
+      }
+    }
   }
   if (valid) {
     f4* o4 = reinterpret_cast<f4*>(a.prims + (size_t)i * PREC);
@@ -311,14 +342,14 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
       o4[1] = f4{F.x, F.y, F.z, __int_as_float(xmin)};
       o4[2] = f4{R.x, R.y, R.z, __int_as_float(xmax)};
       o4[3] = f4{U.x, U.y, U.z, __int_as_float(ymin)};
-      o4[4] = f4{h.x, h.y, h.z, __int_as_float(ymax)};
-      o4[7] = f4{0, 0, 0, 0};
+      o4[4] = (ROUND && rnd) ? f4{q4r.x, q4r.y, q4r.z, __int_as_float(ymax)} : f4{h.x, h.y, h.z, __int_as_float(ymax)};
+      o4[7] = (ROUND && rnd) ? q7r : f4{0, 0, 0, 0};
     }
     o4[5] = q5;
     o4[6] = q6;
   }
   if constexpr (!BIN) {
-    if (a.vis && type == MIR_GEOM_BOX && xmin <= xmax && ymin <= ymax) {
+    if (a.vis && (ROUND ? solid : type == MIR_GEOM_BOX) && xmin <= xmax && ymin <= ymax) {
       // work items of k_global_splat: the 32 x 8 blocks of the rectangle in up to GLOBAL_ITEMS_MAX interleaved shares of about four
       // (a slab close to the camera covers hundreds of blocks and must not keep one workgroup busy after the others have left)
       const int nb = ((xmax >> 5) - (xmin >> 5) + 1) * ((ymax >> 3) - (ymin >> 3) + 1);
@@ -337,7 +368,7 @@ __global__ void k_render_setup(SetupArgs a, BinArgs bn) {
   // the pixel kernel's floor pass.  This replaces the per-workgroup culling prologue of the generic kernel (one global load per
   // thread, two ballots and three barriers per strip: 40 us of the 335 us a 1024 x 480 x 640 render took).
   const int lane = gi & 63;
-  const bool is_floor = valid && g == 0 && type != MIR_GEOM_BOX && R.z == 0.0f && xmin <= 0 && xmax >= bn.W - 1 && ymin <= 0 && ymax >= bn.H - 1;
+  const bool is_floor = valid && g == 0 && (ROUND ? !solid : type != MIR_GEOM_BOX) && R.z == 0.0f && xmin <= 0 && xmax >= bn.W - 1 && ymin <= 0 && ymax >= bn.H - 1;
   const int floor = __builtin_amdgcn_readfirstlane(is_floor ? 1 : 0);  // lane 0 = geom 0
   for (int st = 0; st < bn.nsx * bn.nsy; st++) {
     const int sx = st % bn.nsx, sy = st / bn.nsx;
@@ -423,6 +454,73 @@ __device__ __forceinline__ void plane_region(const f4 ro, const f4 rf, const f4 
   }
 }
 
+// ---- round geoms (the ROUND records of k_render_setup) ----
+// The ray of one pixel, d' = e + x R' (e = F' + y U' of its row), against a capsule of radius r about the segment |z| <= hl of its frame
+// (a sphere: hl = 0), in the reciprocal depth w = 1 / t.  For a sphere with centre offset o'' = o' - s z the entry is
+//   w = (-beta + sqrt(D)) / A,   beta = o''.d',   A = |o''|^2 - r^2 (per record),   D = r^2 |d'|^2 - |o'' x d'|^2
+// (D = beta^2 - A |d'|^2 without the cancellation of that form: for a 5 cm link seen from metres it loses 3 - 5 of float's 7 digits);
+// a hit only where D >= 0 and w > 0 (beta < 0).  The lateral surface is the same in x and y alone and counts where the entry point
+// lies within |z| <= hl.  The capsule's entry is the largest of the three (it is convex, and the flat ends of the cylinder lie inside
+// the end spheres).  ~45 VALU instructions and at most three square roots per pixel (a sphere: one); no reciprocal.  Returns w (<= 0:
+// no hit) and d'.  Shared by every pixel path, which therefore agree bit for bit.
+__device__ __forceinline__ float round_w(const f4 ro, const f4 rr, const f4 rh, const f4 q5, const V3 e, float x, V3& d) {
+  d = V3{fmaf(x, rr.x, e.x), fmaf(x, rr.y, e.y), fmaf(x, rr.z, e.z)};
+  const float cx = fmaf(ro.y, d.z, -(ro.z * d.y)), cy = fmaf(ro.z, d.x, -(ro.x * d.z)), cz = fmaf(ro.x, d.y, -(ro.y * d.x));  // o' x d'
+  const float dd2 = fmaf(d.x, d.x, d.y * d.y), dd = fmaf(d.z, d.z, dd2), cz2 = cz * cz;
+  const float bt = fmaf(ro.z, d.z, fmaf(ro.x, d.x, ro.y * d.y));
+  const float r2 = rh.x, hl = rh.y;
+  // the end sphere at s z: beta = o'.d' - s d'z, (o' - s z) x d' = (cx + s d'y, cy - s d'x, cz)
+  auto sph = [&](float s_, float ia) {
+    const float b = fmaf(-s_, d.z, bt), ux = fmaf(s_, d.y, cx), uy = fmaf(-s_, d.x, cy);
+    const float D = fmaf(r2, dd, -fmaf(ux, ux, fmaf(uy, uy, cz2)));
+    return D >= 0.0f ? (__builtin_amdgcn_sqrtf(D) - b) * ia : 0.0f;
+  };
+  float w = sph(hl, q5.x);
+  if (hl > 0.0f) {  // a capsule (wave-uniform: records are scalar loads)
+    w = fmaxf(w, sph(-hl, q5.y));
+    const float bc = fmaf(ro.x, d.x, ro.y * d.y), Dc = fmaf(r2, dd2, -cz2);
+    const float wc = Dc >= 0.0f ? (__builtin_amdgcn_sqrtf(Dc) - bc) * rh.z : 0.0f;  // (rh.z = 1 / A_c, 0 = no lateral entry)
+    const bool on = fabsf(fmaf(ro.z, wc, d.z)) <= hl * wc;  // the entry point t d' + o' within |z| <= hl
+    w = on && wc > w ? wc : w;
+  }
+  return w;
+}
+// The colour (or aux) word at the entry point p = o' + d' / w: r n = p minus the nearest point of the axis segment.
+// RGB: albedo x (ambient + diffuse max(0, n.l)), rounded like the box faces' colours; AUX: the world normal and the id, as aux_word.
+template <bool AUX>
+__device__ __forceinline__ unsigned round_word(const f4 ro, const f4 rh, const f4 q5, const f4 q6, const f4 q7, float w, const V3 d) {
+  const float t = __builtin_amdgcn_rcpf(w);
+  const float px = fmaf(t, d.x, ro.x), py = fmaf(t, d.y, ro.y), pz0 = fmaf(t, d.z, ro.z);
+  const float pz = pz0 - fminf(fmaxf(pz0, -rh.y), rh.y);
+  if constexpr (AUX) {
+    const float nx = fmaf(px, q5.z, fmaf(py, q6.y, pz * q7.x)), ny = fmaf(px, q5.w, fmaf(py, q6.z, pz * q7.y));
+    const float nz = fmaf(px, q6.x, fmaf(py, q6.w, pz * q7.z));
+    return to_u8((nx + 1.0f) * 0.5f) | to_u8((ny + 1.0f) * 0.5f) << 8 | to_u8((nz + 1.0f) * 0.5f) << 16 | __float_as_uint(q7.w);
+  } else {
+    const float nl = fmaf(px, q6.x, fmaf(py, q6.y, pz * q6.z));
+    const float sh = q5.z + q5.w * fmaxf(nl, 0.0f);
+    return to_u8(q7.x * sh) | to_u8(q7.y * sh) << 8 | to_u8(q7.z * sh) << 16;
+  }
+}
+// a round record on ONE region (the layout of box_region: the lane's 4 pixels of the row with image-plane y `ys`)
+template <bool AUX>
+__device__ __forceinline__ void round_region(const f4 ro, const f4 rf, const f4 rr, const f4 ru, const f4 rh, const f4 q5, const f4 q6, const f4 q7,
+                                             float ys, const f2 (&xs)[2], f2 (&best)[2], unsigned (&col)[4]) {
+  const V3 e = {fmaf(ys, ru.x, rf.x), fmaf(ys, ru.y, rf.y), fmaf(ys, ru.z, rf.z)};
+#pragma unroll
+  for (int h = 0; h < 2; h++) {
+#pragma unroll
+    for (int q = 0; q < 2; q++) {
+      V3 d;
+      const float w = round_w(ro, rr, rh, q5, e, xs[h][q], d);
+      if (w > best[h][q]) {
+        best[h][q] = w;
+        col[2 * h + q] = round_word<AUX>(ro, rh, q5, q6, q7, w, d);
+      }
+    }
+  }
+}
+
 // ---- auxiliary channels (mir_render_outputs) ------------------------------------------------------
 // The aux pixel paths draw with the aux record (k_render_setup<., 1 or 2>) and write, per pixel, from the winning reciprocal depth w and aux
 // word: depth = 1 / w (planar camera-z metres; 0 = sky), segmentation = the word's top byte as a signed id (AUX_SKY -> -1), normal =
@@ -471,8 +569,9 @@ __device__ __forceinline__ void store_aux(const AuxOut& o, size_t pix, const flo
 // of one sub-tile drains under the arithmetic of the next (a workgroup per sub-tile serialises the two: measured
 // 240 us of arithmetic + 150 us of stores = 390 us).  Primitive records are read with wave-uniform addresses
 // straight from global memory (scalar loads, amortised over 16 pixels per lane); LDS holds only the id list.
-// (AUX: the aux pass of mir_render_outputs -- same drawing, the store writes the aux channels; see store_aux)
-template <bool AUX>
+// (AUX: the aux pass of mir_render_outputs -- same drawing, the store writes the aux channels; see store_aux.  ROUND: the records of
+//  spheres and capsules are round ones, drawn by round_region)
+template <bool AUX, bool ROUND = false>
 __device__ __forceinline__ void render_generic(const PixArgs& a, const AuxOut& o) {
   __shared__ int s_ids[256];
   __shared__ int s_wcnt[4];
@@ -549,6 +648,14 @@ __device__ __forceinline__ void render_generic(const PixArgs& a, const AuxOut& o
             const int wy = wy0 + 2 * r;  // wave-uniform region cull: rows wy, wy + 1
             if (ymax < wy || ymin > wy + 1) continue;
             box_region(ro, rf, rr, ru, rh, q7, q5, ysr[r], xs, best[r], col[r]);
+          }
+        } else if (ROUND && (__float_as_int(ro.w) & 255) != MIR_GEOM_PLANE) {
+          const f4 q7 = rec[7];
+#pragma unroll
+          for (int r = 0; r < 4; r++) {
+            const int wy = wy0 + 2 * r;
+            if (ymax < wy || ymin > wy + 1) continue;
+            round_region<AUX>(ro, rf, rr, ru, rh, q5, q6, q7, ysr[r], xs, best[r], col[r]);
           }
         } else {
           const unsigned ceven = __float_as_uint(q5.w), codd = __float_as_uint(q6.w);
@@ -642,6 +749,8 @@ __device__ __forceinline__ void render_generic(const PixArgs& a, const AuxOut& o
 }
 __global__ __launch_bounds__(256) void mir_render_kernel(PixArgs a) { render_generic<false>(a, AuxOut{}); }
 __global__ __launch_bounds__(256) void mir_render_kernel_aux(PixArgs a, AuxOut o) { render_generic<true>(a, o); }
+__global__ __launch_bounds__(256) void mir_render_kernel_round(PixArgs a) { render_generic<false, true>(a, AuxOut{}); }
+__global__ __launch_bounds__(256) void mir_render_kernel_aux_round(PixArgs a, AuxOut o) { render_generic<true, true>(a, o); }
 
 
 // The binned pixel kernel.  Same tiling (workgroup = 4 waves stacked on a 128-pixel-wide strip, walked in 128 x 32 sub-tiles, a
@@ -658,7 +767,9 @@ __global__ __launch_bounds__(256) void mir_render_kernel_aux(PixArgs a, AuxOut o
 //     reciprocal per lane and row), it fills the pixels the boxes left (all of them in the bands no rectangle meets), and the
 //     boxes were depth-tested against its row depth.
 #define NOHIT 0xffffffffu
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) void mir_render_binned(PixArgs a) {
+// (ROUND: the round records of spheres and capsules are drawn by round_region; at least 4 waves per SIMD)
+template <bool ROUND = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(ROUND ? 4 : 6, 6))) void mir_render_binned(PixArgs a) {
   __shared__ unsigned s_tile[4][8 * 128];  // per wave: 8 rows x 128 pixels of packed colours
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   // XCD-contiguous walk.  Workgroups go to the 8 XCDs round robin by linear id; the workgroups of XCD j take the j-th eighth
@@ -734,6 +845,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
             const cf4* rec = (const cf4*)(uintptr_t)(prims + (size_t)(e & 63) * PREC);
             const f4 ro = rec[0], rf = rec[1], rr = rec[2], ru = rec[3], q5 = rec[5], q6 = rec[6];
             if ((__float_as_int(ro.w) & 255) == MIR_GEOM_BOX) box_region(ro, rf, rr, ru, rec[4], rec[7], q5, ya, xsa, best, ca);
+            else if (ROUND && (__float_as_int(ro.w) & 255) != MIR_GEOM_PLANE) round_region<false>(ro, rf, rr, ru, rec[4], q5, q6, rec[7], ya, xsa, best, ca);
             else plane_region(ro, rf, rr, ru, q5, q6, ya, xsa, best, ca);
           }
         }
@@ -798,6 +910,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6, 6))) voi
 // to leave its registers.  The floor is a row constant here in both w and word (one aux word per plane), so it costs one reciprocal
 // pair per lane and band; untouched columns store it directly.  (The normal channel, 3 bytes per pixel, goes out as 96-byte row pieces
 // per store instruction; the four columns of a band complete its 384-byte rows.)
+template <bool ROUND = false>
 __global__ __launch_bounds__(256) void mir_render_binned_aux(PixArgs a, AuxOut o) {
   const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const unsigned wid = blockIdx.x, wseq = (wid & 7u) * (gridDim.x >> 3) + (wid >> 3);
@@ -851,6 +964,7 @@ __global__ __launch_bounds__(256) void mir_render_binned_aux(PixArgs a, AuxOut o
           const cf4* rec = (const cf4*)(uintptr_t)(prims + (size_t)(e & 63) * PREC);
           const f4 ro = rec[0], rf = rec[1], rr = rec[2], ru = rec[3], q5 = rec[5], q6 = rec[6];
           if ((__float_as_int(ro.w) & 255) == MIR_GEOM_BOX) box_region(ro, rf, rr, ru, rec[4], rec[7], q5, ya, xsa, best, ca);
+          else if (ROUND && (__float_as_int(ro.w) & 255) != MIR_GEOM_PLANE) round_region<true>(ro, rf, rr, ru, rec[4], q5, q6, rec[7], ya, xsa, best, ca);
           else plane_region(ro, rf, rr, ru, q5, q6, ya, xsa, best, ca);
         }
 #pragma unroll
@@ -886,17 +1000,34 @@ struct SplatArgs {
 };
 
 // one box, the 32 x 8 blocks b = first, first + stride, ... of its rectangle (row-major), lane = pixel
+// (ROUND: or a round record -- round_w / round_word per pixel, the word an aux word when AUX)
+template <bool ROUND = false, bool AUX = false>
 __device__ __forceinline__ void splat_box(const SplatArgs& a, unsigned iprim, int first, int stride) {
   const float* prim = a.prims + (size_t)iprim * PREC;
   const int tid = threadIdx.x;
   const cf4* rec = (const cf4*)(uintptr_t)prim;
   const f4 q0 = rec[0], q1 = rec[1], q2 = rec[2], q3 = rec[3], q4 = rec[4];
   const int tw = __float_as_int(q0.w);
-  if ((tw & 255) != MIR_GEOM_BOX) return;
+  if ((tw & 255) != MIR_GEOM_BOX && !(ROUND && (tw & 255) != MIR_GEOM_PLANE)) return;
   const int xmin = __float_as_int(q1.w), xmax = min(__float_as_int(q2.w), a.W - 1), ymin = __float_as_int(q3.w), ymax = min(__float_as_int(q4.w), a.H - 1);
   if (xmin > xmax || ymin > ymax) return;
   const int nbx = (xmax >> 5) - (xmin >> 5) + 1, nb = nbx * ((ymax >> 3) - (ymin >> 3) + 1);
   const f4 q5 = rec[5], q7 = rec[7];
+  if (ROUND && (tw & 255) != MIR_GEOM_BOX) {
+    const f4 q6 = rec[6];
+    for (int blk = first; blk < nb; blk += stride) {
+      const int by = (ymin & ~7) + 8 * (blk / nbx), bx = (xmin & ~31) + 32 * (blk % nbx);
+      const int py = by + (tid >> 5), px = bx + (tid & 31);
+      if (px < xmin || px > xmax || py < ymin || py > ymax) continue;
+      const float ys = a.y0 + (float)py * a.dy;
+      const V3 e = {fmaf(ys, q3.x, q1.x), fmaf(ys, q3.y, q1.y), fmaf(ys, q3.z, q1.z)};
+      V3 d;
+      const float w = round_w(q0, q2, q4, q5, e, a.x0 + (float)px * a.dx, d);
+      if (w > 0.0f)
+        atomicMax(a.zbuf + (size_t)py * a.W + px, (unsigned long long)__float_as_uint(w) << 32 | (unsigned long long)round_word<AUX>(q0, q4, q5, q6, q7, w, d));
+    }
+    return;
+  }
   const int nup = tw >> 8;
   const unsigned c0 = __float_as_uint(q5.x), c1 = __float_as_uint(q5.y), c2 = __float_as_uint(q5.z);
   for (int blk = first; blk < nb; blk += stride) {
@@ -920,6 +1051,8 @@ __device__ __forceinline__ void splat_box(const SplatArgs& a, unsigned iprim, in
 }
 
 #define GLOBAL_SPLAT_GRID 2048
+// (ROUND: the round records' words are computed per pixel, so the round splat comes in an RGB and an aux flavour)
+template <bool ROUND = false, bool AUX = false>
 __global__ __launch_bounds__(256) void k_global_splat(SplatArgs a) {
   // (a WAVE per box with the waves taking boxes round robin is twice as slow: 1.0 ms at 4096 envs -- the few boxes with large rectangles
   //  decide, and they want lanes.)  The workgroups walk the LIST of work items k_render_setup made of the boxes that can be on screen:
@@ -928,7 +1061,7 @@ __global__ __launch_bounds__(256) void k_global_splat(SplatArgs a) {
   const unsigned n = a.vis[0];
   for (unsigned k = blockIdx.x; k < n; k += GLOBAL_SPLAT_GRID) {
     const unsigned it = a.vis[VIS_HDR + k];
-    splat_box(a, it & 0x3fffffu, (int)(it >> 22 & 31u), (int)(it >> 27) + 1);
+    splat_box<ROUND, AUX>(a, it & 0x3fffffu, (int)(it >> 22 & 31u), (int)(it >> 27) + 1);
   }
 }
 
@@ -1030,6 +1163,7 @@ static int render_impl(MirHandle h, const MirCameraSpec* cam, const MirVisualSpe
                        const AuxOut* aux = nullptr, int seg_level = 0) {
   if (!h || !cam || !vis || (!pixels && !aux)) return mir_set_error(MIR_E_INVALID, "mir_render: null argument");
   if (vis->struct_size != (int)sizeof(MirVisualSpec)) return mir_set_error(MIR_E_INVALID, "mir_render: MirVisualSpec size mismatch");
+  if (vis->flags & ~MIR_VIS_ROUND_GEOMS) return mir_set_error(MIR_E_INVALID, "mir_render: unknown MirVisualSpec flags");
   if (cam->width <= 0 || cam->height <= 0 || !(cam->fov_deg > 0.0 && cam->fov_deg < 180.0))
     return mir_set_error(MIR_E_INVALID, "mir_render: bad camera (res / fov)");
   if (mode != MIR_RENDER_PER_ENV && mode != MIR_RENDER_GLOBAL) return mir_set_error(MIR_E_INVALID, "mir_render: unknown mode");
@@ -1097,6 +1231,19 @@ static int render_impl(MirHandle h, const MirCameraSpec* cam, const MirVisualSpe
       pa.sky = aux ? AUX_SKY : u8(vis->sky_rgb[0]) | u8(vis->sky_rgb[1]) << 8 | u8(vis->sky_rgb[2]) << 16;
     }
     const AuxOut ao = aux ? *aux : AuxOut{};
+    // the round instantiations only for a scene that has a sphere or a capsule: every other render runs today's kernels
+    const bool round = (vis->flags & MIR_VIS_ROUND_GEOMS) && h->render_round;
+    // k_render_setup<BIN, AUX, ROUND> for this call (aux pass: AUX 1 = link ids, 2 = geom ids)
+    auto setup = [&](auto bin_c, dim3 grid, const BinArgs& ba) {
+      constexpr bool BIN = decltype(bin_c)::value;
+      if (round) {
+        if (aux) hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_level ? k_render_setup<BIN, 2, true> : k_render_setup<BIN, 1, true>), grid, dim3(256), 0, st, sa, ba);
+        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_render_setup<BIN, 0, true>), grid, dim3(256), 0, st, sa, ba);
+      } else {
+        if (aux) hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_level ? k_render_setup<BIN, 2> : k_render_setup<BIN, 1>), grid, dim3(256), 0, st, sa, ba);
+        else hipLaunchKernelGGL(k_render_setup<BIN>, grid, dim3(256), 0, st, sa, ba);
+      }
+    };
     pa.th = h->render_th > 0 ? h->render_th : TH;
     const int nimg = mode == MIR_RENDER_GLOBAL ? 1 : B;
     // Per-env images (short primitive lists) take the binned kernel; the global view of all envs (one long list), widths
@@ -1116,12 +1263,12 @@ static int render_impl(MirHandle h, const MirCameraSpec* cam, const MirVisualSpe
       BinArgs ba;
       ba.prims = h->prims; ba.bins = h->bins; ba.W = cam->width; ba.H = cam->height; ba.nprim = pa.nprim; ba.th = pa.th;
       ba.nsx = nsx; ba.nsy = nsy; ba.nimg = nimg;
-      if (aux) hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_level ? k_render_setup<true, 2> : k_render_setup<true, 1>), dim3((B * 64 + 255) / 256), dim3(256), 0, st, sa, ba);
-      else hipLaunchKernelGGL(k_render_setup<true>, dim3((B * 64 + 255) / 256), dim3(256), 0, st, sa, ba);
+      setup(std::true_type{}, dim3((B * 64 + 255) / 256), ba);
       pa.bins = h->bins;
       pa.nsx = nsx; pa.nsy = nsy; pa.nwg = nimg * nsx * nsy;
-      if (aux) hipLaunchKernelGGL(mir_render_binned_aux, dim3((unsigned)((pa.nwg + 7) & ~7)), dim3(256), 0, st, pa, ao);
-      else hipLaunchKernelGGL(mir_render_binned, dim3((unsigned)((pa.nwg + 7) & ~7)), dim3(256), 0, st, pa);
+      const dim3 grid((unsigned)((pa.nwg + 7) & ~7));
+      if (aux) hipLaunchKernelGGL(HIP_KERNEL_NAME(round ? mir_render_binned_aux<true> : mir_render_binned_aux<false>), grid, dim3(256), 0, st, pa, ao);
+      else hipLaunchKernelGGL(HIP_KERNEL_NAME(round ? mir_render_binned<true> : mir_render_binned<false>), grid, dim3(256), 0, st, pa);
     } else if (mode == MIR_RENDER_GLOBAL && pa.nprim > 512 && !h->render_generic) {
       // the global view of many envs: one workgroup per box into a depth / colour buffer, then a resolve pass (see k_global_splat)
       const size_t npix = (size_t)cam->width * cam->height, need = npix;
@@ -1148,23 +1295,19 @@ static int render_impl(MirHandle h, const MirCameraSpec* cam, const MirVisualSpe
         (void)hipMemsetAsync(h->vis, 0, VIS_HDR * sizeof(unsigned), st);
       }
       sa.vis = h->vis;
-      if (aux) hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_level ? k_render_setup<false, 2> : k_render_setup<false, 1>), dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
-      else hipLaunchKernelGGL(k_render_setup<false>, dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
+      setup(std::false_type{}, dim3((B * ng + 255) / 256), BinArgs{});
       SplatArgs sp;
       sp.prims = h->prims; sp.zbuf = h->zbuf; sp.vis = h->vis; sp.pixels = pixels; sp.W = cam->width; sp.H = cam->height; sp.nprim = pa.nprim; sp.ngeom = ng;
       sp.x0 = pa.x0; sp.dx = pa.dx; sp.y0 = pa.y0; sp.dy = pa.dy; sp.sky = pa.sky; sp.aux = ao;
-      hipLaunchKernelGGL(k_global_splat, dim3(GLOBAL_SPLAT_GRID), dim3(256), 0, st, sp);
+      if (round) hipLaunchKernelGGL(HIP_KERNEL_NAME(aux ? k_global_splat<true, true> : k_global_splat<true, false>), dim3(GLOBAL_SPLAT_GRID), dim3(256), 0, st, sp);
+      else hipLaunchKernelGGL(k_global_splat<>, dim3(GLOBAL_SPLAT_GRID), dim3(256), 0, st, sp);
       if (aux) hipLaunchKernelGGL(k_global_resolve<true>, dim3((cam->width + 255) / 256, (cam->height + 3) / 4), dim3(256), 0, st, sp);
       else hipLaunchKernelGGL(k_global_resolve<false>, dim3((cam->width + 255) / 256, (cam->height + 3) / 4), dim3(256), 0, st, sp);
     } else {
       const dim3 grid((cam->width + TW - 1) / TW, (cam->height + pa.th - 1) / pa.th, nimg);
-      if (aux) {
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(seg_level ? k_render_setup<false, 2> : k_render_setup<false, 1>), dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
-        hipLaunchKernelGGL(mir_render_kernel_aux, grid, dim3(256), 0, st, pa, ao);
-      } else {
-        hipLaunchKernelGGL(k_render_setup<false>, dim3((B * ng + 255) / 256), dim3(256), 0, st, sa, BinArgs{});
-        hipLaunchKernelGGL(mir_render_kernel, grid, dim3(256), 0, st, pa);
-      }
+      setup(std::false_type{}, dim3((B * ng + 255) / 256), BinArgs{});
+      if (aux) hipLaunchKernelGGL(round ? mir_render_kernel_aux_round : mir_render_kernel_aux, grid, dim3(256), 0, st, pa, ao);
+      else hipLaunchKernelGGL(round ? mir_render_kernel_round : mir_render_kernel, grid, dim3(256), 0, st, pa);
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) rc = mir_set_error(MIR_E_HIP, hipGetErrorString(e));

@@ -31,6 +31,7 @@ struct MirScene {
   size_t bins_cap = 0;      // ints
   int render_th = 0;        // strip height override (mir_debug_render_path; 0 = default)
   int render_generic = 0;   // force the generic pixel kernel (mir_debug_render_path)
+  int render_round = 0;     // the scene has a sphere or a capsule: MIR_VIS_ROUND_GEOMS takes the round instantiations (mir_render.hip)
   unsigned long long* zbuf = nullptr;  // depth / colour buffer of the global view of many envs (mir_render.hip, k_global_splat)
   size_t zbuf_cap = 0;
   unsigned* vis = nullptr;         // [0] boxes with a non-empty screen rectangle this render, [1 ..] their indices (k_render_setup -> k_global_splat)

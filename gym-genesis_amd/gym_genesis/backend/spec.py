@@ -156,10 +156,13 @@ class MirCameraSpec(C.Structure):
     ]
 
 
+MIR_VIS_ROUND_GEOMS = 1  # MirVisualSpec.flags: spheres and capsules drawn as themselves (include/mirigid.h)
+
+
 class MirVisualSpec(C.Structure):
     _fields_ = [
         ("struct_size", C.c_int32),
-        ("_pad", C.c_int32),
+        ("flags", C.c_int32),
         ("geom_rgb", (C.c_double * 3) * MIR_MAX_GEOM),
         ("light_dir", C.c_double * 3),
         ("ambient", C.c_double),
@@ -316,10 +319,12 @@ class SceneBuilder:
         return len(self.geoms) - 1
 
     def visual(self, light_dir=(0.3, -0.4, 0.85), ambient=0.35, diffuse=0.65, sky_rgb=(0.55, 0.7, 0.9),
-               checker_rgb=((0.82, 0.82, 0.82), (0.42, 0.42, 0.45)), checker_size=0.5) -> "MirVisualSpec":
-        """Appearance used by mir_render: per-geom albedo from add_geom(rgb=...), one directional light."""
+               checker_rgb=((0.82, 0.82, 0.82), (0.42, 0.42, 0.45)), checker_size=0.5, round_geoms=False) -> "MirVisualSpec":
+        """Appearance used by mir_render: per-geom albedo from add_geom(rgb=...), one directional light.  round_geoms: draw spheres
+        and capsules as themselves instead of their bounding boxes (MIR_VIS_ROUND_GEOMS)."""
         v = MirVisualSpec()
         v.struct_size = C.sizeof(MirVisualSpec)
+        v.flags = MIR_VIS_ROUND_GEOMS if round_geoms else 0
         for i, g in enumerate(self.geoms):
             v.geom_rgb[i][:] = g["rgb"]
         v.light_dir[:] = light_dir

@@ -37,7 +37,10 @@ ENV_DIM = 11
 class FrankaCubePickBatch:
     def __init__(self, enable_pixels, observation_height, observation_width, num_envs, env_spacing,
                  camera_capture_mode, strip_environment_state, shard: Optional[Tuple[int, int]] = None, link_shape: str = "capsule",
-                 contact_capacity: int = 16, exact_contacts: bool = True):
+                 contact_capacity: int = 16, exact_contacts: bool = True, round_geoms: bool = False):
+        # round_geoms: the camera draws spheres and capsules (the capsule links) as themselves, not as their bounding boxes
+        # (MIR_VIS_ROUND_GEOMS); not a reference kwarg
+        self.round_geoms = bool(round_geoms)
         # link_shape: collision stand-ins of links 1-7, "box" or "capsule" (models._add_franka); not a reference kwarg
         # contact_capacity: contact points kept per env (not a reference kwarg; Genesis keeps 100+ pairs).  16 = the 16-lane kernel
         # (manifolds thinned beyond that: 29 % of the env-steps of the reference's expert, same success rate -- tests/test_ref_expert.py);
@@ -94,7 +97,7 @@ class FrankaCubePickBatch:
         self.eef = self.franka.get_link("hand")
         if self.enable_pixels:  # cube_pick.py:55-63
             self.cam = CameraView(self._mir, builder, self.scene, res=(self.observation_width, self.observation_height),
-                                  pos=(3.5, 0.0, 2.5), lookat=(0, 0, 0.5), fov=30)
+                                  pos=(3.5, 0.0, 2.5), lookat=(0, 0, 0.5), fov=30, round_geoms=self.round_geoms)
         self.motors_dof = np.arange(7)
         self.fingers_dof = np.arange(7, 9)
         # persistent device buffers: one set, rewritten by every fused step

@@ -37,7 +37,10 @@ AGENT_OBS, ENV_OBS = 8, 11            # what get_obs() actually returns
 
 class CubePick:
     def __init__(self, enable_pixels, observation_height, observation_width, num_envs, env_spacing,
-                 camera_capture_mode, strip_environment_state, shard: Optional[Tuple[int, int]] = None, exact_contacts: bool = True):
+                 camera_capture_mode, strip_environment_state, shard: Optional[Tuple[int, int]] = None, exact_contacts: bool = True,
+                 round_geoms: bool = False):
+        # round_geoms: the camera draws spheres and capsules as themselves (MIR_VIS_ROUND_GEOMS); not a reference kwarg
+        self.round_geoms = bool(round_geoms)
         # exact_contacts (not a reference kwarg): see tasks/franka/cube_pick.py
         self.exact_contacts = bool(exact_contacts)
         self.enable_pixels = enable_pixels
@@ -72,7 +75,7 @@ class CubePick:
             # envs_offset[i] + (3.5, 0, 2.5) -> envs_offset[i] + (0, 0, 0.5) (so101/cube_pick.py:139-147), fov 30 as in the
             # Franka pick task this code was copied from (franka/cube_pick.py:56-63).
             self.cam = CameraView(self._mir, builder, self.scene, res=(observation_width, observation_height),
-                                  pos=(3.5, 0.0, 2.5), lookat=(0, 0, 0.5), fov=30)
+                                  pos=(3.5, 0.0, 2.5), lookat=(0, 0, 0.5), fov=30, round_geoms=self.round_geoms)
         self.motors_dof = np.arange(5)
         self.fingers_dof = np.array([5])
         box = lambda n: spaces.Box(low=-np.inf, high=np.inf, shape=(n,), dtype=np.float32)  # noqa: E731

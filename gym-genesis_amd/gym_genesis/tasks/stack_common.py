@@ -31,7 +31,9 @@ class StackTaskBase:
     EEF_LINK = ""
 
     def __init__(self, enable_pixels, observation_height, observation_width, num_envs, env_spacing, camera_capture_mode,
-                 strip_environment_state, shard: Optional[Tuple[int, int]] = None):
+                 strip_environment_state, shard: Optional[Tuple[int, int]] = None, round_geoms: bool = False):
+        # round_geoms: the cameras draw spheres and capsules as themselves (MIR_VIS_ROUND_GEOMS); not a reference kwarg
+        self.round_geoms = bool(round_geoms)
         self.enable_pixels = enable_pixels
         self.observation_height = observation_height
         self.observation_width = observation_width
@@ -61,7 +63,8 @@ class StackTaskBase:
         self.eef = robot.get_link(self.EEF_LINK)
         if enable_pixels:  # utils.py:310-337 / :668-696 -- top, side (observation resolution) and wrist (always 640x480)
             res = (self.observation_width, self.observation_height)
-            mk = lambda res_, cfg: CameraView(self._mir, builder, self.scene, res=res_, pos=cfg[0], lookat=cfg[1], fov=cfg[2])  # noqa: E731
+            mk = lambda res_, cfg: CameraView(self._mir, builder, self.scene, res=res_, pos=cfg[0], lookat=cfg[1], fov=cfg[2],
+                                              round_geoms=self.round_geoms)  # noqa: E731
             self.cam_top, self.cam_side = mk(res, self.CAM_TOP), mk(res, self.CAM_SIDE)
             self.cam_wrist = mk((640, 480), self.CAM_WRIST)
         self.observation_space = self._make_obs_space()

@@ -17,9 +17,9 @@ from .so101.cube_stack_batch import CubeStackBatch
 
 class _One:
     def __init__(self, enable_pixels, observation_height, observation_width, num_envs, env_spacing, camera_capture_mode,
-                 strip_environment_state, shard=None):
+                 strip_environment_state, shard=None, round_geoms=False):
         super().__init__(enable_pixels, observation_height, observation_width, 1, env_spacing, camera_capture_mode,
-                         strip_environment_state)
+                         strip_environment_state, round_geoms=round_geoms)
         self.batch_envs = 1
         self.unbatched = True
 

@@ -192,14 +192,15 @@ class CameraView:
     array; depth, segmentation and normal images on request (Genesis returns rgb, depth, segmentation, normal).  ``render_envs()`` is the batched per-env image
     tensor used for the ``pixels`` observation: one launch instead of the reference's B renders."""
 
-    def __init__(self, mir, builder, scene, res, pos, lookat, fov, up=(0.0, 0.0, 1.0)):
+    def __init__(self, mir, builder, scene, res, pos, lookat, fov, up=(0.0, 0.0, 1.0), round_geoms=False):
         from ..backend.spec import make_camera
 
         self._mir, self._scene = mir, scene
         self.res = (int(res[0]), int(res[1]))
         self.fov = float(fov)
         self._make = make_camera
-        self._vis = builder.visual()
+        # round_geoms: spheres and capsules drawn as themselves (MIR_VIS_ROUND_GEOMS), in every image and channel of this camera
+        self._vis = builder.visual(round_geoms=round_geoms)
         self._up = tuple(up)
         self._home = (tuple(float(v) for v in pos), tuple(float(v) for v in lookat))
         self.set_pose(pos=pos, lookat=lookat)
@@ -227,7 +228,7 @@ class CameraView:
         img = self._mir.render(self._spec(self.pos, self.lookat), self._vis, mode=1, env_offset=self._offsets)
         # (what render() may reuse: the image is the tensor handed out as observation['pixels'], so its in-place version counter is kept
         #  too -- an edit by the caller, a normalisation or an overlay, makes render() draw again)
-        self._last_global = (getattr(self._mir, "state_version", None), self.pos, self.lookat, self.res, self.fov, self._up, id(self._vis),
+        self._last_global = (getattr(self._mir, "state_version", None), self.pos, self.lookat, self.res, self.fov, self._up, (id(self._vis), self._vis.flags),
                              img, img._version)
         self._record(img)
         return img
@@ -274,7 +275,7 @@ class CameraView:
         #  moved since -- mir_get_state_version -- so it is copied out, not drawn again; the caller gets a fresh array either way)
         last = self.__dict__.get("_last_global")
         ver = getattr(self._mir, "state_version", None)
-        same = (last is not None and ver is not None and last[:7] == (ver, self.pos, self.lookat, self.res, self.fov, self._up, id(self._vis))
+        same = (last is not None and ver is not None and last[:7] == (ver, self.pos, self.lookat, self.res, self.fov, self._up, (id(self._vis), self._vis.flags))
                 and last[7]._version == last[8])
         if same:
             img = last[7]

@@ -419,8 +419,9 @@ int mir_forward(MirHandle h, float* M, float* qfrc_bias, float* qacc_smooth, flo
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
  *                                                  gym_genesis/env.py:97-98
  * The reference renders through Genesis's OpenGL rasteriser over mesh assets that are not in the
- * reference tree; here the image is formed from the scene's own collision primitives (boxes, planes)
- * by a tiled HIP kernel: pinhole camera (vertical fov, +z up, pixel-centre sampling, row 0 = top),
+ * reference tree; here the image is formed from the scene's own collision primitives (boxes, planes;
+ * spheres and capsules as their bounding boxes, or as themselves with MIR_VIS_ROUND_GEOMS; hulls as their
+ * bounding boxes) by a tiled HIP kernel: pinhole camera (vertical fov, +z up, pixel-centre sampling, row 0 = top),
  * nearest primitive per pixel, Lambert shading from one directional light, a checker on planes. */
 typedef struct MirCameraSpec {
   int32_t width, height; /* res=(W,H) */
@@ -430,7 +431,7 @@ typedef struct MirCameraSpec {
 
 typedef struct MirVisualSpec {
   int32_t struct_size; /* = sizeof(MirVisualSpec) */
-  int32_t _pad;
+  int32_t flags;       /* MIR_VIS_* bits; 0 = every sphere, capsule and hull is drawn as its bounding box */
   double geom_rgb[MIR_MAX_GEOM][3]; /* albedo per geom, 0..1 */
   double light_dir[3];              /* direction TOWARDS the light (normalised by the library) */
   double ambient, diffuse;          /* colour = albedo * (ambient + diffuse * max(0, n.l)) */
@@ -438,6 +439,11 @@ typedef struct MirVisualSpec {
   double checker_rgb[2][3];         /* plane geoms: albedo of the two checker colours */
   double checker_size;              /* checker cell edge, metres */
 } MirVisualSpec;
+
+/* MirVisualSpec.flags.  MIR_VIS_ROUND_GEOMS: spheres and capsules are drawn as the exact sphere and capsule in every render entry point,
+ * mode and channel (RGB, depth, segmentation, normal; shading per pixel from the surface normal); hulls stay bounding boxes.  Off (the
+ * default) the images are those of the bounding boxes.  Any other bit: MIR_E_INVALID. */
+#define MIR_VIS_ROUND_GEOMS 1
 
 #define MIR_RENDER_PER_ENV 0 /* one image per env, camera pose relative to the env (cube_pick.py:166-171) */
 #define MIR_RENDER_GLOBAL 1  /* one image of all envs placed at env_offset (cube_pick.py:174-176) */
@@ -476,7 +482,8 @@ int mir_render_cams(MirHandle h, const MirCameraSpec* cam, const MirVisualSpec* 
  *                 In mode GLOBAL the id carries no env index.
  *   normal:       uint8 (..,3), the unit outward world-frame normal of the visible face as round((n + 1) / 2 * 255), clamped like the
  *                 colours; a plane's normal is the one facing the camera; sky = 0 0 0.
- * Spheres and capsules are drawn as their bounding boxes, as in RGB, so their depth and normals are those of the box.
+ * Spheres and capsules are drawn as in RGB: as their bounding boxes (depth and normals those of the box), or with MIR_VIS_ROUND_GEOMS
+ * as themselves (the normal of the curved surface at the pixel).
  * rgb goes through the kernels of mir_render; depth / segmentation / normal through ONE further pass that writes any subset of them.
  * mode, env_offset and cam_pos / cam_lookat / cam_up mean what they mean for mir_render and mir_render_cams (per-env cameras: cam_pos
  * and cam_lookat non-null, mode PER_ENV).  MIR_E_INVALID: struct_size != sizeof(MirRenderOutputs), seg_level not 0 / 1, every
