@@ -186,28 +186,28 @@ struct Outs {
   AutoResetArgs ar = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
   bool diag = true;
   bool poses = false;  // 16-lane kernel: also write the link poses into h->poses (the rasteriser reads them)
-  int phase = 0;       // 16-lane kernel: 0 whole step, 1 / 2 the two halves of a split step, 3 rotated, 4 the list instantiation of exact contacts (mir_step.h)
+  int kind = STEP_FULL;  // 16-lane kernel: which launch (StepKind, mir_step.h); STEP_FULL = a whole step, narrowed by mir_launch_step
   int exact = 0;       // 16-lane kernel: defer the envs with more candidate points than lanes (StepArgs::exact)
-  int over_cap = 0;    // 16-lane kernel, phase 4 / 5 (StepArgs::over_cap)
-  const int32_t* env_list = nullptr;  // 16-lane kernel, phase 1: serve the envs env_list[0 .. nlist) (StepArgs::env_list)
+  int over_cap = 0;    // 16-lane kernel, STEP_LIST48 / STEP_HEAVY48 (StepArgs::over_cap)
+  const int32_t* env_list = nullptr;  // 16-lane kernel, the kinds of step_reads_env_list: serve the envs env_list[0 .. nlist) (StepArgs::env_list)
   int nlist = 0;
-  uint32_t* next_host = nullptr;      // 16-lane kernel, phase 7 (StepArgs::next_host)
+  uint32_t* next_host = nullptr;      // 16-lane kernel, STEP_PRE48 (StepArgs::next_host)
   unsigned long long* prof = nullptr;  // 16-lane kernel only (debug)
 };
 
 int launch(MirScene* h, const Outs& o, void* stream) {
   int rc;
-  // (phase 4 -- the list instantiation of exact contacts -- steps the envs the pending step's launch deferred and writes THEIR scratch
+  // (STEP_LIST48 -- the list instantiation of exact contacts -- steps the envs the pending step's launch deferred and writes THEIR scratch
   //  rows for the state it leaves: it completes that launch, the handle's bookkeeping is the pending step's)
-  if (o.phase != 1 && o.phase != 7 && o.phase != 4 && o.mode != 2) h->pre_valid = 0;  // (whatever this launch is, the state it leaves is not the one `pre` was made from)
+  if (!step_keeps_pre(o.kind) && o.mode != 2) h->pre_valid = 0;  // (whatever this launch is, the state it leaves is not the one `pre` was made from)
   // Link poses for the rasteriser.  Once a render has been asked for (poses_live), every launch that integrates also leaves the
   // link poses of its final state in h->poses -- its closing forward kinematics has them -- so that a render behind a step needs
   // no pose-refresh launch (6 us per 1024 envs).  poses_current: h->poses matches qpos for every env.
-  const bool integrates = o.mode == 0 && o.phase != 1 && o.phase != 7;
-  if (integrates && o.phase != 4 && o.phase != 8) h->state_version++;  // (phase 8: the second list of a step whose first list has counted)
+  const bool integrates = o.mode == 0 && step_integrates(o.kind);
+  if (integrates && !step_completes_counted_step(o.kind)) h->state_version++;  // (STEP_ROTATED_LIST: the second list of a step whose first list has counted)
   const bool wr_poses = o.poses || (h->poses_live && integrates);
   if (o.mode == 2 && o.poses) h->poses_current = 1;
-  else if (integrates && o.phase != 4) h->poses_current = (h->kernel == 64 || wr_poses) && !o.ar.episode_len;  // (an in-kernel reset moves envs after the closing FK)
+  else if (integrates && o.kind != STEP_LIST48) h->poses_current = (h->kernel == 64 || wr_poses) && !o.ar.episode_len;  // (an in-kernel reset moves envs after the closing FK)
   if (h->kernel == 16) {
     StepArgs a;
     memset(&a, 0, sizeof a);
@@ -218,19 +218,19 @@ int launch(MirScene* h, const Outs& o, void* stream) {
     a.term_bad = h->pin_dev ? reinterpret_cast<uint32_t*>(h->pin_dev + h->pin_flag_off + 16) : nullptr;
     a.term_wstride = h->term_wstride;
     a.diag = (o.diag && h->diag_on) ? h->diag : nullptr;
-    a.B = h->B; a.qst = h->hm.qstride; a.nu = h->hm.nu; a.features = (h->hm.has_convex ? 1 : 0) | (h->hm.use_sap ? 3 : 0) | ((h->spec_pick && (!wr_poses || o.phase >= 3)) ? 4 : 0);
+    a.B = h->B; a.qst = h->hm.qstride; a.nu = h->hm.nu; a.features = (h->hm.has_convex ? FEAT_CONVEX : 0) | (h->hm.use_sap ? FEAT_CONVEX | FEAT_SAP : 0) | ((h->spec_pick && (!wr_poses || step_spec_stores_poses(o.kind))) ? FEAT_SPEC : 0);
     a.action = o.action; a.agent_pos = o.agent_pos; a.env_state = o.env_state; a.reward = o.reward; a.terminated = o.terminated;
     a.out_M = o.out_M; a.out_bias = o.out_bias; a.out_qas = o.out_qas; a.out_qacc = o.out_qacc; a.out_xpos = o.out_xpos; a.out_xquat = o.out_xquat;
     a.rows = o.rows; a.row_stride = o.row_stride; a.mode = o.mode; a.n_steps = o.n_steps; a.prof = o.prof;
     a.act_step = o.act_step; a.rows_step = o.rows_step; a.ar = o.ar;
     a.term_host = o.term_host; a.term_tag = o.term_tag; a.done_ticket = o.done_ticket; a.done_flag = o.done_flag; a.done_seq = o.done_seq;
-    a.phase = o.phase; a.pre = h->pre;
+    a.kind = o.kind; a.pre = h->pre;
     a.exact = o.exact; a.over_cap = o.over_cap;
-    a.pre_big = (o.phase == 4 || o.phase == 6 || o.phase == 7) ? h->pre_big : nullptr;
+    a.pre_big = step_uses_pre_big(o.kind) ? h->pre_big : nullptr;
     a.next_host = o.next_host;
     if (o.env_list) { a.env_list = o.env_list; a.B = o.nlist; }
-    if (o.phase == 4) a.term_wstride = 1;  // (the terminated byte of list entry k is byte k of term_host)
-    rc = mir_launch_step(&a, h->hm.max_contacts, (hipStream_t)stream);
+    if (o.kind == STEP_LIST48) a.term_wstride = 1;  // (the terminated byte of list entry k is byte k of term_host)
+    rc = mir_launch_step(&a, (hipStream_t)stream);
   } else {
     StepArgs64 a;
     memset(&a, 0, sizeof a);
@@ -670,7 +670,7 @@ int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* en
   // split step: if the previous mir_step_begin left the action-independent half of THIS step in `pre` (same stream, nothing
   // touched the state since), only the other half is launched now
   // exact contacts, HEAVY phase (mir_step_end decides): most envs of the last step had more points than the one-contact-per-lane kernel
-  // holds, so the whole batch takes the three-contacts-per-lane instantiation's first pass in ONE launch (mir_step.hip: VARIANT 7) -- no
+  // holds, so the whole batch takes the three-contacts-per-lane instantiation's first pass in ONE launch (STEP_HEAVY48) -- no
   // launch that defers, no list launch behind it, no scratch rows (the first light step afterwards is launched like the one behind a reset)
   // exact contacts, an OVERFLOW RUN in a loop that leaves room between two steps (mir_scene.h): the step as TWO launches of the
   // three-contacts-per-lane instantiation for the whole batch -- second half (-> terminated bytes), then, on the side stream, the first
@@ -693,7 +693,7 @@ int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* en
   // (one rotated launch -- this step's second half, then the next step's first half -- where the closing FK can be shared between
   //  the waves; otherwise two launches)
   const bool rotated = have_pre && h->hm.fk_free_leaf != 0 && h->split_step != 2 && !bigrot;
-  o.phase = heavy ? 5 : (bigrot ? 6 : (rotated ? 3 : (have_pre ? 2 : 0)));
+  o.kind = heavy ? STEP_HEAVY48 : (bigrot ? STEP_POST48 : (rotated ? STEP_ROTATED : (have_pre ? STEP_POST : STEP_FULL)));
   o.exact = h->exact;
   if (bigrot) {
     o.over_cap = h->hm.max_contacts < K16_MAX_CONTACT ? h->hm.max_contacts : K16_MAX_CONTACT;
@@ -717,7 +717,7 @@ int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* en
     if (int rc = split_lists(h, &buf, &nh_split)) return rc;
     h->pend_perm = buf;
     if (nh_split == 0 || nh_split >= h->B) {  // (one list after all)
-      o.phase = nh_split == 0 ? 8 : 6;
+      o.kind = nh_split == 0 ? STEP_ROTATED_LIST : STEP_POST48;
       o.env_list = h->perm_dev[buf]; o.nlist = h->B;
       nh_split = -1;
     }
@@ -741,7 +741,7 @@ int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* en
     // the others in ONE round of the one-contact-per-lane kernel's 40 KB workgroups on the side stream; the step's stream waits for those
     Outs oh = o, ol = o;
     oh.env_list = h->perm_dev[h->pend_perm]; oh.nlist = nh_split;
-    ol.phase = 8; ol.over_cap = 0; ol.prof = nullptr;
+    ol.kind = STEP_ROTATED_LIST; ol.over_cap = 0; ol.prof = nullptr;
     ol.env_list = h->perm_dev[h->pend_perm] + nh_split; ol.nlist = h->B - nh_split;
     ol.term_host = h->pin_dev + (size_t)(nh_split / 4) * h->term_wstride * sizeof(uint32_t);
     // (the side stream's launch reads the caller's action too: behind whatever produced it on the step's stream -- an event recorded
@@ -773,7 +773,7 @@ int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* en
   if (split && !rotated) {
     // ... and the action-independent half of the NEXT step goes out right behind it: it runs while the host is between two calls
     Outs p;
-    p.phase = bigrot ? 7 : 1; p.diag = false;
+    p.kind = bigrot ? STEP_PRE48 : STEP_PRE; p.diag = false;
     if (bigrot && h->big_side) {
       // (... on the side stream, behind the launch above: beside the caller's work between two steps; the next mir_step_begin -- and the
       //  launches for envs this step defers -- come behind it through ovf_event)
@@ -823,7 +823,7 @@ int mir_step_go(MirHandle h, const float* action, void* stream) {
 }
 
 /* exact contacts: the n envs of h->ovf_list_host were deferred by the launch(es) of the pending mir_step_begin (their state rows are
- * those of the step's start).  They are stepped here by the LIST INSTANTIATION of the 16-lane kernel (mir_step.hip, VARIANT 6: three
+ * those of the step's start).  They are stepped here by the LIST INSTANTIATION of the 16-lane kernel (STEP_LIST48, mir_step.h: three
  * contacts per lane, 48 points, four envs per workgroup) -- one launch that takes the action and the output pointers of the pending
  * step, stores state, observations and the terminated byte of list entry k into ovf_term_host[k], and then writes the envs' scratch
  * rows for the NEXT step (which also say whether they are deferred again).  An env beyond THAT kernel's capacity (more than 48 points,
@@ -891,7 +891,7 @@ static int exact_finish(MirScene* h, int n, uint8_t* terminated_host) {
     o.action = h->pend_action;
     o.agent_pos = (float*)h->pend_out[0]; o.env_state = (float*)h->pend_out[1]; o.reward = (float*)h->pend_out[2]; o.terminated = (uint8_t*)h->pend_out[3];
     o.term_host = h->ovf_term_dev; o.term_tag = h->tag;
-    o.phase = 4; o.env_list = h->ovf_list_dev; o.nlist = n;
+    o.kind = STEP_LIST48; o.env_list = h->ovf_list_dev; o.nlist = n;
     o.prof = h->dbg_prof_list;
     h->dbg_prof_list = nullptr;
     int rc = launch(h, o, side);
@@ -923,7 +923,7 @@ static int exact_finish(MirScene* h, int n, uint8_t* terminated_host) {
     h->poses_current = 0;  // (these envs' link poses were not written)
     if (h->pre_valid) {  // (split step: the scratch rows of the coming step, for the envs that have only now reached its starting state)
       Outs p;
-      p.phase = 1; p.diag = false; p.env_list = wlist_dev; p.nlist = nw;
+      p.kind = STEP_PRE; p.diag = false; p.env_list = wlist_dev; p.nlist = nw;
       rc = launch(h, p, side);
       if (rc != MIR_OK) return rc;
     }
@@ -1228,7 +1228,7 @@ extern "C" int mir_debug_rotated_launches(MirHandle h, const float* actions, int
     Outs f; f.action = actions; f.diag = false;
     int rc = launch(h, f, stream);
     if (rc != MIR_OK) return rc;
-    Outs p; p.phase = 1; p.diag = false;
+    Outs p; p.kind = STEP_PRE; p.diag = false;
     rc = launch(h, p, stream);
     if (rc != MIR_OK) return rc;
   }
@@ -1238,7 +1238,7 @@ extern "C" int mir_debug_rotated_launches(MirHandle h, const float* actions, int
   //  the host consumes them, rocprofv3 has the kernel at 22.3 us)
   const bool outs = outputs != nullptr;
   for (int i = 0; i < n; i++) {
-    Outs o; o.action = actions + (size_t)(i % (n_actions > 0 ? n_actions : 1)) * h->B * h->nu; o.diag = false; o.phase = 3;
+    Outs o; o.action = actions + (size_t)(i % (n_actions > 0 ? n_actions : 1)) * h->B * h->nu; o.diag = false; o.kind = STEP_ROTATED;
     if (outs) {
       o.agent_pos = (float*)outputs[0]; o.env_state = (float*)outputs[1]; o.reward = (float*)outputs[2]; o.terminated = (uint8_t*)outputs[3];
     }
@@ -1341,10 +1341,10 @@ int mir_rollout(MirHandle h, const float* actions, int32_t n_steps, float* rows,
 
 /* Device-resident K-step rollout that keeps every contact point (mirigid.h: mir_rollout_exact).  A fixed chain on the caller's stream:
  *   memset of the two list counters;
- *   the one-wave step loop with hand-off (VARIANT 12) for the whole batch -- an env stays on it until its first step above the
+ *   the one-wave step loop with hand-off (STEP_XR16) for the whole batch -- an env stays on it until its first step above the
  *     one-contact-per-lane capacity, then stores its state of that step's start and appends itself to list 1 (exact == 2: every env at
  *     step 0, the twin route of the tests);
- *   the three-contacts-per-lane step loop (VARIANT 13) over list 1 -- fixed grid, a workgroup past the list's device count exits at
+ *   the three-contacts-per-lane step loop (STEP_XR48) over list 1 -- fixed grid, a workgroup past the list's device count exits at
  *     once -- each env from its own start step to the end of the call, which hands an env beyond 48 points or 16 candidate pairs on to
  *     list 2 (scenes whose host-closed route has no list instantiation: list 1 is list 2);
  *   the wave-per-env kernel in list mode over list 2, each env resuming at its own step (the 16-lane layout in and out);
@@ -1386,25 +1386,25 @@ static int rollout_exact(MirScene* h, const float* actions, int32_t n_steps, flo
   a.early_stats = h->early_stats; a.no_early_mask = 1;
   a.term_wstride = h->term_wstride;
   a.B = h->B; a.qst = h->hm.qstride; a.nu = h->hm.nu;
-  a.features = (h->hm.has_convex ? 1 : 0) | (h->hm.use_sap ? 3 : 0) | (h->spec_pick ? 4 : 0);
+  a.features = (h->hm.has_convex ? FEAT_CONVEX : 0) | (h->hm.use_sap ? FEAT_CONVEX | FEAT_SAP : 0) | (h->spec_pick ? FEAT_SPEC : 0);
   a.row_stride = row_stride; a.mode = 0;
   a.ar = ar;
   a.exact = h->exact;
   // (without the list instantiation the hand-off of (1) goes to list 2 directly: the step index it records carries no tier bit, which
-  //  only VARIANT 13 reads)
+  //  only STEP_XR48 reads)
   a.xr_list = h->exact_big ? h->xr_list : h->xr_list2; a.xr_count = h->exact_big ? h->xr_count : h->xr_count + 1;
   a.xr_list2 = h->xr_list2; a.xr_count2 = h->xr_count + 1;
   a.xr_start = h->xr_start; a.xr_stats = h->xr_stats;
   const long as = (long)h->B * h->nu, rs = (long)h->B * row_stride;
   // (1) the whole batch on the one-wave step loop, every env until its hand-off
-  a.phase = 12; a.action = actions; a.rows = rows; a.n_steps = n_steps; a.act_step = as; a.rows_step = rs;
-  int rc = mir_launch_step(&a, h->hm.max_contacts, st);
+  a.kind = STEP_XR16; a.action = actions; a.rows = rows; a.n_steps = n_steps; a.act_step = as; a.rows_step = rs;
+  int rc = mir_launch_step(&a, st);
   if (rc != 0) return hip_fail((hipError_t)rc, who);
   // (2) list 1 on the three-contacts-per-lane step loop, each env from its own step (scenes whose host-closed route sends the deferred
   //     envs to the wave-per-env kernel instead -- no split closing FK, or MIR_EXACT_WAVE -- hand them straight to list 2 in (1))
   if (h->exact_big) {
-    a.phase = 13; a.env_list = h->xr_list; a.n_steps = n_steps; a.action = actions; a.rows = rows; a.act_step = as; a.rows_step = rs;
-    rc = mir_launch_step(&a, h->hm.max_contacts, st);
+    a.kind = STEP_XR48; a.env_list = h->xr_list; a.n_steps = n_steps; a.action = actions; a.rows = rows; a.act_step = as; a.rows_step = rs;
+    rc = mir_launch_step(&a, st);
     if (rc != 0) return hip_fail((hipError_t)rc, who);
   }
   // (3) list 2 on the wave-per-env kernel, each env from its own step to the end of the call

@@ -70,7 +70,7 @@ struct MirScene {
   // (hm64 / dm64 = the same scene compiled for it with 48 points) from the untouched state rows, then recomputes their scratch rows.
   int exact;                // 0 off, 1 on, 2 (tests) every env is deferred: the whole batch takes the list instantiation
   int exact_big;            // the deferred envs take the list instantiation of the 16-lane kernel (three contacts per lane); 0: the wave-per-env kernel (MIR_EXACT_WAVE=1)
-  int heavy;                // the coming mir_step_begin steps the WHOLE batch with three contacts per lane (one launch: mir_step.hip VARIANT 7); decided by mir_step_end
+  int heavy;                // the coming mir_step_begin steps the WHOLE batch with three contacts per lane (one launch: STEP_HEAVY48, mir_step.h); decided by mir_step_end
   int heavy_enter, heavy_leave;  // thresholds of that decision, in envs (MIR_EXACT_HEAVY)
   int pend_heavy;           // the pending step is such a launch
   int32_t* perm_host[2];    // pinned, device-mapped: the order in which a heavy launch serves the envs (the ones above 16 points first), double-buffered
@@ -92,7 +92,7 @@ struct MirScene {
   void* pend_out[4];
   int pend_rotated;         // the pending step is ONE rotated launch (else: a launch followed by the first half of the next step for all envs)
   unsigned long long ex_steps, ex_ovf_steps, ex_ovf_envs, ex_ovf_max;  // steps closed / steps with deferred envs / deferred env-steps / most in one step
-  // OVERFLOW RUNS as two launches per step (mir_step.hip VARIANT 9 / 10, StepArgs::phase 6 / 7): from the step after one that
+  // OVERFLOW RUNS as two launches per step (STEP_POST48 / STEP_PRE48, mir_step.h): from the step after one that
   // deferred envs until a step in which no env is above 16 points, a mir_step_begin that finds the caller left room between two steps steps
   // the WHOLE batch with the three-contacts-per-lane instantiation -- the second half from the scratch rows (an env with 17 .. 48 contacts has
   // its row in pre_big) on the step's stream, then the first half of the next step with the 48-point capacity on the side stream.  An env
@@ -108,7 +108,7 @@ struct MirScene {
   void* main_event;         // hipEvent_t: recorded behind the second-half launch of such a step (the side stream's first-half launch waits for it)
   // ... and its second half as TWO LISTS once the first-half launch of the step before has said which envs are above 16 points NOW
   // (StepArgs::next_host): those on the three-contacts-per-lane instantiation on the step's stream, the others -- one round of 40 KB
-  // workgroups -- on the rotated launch's first pass (VARIANT 11) on the side stream
+  // workgroups -- on the rotated launch's first pass (STEP_ROTATED_LIST) on the side stream
   uint32_t* next_host;      // pinned, device-mapped: (B + 3) / 4 words
   uint32_t* next_dev;
   int big_lists;            // (MIR_EXACT_BIG_LISTS=0: never)

@@ -30,13 +30,8 @@
 //     the arithmetic, vectors that a whole row needs once travel by row broadcast instead of through LDS, and every global
 //     read of a launch (tables, per-lane record, model scalars, state, action, cached poses) leaves before the first LDS
 //     store -- one L2 round trip at the start.
-//   * instantiations: <0> one step per launch (two waves, no step loop, no AGPRs), <1> K-step rollouts with packed rows, <2>
-//     everything (per-stage outputs, pose refresh, profiling stamps); <3> / <4> the action-independent / action-dependent half
-//     of a step through a scratch row in HBM, <5> the ROTATED launch of GenesisEnv.step -- <4> of this step followed by <3> of
-//     the next in one kernel, so that the host has its `terminated` after half a step and the rest runs while it is between two
-//     calls; with three contacts per lane (CPL = 3, exact contacts) <6> the whole step + the next step's <3> for a list of envs, <7> the
-//     whole step for the batch (heavy phase), <9> / <10> the two halves as two launches (overflow runs), and <11> (CPL = 1) <5>'s first
-//     pass alone for a list.  One step body serves all of them; built with -ffp-contract=on so that they agree bit for bit.
+//   * instantiations: one step body serves every kind of launch -- single step, rollout loop, the halves of a split step, the
+//     rotated launch, the three-contacts-per-lane tier of exact contacts; StepKind and its table in mir_step.h name and describe them.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -54,7 +49,7 @@
 #define MSTR 20     /* row stride of M in LDS (floats): 16-byte aligned rows, conflict-free b128 row reads */
 #define JB_SKEW 8   /* see EnvLds::Jb_ */
 #define JBROW(Sx, c) (&(Sx).Jb_[(c) * JST + jbs])
-static_assert(K16_MAX_CONTACT == G, "lane c owns contact c (one contact per lane; the list instantiation for exact contacts keeps CPL = 3 per lane)");
+static_assert(K16_MAX_CONTACT == G, "lane c owns contact c (one contact per lane; the step_big kinds keep CPL = 3 per lane)");
 
 // optional phase timestamps (debug): block 0, thread 0 records the shader clock at phase boundaries
 #ifdef MIR_PROFILE_SINGLE
@@ -107,7 +102,7 @@ struct ColScratchT {
   float clip[48];                 // polygon clipping scratch of the box-box routine (one row)
 };
 static_assert(sizeof(((ColScratchT<1>*)nullptr)->sap) <= sizeof(((ColScratchT<1>*)nullptr)->stage), "SAP scratch must fit under the staging area");
-// CPL = contacts per lane: 1 everywhere but in the list instantiation for exact contacts (VARIANT 6), where lane c owns contacts
+// CPL = contacts per lane: 1 everywhere but in the step_big kinds (mir_step.h), where lane c owns contacts
 // c, c + 16, c + 32 (capacity 48 = MIR_MAX_CONTACT, what the wave-per-env kernel holds).
 template <int CPL>
 struct ContactArraysT {
@@ -135,7 +130,7 @@ struct EnvLdsT : ConBWords<CPL> {
   float cdof[G][8];               // ang(3) pad lin(3) pad
   float M[G][MSTR];
   int ncon, ncand, coupled /* some contact joins the two kinematic trees: the Newton Hessian is not block diagonal */;
-  int cin_ready;  // two-wave instantiations: the collision wave has stored the body inertias of this step (main wave spins on it; VARIANT 6: of pass cin_ready - 1)
+  int cin_ready;  // two-wave instantiations: the collision wave has stored the body inertias of this step (main wave spins on it; STEP_LIST48: of pass cin_ready - 1)
   // Phase-aliased working set.  `dyn` (smooth dynamics) and `col` (collision detection) are live AT THE SAME TIME in the
   // single-step instantiation, where a second wave of the workgroup detects collisions while the first one does the dynamics;
   // the contact arrays and the contact Jacobians take the place of both afterwards (CPL == 1: con never overlaps col -- the contact
@@ -248,52 +243,9 @@ __device__ __forceinline__ void step_rows_l(float al, float ljar, float ljv, flo
 }
 
 // ---------------------------------------------------------------------------------------------
-// SINGLE = one full step per launch without the rollout / autoreset / per-stage-output options (the headline launch): the
-// step loop disappears at compile time, and with it the block of scalar-register spills that the loop structure forces in
-// front of it (every launch-invariant value is otherwise saved before the loop and restored inside it).
-// VARIANT 0 = SINGLE (above); 1 = the step loop for rollouts (no per-stage / debug outputs and no separate observation
-// buffers: only packed rows), which keeps 11 pointers out of the scalar registers; 2 = everything.
-// FEAT bit 0 (CONVEX) = the scene has sphere / capsule geoms: the closed-form plane cases and the lane-private GJK / MPR
-// narrowphase (mir_convex.h) are compiled in.  FEAT bit 1 (SAP) = the candidate pairs come from a sweep-and-prune over the
-// geoms' world AABBs instead of the static pair list (scenes whose static list would exceed K16_MAX_PAIR, e.g. with
-// self-collision enabled).  Scenes of planes and boxes with a short static list run the instantiation without either, whose
-// register allocation and schedule are therefore untouched by that code.
-// FEAT bit 2 (SPEC) = the headline scene: its sizes and options (SpecPick, mir_spec_pick.h) are literals instead of model reads.
-//
-// DUAL (the single-step instantiation): the workgroup has TWO waves.  Collision detection (geom poses, broadphase, narrowphase)
-// needs only the link poses, and so do the smooth dynamics (subspaces, CRB, RNE, mass matrix, smooth solve): wave 1 does the
-// former while wave 0 does the latter, in disjoint LDS areas, between two workgroup barriers.  At 4096 envs there is otherwise
-// ONE wave per SIMD that spends 60 % of its life waiting on LDS round trips; the second wave fills those slots and takes
-// ~5 k cycles out of the ~50 k of a step.  Wave 1 also opens the launch with the forward kinematics of the stored state (its loads
-// -- one qpos row, four quads of lane constants -- are back before wave 0's, which brings in the model table and everything else),
-// and after the contacts it accumulates the all-rows-active Newton Hessian beside wave 0's warm start and first gradient: four
-// barriers in all.  The step-loop instantiations keep one wave (they need the AGPRs a second wave per SIMD would have to give up);
-// both run the same code in the same order of operations, so they agree bit for bit.
-// VARIANT 3 / 4 = the two halves of a single step for GenesisEnv.step (StepArgs.phase 1 / 2): 3 is the action-independent
-// half -- everything the two waves do up to the contact Jacobians -- whose results go to the `pre` buffer instead of staying in
-// LDS; 4 picks them up and runs the rest on one wave (all-rows-active Hessian included).  The host launches 3 for the NEXT step
-// right behind the current step, so that it runs while the host is between two env.step() calls.
-// VARIANT 6 (CPL = 3) = the LIST instantiation for EXACT CONTACTS: the envs of StepArgs::env_list -- the ones a launch of the
-// mir_step_begin path deferred because their narrowphase found more candidate points than lanes -- take the WHOLE step here (the
-// fused launch's pass: two waves, dynamics beside collision detection) with three contacts per lane, capacity 48 = MIR_MAX_CONTACT
-// (Genesis keeps every point of its candidate pairs: /root/reference/gym_genesis/tasks/franka/cube_pick.py:46), store state, targets,
-// observations and their terminated bytes (byte k of StepArgs::term_host for list entry k), and then run the action-independent half
-// of the NEXT step like the rotated launch's second pass, into the env's scratch row: one launch instead of the wave-per-env kernel
-// on the list followed by VARIANT 3 on the list, four envs per workgroup instead of one.  80 KB of LDS per workgroup, two workgroups
-// per CU, one wave per SIMD with the whole register file.  An env with more than 48 points or more than 16 candidate pairs is
-// deferred AGAIN (bit 7 of its byte; nothing stored): the wave-per-env kernel (64 candidates) stays the fallback for those.
-// VARIANT 7 (CPL = 3) = the same first pass ALONE, for the whole batch (no list, the regular terminated words): what mir_step_begin
-// launches INSTEAD of the one-contact-per-lane kernel while most envs would be deferred anyway (the reference's expert holds 70 % of
-// its envs above 16 points through its two grasp stages): one launch per step instead of a launch that computes garbage for the
-// deferred majority followed by the list launch for them.  Bit 6 of a byte: the env had more points than StepArgs::over_cap (what
-// the host decides on when to go back).
-// VARIANT 12 / 13 = the device-resident rollout that keeps every contact point (mir_rollout_exact; StepArgs::xr_*).  12 (CPL = 1) is
-// VARIANT 1 -- the same one-wave step loop, the same arithmetic -- with DEFERRAL: at the first step whose candidate points exceed the
-// one-contact-per-lane capacity an env stores its state of that step's start and hands itself off to a device list; from there on the
-// launch stores nothing for it (its lanes compute on, unread).  13 (CPL = 3) is a step loop of passes of VARIANT 7's whole step, each
-// env of that list from its own start step, with the step's packed row and the episode loop of VARIANT 1 inside (mir_step_kernel); an
-// env beyond its capacity goes on a second list for the wave-per-env kernel.  VARIANT 1 itself is untouched by either.
-// One pass of the body as a device function: VARIANT 13's step loop (mir_step_kernel) calls it once per step of the call.  The other
+// The step kernel.  VARIANT is a StepKind, FEAT a mask of FEAT_* bits, CPL = step_cpl(VARIANT): mir_step.h describes every kind and
+// holds the table of their properties, from which the attributes below, the launch (launch_feat) and the body's switches come.
+// One pass of the body as a device function: STEP_XR48's step loop (mir_step_kernel) calls it once per step of the call.  The other
 // instantiations keep the body as the kernel's own (the same text, mir_step_body.inc), so that their code is what it was.
 template <int VARIANT, int FEAT, int CPL = 1>
 __device__ __attribute__((always_inline)) inline void mir_step_pass(StepArgs a) {
@@ -301,9 +253,9 @@ __device__ __attribute__((always_inline)) inline void mir_step_pass(StepArgs a) 
 }
 
 template <int VARIANT, int FEAT, int CPL = 1>
-__global__ __launch_bounds__((VARIANT == 0 || VARIANT == 3 || (VARIANT >= 5 && VARIANT != 12)) ? 128 : 64)
-__attribute__((amdgpu_waves_per_eu((VARIANT == 5 || VARIANT == 11) ? 2 : 1, (VARIANT == 5 || VARIANT == 11) ? 2 : ((VARIANT >= 6 && VARIANT != 12) ? 1 : 10)))) void mir_step_kernel(StepArgs a) {
-  if constexpr (VARIANT == 13) {
+__global__ __launch_bounds__(step_block(VARIANT))
+__attribute__((amdgpu_waves_per_eu(step_wpe_min(VARIANT), step_wpe_max(VARIANT)))) void mir_step_kernel(StepArgs a) {
+  if constexpr (VARIANT == STEP_XR48) {
     // The STEP LOOP of the three-contacts-per-lane tier (mir_rollout_exact): workgroup g serves list entries 4g .. 4g + 3 (and leaves at
     // once when 4g is past the list's device count) through the steps of the call from the earliest start among them.  Every pass is
     // the whole step of one step index -- the env's state rows go through HBM between two passes, as between two launches, so a pass is
@@ -372,63 +324,61 @@ extern "C" int mir_launch_debug_convex(const float* in, float* out, int n, hipSt
 // (mir_step_convex.hip = this file compiled with MIR_STEP_CONVEX_TU and WITHOUT -fno-signed-zeros: together with
 // -ffp-contract=on that flag miscompiles the support-mapping selects of mir_convex.h -- box pairs lose contacts -- while the
 // planes-and-boxes kernels gain 1 % from it).
-#ifdef MIR_STEP_CONVEX_TU
+template <int KIND, int FEAT>
+static int launch_kind(const StepArgs& a, int blocks, hipStream_t stream) {
+  hipLaunchKernelGGL((mir_step_kernel<KIND, FEAT, step_cpl(KIND)>), dim3(blocks), dim3(step_block(KIND)), 0, stream, a);
+  return (int)hipGetLastError();
+}
+// THE dispatch: kind -> instantiation, for the FEAT mask of the caller's translation unit.  A kind that a mask does not carry is an
+// error.  (STEP_POST has no collision code in it: one instantiation, FEAT_PLAIN, serves every scene; STEP_FULL stays generic.)
 template <int FEAT>
-static void launch_feat(const StepArgs& a, int blocks, int single, int plain_loop, hipStream_t stream) {
-  if (a.phase == 1) hipLaunchKernelGGL((mir_step_kernel<3, FEAT>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 3) hipLaunchKernelGGL((mir_step_kernel<5, FEAT>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 4) hipLaunchKernelGGL((mir_step_kernel<6, FEAT, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 5) hipLaunchKernelGGL((mir_step_kernel<7, FEAT, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 6) hipLaunchKernelGGL((mir_step_kernel<9, FEAT, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 7) hipLaunchKernelGGL((mir_step_kernel<10, FEAT, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 8) hipLaunchKernelGGL((mir_step_kernel<11, FEAT>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 12) hipLaunchKernelGGL((mir_step_kernel<12, FEAT>), dim3(blocks), dim3(64), 0, stream, a);
-  else if (a.phase == 13) hipLaunchKernelGGL((mir_step_kernel<13, FEAT, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (single) hipLaunchKernelGGL((mir_step_kernel<0, FEAT>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (plain_loop) hipLaunchKernelGGL((mir_step_kernel<1, FEAT>), dim3(blocks), dim3(64), 0, stream, a);
-  else if constexpr ((FEAT & 4) == 0) hipLaunchKernelGGL((mir_step_kernel<2, FEAT>), dim3(blocks), dim3(64), 0, stream, a);
-}
-extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_convex(const StepArgs* args, int single, int plain_loop, hipStream_t stream) {
-  StepArgs a = *args;
-  const int blocks = (a.B + EPB - 1) / EPB;
-  // the headline scene's instantiation (features bit 2: mir_create found SpecPick::matches); the everything-variant stays generic
-  if ((a.features & 4) && (a.phase == 1 || a.phase == 3 || a.phase == 4 || a.phase == 5 || a.phase == 6 || a.phase == 7 || a.phase == 8 || a.phase == 12 || a.phase == 13 || single || plain_loop)) launch_feat<5>(a, blocks, single, plain_loop, stream);
-  else if (a.features & 2) launch_feat<3>(a, blocks, single, plain_loop, stream);  // sweep-and-prune scenes carry the convex code too
-  else launch_feat<1>(a, blocks, single, plain_loop, stream);
-  return (int)hipGetLastError();
-}
-#else
-extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_convex(const StepArgs* args, int single, int plain_loop, hipStream_t stream);
-extern "C" int mir_launch_step(const StepArgs* args, int max_contacts_lds, hipStream_t stream) {
-  StepArgs a = *args;
-  int blocks = (a.B + EPB - 1) / EPB;
-  (void)max_contacts_lds;
-#ifdef MIR_PROFILE_SINGLE
-  const bool prof_blocks_single = false;
-#else
-  const bool prof_blocks_single = a.prof != nullptr;
-#endif
-  const bool single = a.mode == 0 && a.n_steps == 1 && !a.act_step && !a.rows_step && !a.ar.episode_len && !prof_blocks_single && !a.out_M && !a.out_bias &&
-                      !a.out_qas && !a.out_qacc && !a.out_xpos && !a.out_xquat;
-  const bool plain_loop = a.mode == 0 && !a.prof && !a.out_M && !a.out_bias && !a.out_qas && !a.out_qacc && !a.out_xpos && !a.out_xquat && !a.agent_pos &&
-                          !a.env_state && !a.reward && !a.terminated && !a.term_host && !a.done_ticket;
-  if (a.phase == 2) {  // (the second half of a split step has no collision code in it: one instantiation serves every scene)
-    hipLaunchKernelGGL((mir_step_kernel<4, 0>), dim3(blocks), dim3(64), 0, stream, a);
-    return (int)hipGetLastError();
+static int launch_feat(const StepArgs& a, int kind, int blocks, hipStream_t stream) {
+  switch (kind) {
+    case STEP_POST: if constexpr (FEAT == FEAT_PLAIN) return launch_kind<STEP_POST, FEAT>(a, blocks, stream); else break;
+    case STEP_PRE: return launch_kind<STEP_PRE, FEAT>(a, blocks, stream);
+    case STEP_ROTATED: return launch_kind<STEP_ROTATED, FEAT>(a, blocks, stream);
+    case STEP_LIST48: return launch_kind<STEP_LIST48, FEAT>(a, blocks, stream);
+    case STEP_HEAVY48: return launch_kind<STEP_HEAVY48, FEAT>(a, blocks, stream);
+    case STEP_POST48: return launch_kind<STEP_POST48, FEAT>(a, blocks, stream);
+    case STEP_PRE48: return launch_kind<STEP_PRE48, FEAT>(a, blocks, stream);
+    case STEP_ROTATED_LIST: return launch_kind<STEP_ROTATED_LIST, FEAT>(a, blocks, stream);
+    case STEP_XR16: return launch_kind<STEP_XR16, FEAT>(a, blocks, stream);
+    case STEP_XR48: return launch_kind<STEP_XR48, FEAT>(a, blocks, stream);
+    case STEP_SINGLE: return launch_kind<STEP_SINGLE, FEAT>(a, blocks, stream);
+    case STEP_LOOP: return launch_kind<STEP_LOOP, FEAT>(a, blocks, stream);
+    case STEP_FULL: if constexpr ((FEAT & FEAT_SPEC) == 0) return launch_kind<STEP_FULL, FEAT>(a, blocks, stream); else break;
   }
-  if (a.features) return mir_launch_step_convex(&a, single, plain_loop, stream);
-  if (a.phase == 1) hipLaunchKernelGGL((mir_step_kernel<3, 0>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 3) hipLaunchKernelGGL((mir_step_kernel<5, 0>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 4) hipLaunchKernelGGL((mir_step_kernel<6, 0, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 5) hipLaunchKernelGGL((mir_step_kernel<7, 0, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 6) hipLaunchKernelGGL((mir_step_kernel<9, 0, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 7) hipLaunchKernelGGL((mir_step_kernel<10, 0, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 8) hipLaunchKernelGGL((mir_step_kernel<11, 0>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (a.phase == 12) hipLaunchKernelGGL((mir_step_kernel<12, 0>), dim3(blocks), dim3(64), 0, stream, a);
-  else if (a.phase == 13) hipLaunchKernelGGL((mir_step_kernel<13, 0, 3>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (single) hipLaunchKernelGGL((mir_step_kernel<0, 0>), dim3(blocks), dim3(128), 0, stream, a);
-  else if (plain_loop) hipLaunchKernelGGL((mir_step_kernel<1, 0>), dim3(blocks), dim3(64), 0, stream, a);
-  else hipLaunchKernelGGL((mir_step_kernel<2, 0>), dim3(blocks), dim3(64), 0, stream, a);
-  return (int)hipGetLastError();
+  return (int)hipErrorInvalidValue;
+}
+#ifdef MIR_STEP_CONVEX_TU
+extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_convex(const StepArgs* args, int kind, hipStream_t stream) {
+  const StepArgs& a = *args;
+  const int blocks = (a.B + EPB - 1) / EPB;
+  // the headline scene's instantiation (FEAT_SPEC: mir_create found SpecPick::matches); the everything-variant stays generic
+  if ((a.features & FEAT_SPEC) && kind != STEP_FULL) return launch_feat<FEAT_CONVEX | FEAT_SPEC>(a, kind, blocks, stream);
+  if (a.features & FEAT_SAP) return launch_feat<FEAT_CONVEX | FEAT_SAP>(a, kind, blocks, stream);  // sweep-and-prune scenes carry the convex code too
+  return launch_feat<FEAT_CONVEX>(a, kind, blocks, stream);
+}
+#else
+extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_convex(const StepArgs* args, int kind, hipStream_t stream);
+extern "C" int mir_launch_step(const StepArgs* args, hipStream_t stream) {
+  const StepArgs& a = *args;
+  const int blocks = (a.B + EPB - 1) / EPB;
+  // a whole step (STEP_FULL asked for) takes the leanest instantiation that has everything the arguments use
+  int kind = a.kind;
+  if (kind == STEP_FULL) {
+#ifdef MIR_PROFILE_SINGLE
+    const bool prof_blocks_single = false;
+#else
+    const bool prof_blocks_single = a.prof != nullptr;
+#endif
+    const bool single = a.mode == 0 && a.n_steps == 1 && !a.act_step && !a.rows_step && !a.ar.episode_len && !prof_blocks_single && !a.out_M && !a.out_bias &&
+                        !a.out_qas && !a.out_qacc && !a.out_xpos && !a.out_xquat;
+    const bool plain_loop = a.mode == 0 && !a.prof && !a.out_M && !a.out_bias && !a.out_qas && !a.out_qacc && !a.out_xpos && !a.out_xquat && !a.agent_pos &&
+                            !a.env_state && !a.reward && !a.terminated && !a.term_host && !a.done_ticket;
+    kind = single ? STEP_SINGLE : (plain_loop ? STEP_LOOP : STEP_FULL);
+  }
+  if (a.features && !step_post_only(kind)) return mir_launch_step_convex(&a, kind, stream);
+  return launch_feat<FEAT_PLAIN>(a, kind, blocks, stream);
 }
 #endif

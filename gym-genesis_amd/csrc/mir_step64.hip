@@ -33,6 +33,7 @@
 
 #include "mir_model64.h"
 #include "mir_step64.h"
+#include "mir_step.h"  // StepKind: STEP_SINGLE / STEP_LOOP / STEP_FULL
 
 #define G 16
 #include "mir_dev.h"
@@ -416,7 +417,8 @@ __device__ __forceinline__ void condot3x3(const Env64& S, int c, const float* x,
 // ---------------------------------------------------------------------------------------------
 // SINGLE = one full step per launch without the rollout / autoreset / per-stage-output options: no step loop, hence none of
 // the scalar-register spills the loop structure forces (see mir_step.hip).
-// VARIANT 0 = SINGLE; 1 = the step loop of rollouts (packed rows only, no per-stage / separate outputs); 2 = everything.
+// VARIANT = STEP_SINGLE; STEP_LOOP = the step loop of rollouts (packed rows only, no per-stage / separate outputs); STEP_FULL = everything
+// (the first three StepKinds of mir_step.h, with the same meaning).
 // DUAL (the single-step instantiation): the workgroup is TWO waves on one env.  Wave 1 stages the model tables, then -- once
 // wave 0 has the body poses -- runs the whole collision phase (geom poses, broadphase, plane-box, box-box, contact finish, per-block
 // lists) in its own scratch while wave 0 runs the dynamics up to the smooth solve; they meet before the Jacobian segments are
@@ -425,9 +427,9 @@ __device__ __forceinline__ void condot3x3(const Env64& S, int c, const float* x,
 // here, as in the 16-lane kernel): plane - sphere / capsule in closed form, every other pair that is not box - box through GJK on
 // the cores and MPR (mir_convex.h), lane = candidate pair.
 template <int VARIANT, bool CONVEX>
-__global__ __launch_bounds__(VARIANT == 0 ? 128 : 64) __attribute__((amdgpu_waves_per_eu(VARIANT == 0 ? 2 : 1, VARIANT == 0 ? 2 : 1)))
+__global__ __launch_bounds__(VARIANT == STEP_SINGLE ? 128 : 64) __attribute__((amdgpu_waves_per_eu(VARIANT == STEP_SINGLE ? 2 : 1, VARIANT == STEP_SINGLE ? 2 : 1)))
 void mir_step64_kernel(StepArgs64 a) {
-  constexpr bool SINGLE = VARIANT == 0;
+  constexpr bool SINGLE = VARIANT == STEP_SINGLE;
   constexpr bool DUAL = SINGLE;
   __shared__ __attribute__((aligned(16))) Env64 S;
   const DevModel64* __restrict__ m = a.model;
@@ -1196,7 +1198,7 @@ void mir_step64_kernel(StepArgs64 a) {
     a.prof = nullptr;
 #endif
   }
-  if (VARIANT == 1) { a.mode = 0; a.out_M = a.out_bias = a.out_qas = a.out_qacc = a.out_xpos = a.out_xquat = nullptr; a.prof = nullptr; a.agent_pos = a.env_state = a.reward = nullptr; a.terminated = a.term_host = nullptr; }
+  if (VARIANT == STEP_LOOP) { a.mode = 0; a.out_M = a.out_bias = a.out_qas = a.out_qacc = a.out_xpos = a.out_xquat = nullptr; a.prof = nullptr; a.agent_pos = a.env_state = a.reward = nullptr; a.terminated = a.term_host = nullptr; }
   // packed output row [agent_pos | env_state | reward | terminated] of the current kinematic state
   const int eb = m->eef_body, ob = m->obj_body, ob2 = m->obj2_body;
   const int ad = m->agent_dim, ed = m->env_dim;
@@ -2066,13 +2068,13 @@ extern "C" int mir_launch_step64(const StepArgs64* args, hipStream_t stream) {
   const bool plain_loop = a.mode == 0 && !a.prof && !a.out_M && !a.out_bias && !a.out_qas && !a.out_qacc && !a.out_xpos && !a.out_xquat && !a.agent_pos &&
                           !a.env_state && !a.reward && !a.terminated && !a.term_host;
   if (a.convex) {
-    if (single) hipLaunchKernelGGL((mir_step64_kernel<0, true>), dim3(a.B), dim3(128), 0, stream, a);  // two waves per env
-    else if (plain_loop) hipLaunchKernelGGL((mir_step64_kernel<1, true>), dim3(a.B), dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL((mir_step64_kernel<2, true>), dim3(a.B), dim3(64), 0, stream, a);
+    if (single) hipLaunchKernelGGL((mir_step64_kernel<STEP_SINGLE, true>), dim3(a.B), dim3(128), 0, stream, a);  // two waves per env
+    else if (plain_loop) hipLaunchKernelGGL((mir_step64_kernel<STEP_LOOP, true>), dim3(a.B), dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((mir_step64_kernel<STEP_FULL, true>), dim3(a.B), dim3(64), 0, stream, a);
   } else {
-    if (single) hipLaunchKernelGGL((mir_step64_kernel<0, false>), dim3(a.B), dim3(128), 0, stream, a);  // two waves per env
-    else if (plain_loop) hipLaunchKernelGGL((mir_step64_kernel<1, false>), dim3(a.B), dim3(64), 0, stream, a);
-    else hipLaunchKernelGGL((mir_step64_kernel<2, false>), dim3(a.B), dim3(64), 0, stream, a);
+    if (single) hipLaunchKernelGGL((mir_step64_kernel<STEP_SINGLE, false>), dim3(a.B), dim3(128), 0, stream, a);  // two waves per env
+    else if (plain_loop) hipLaunchKernelGGL((mir_step64_kernel<STEP_LOOP, false>), dim3(a.B), dim3(64), 0, stream, a);
+    else hipLaunchKernelGGL((mir_step64_kernel<STEP_FULL, false>), dim3(a.B), dim3(64), 0, stream, a);
   }
   return (int)hipGetLastError();
 }

@@ -1,37 +1,22 @@
 // mir_step_body.inc -- the body of mir_step_kernel (mir_step.hip), included there twice: as the kernel's own body for every
-// instantiation but VARIANT 13, and as the body of one pass of VARIANT 13's step loop (mir_step_pass).  Not a header of its own.
-  // VARIANT 5 = both halves in one launch, ROTATED: first the action-dependent half of THIS step (from the pre buffer), then the
-  // action-independent half of the NEXT one (into the pre buffer).  The host sees `terminated` after the first half; the second
-  // runs while it is between two env.step() calls, without a second launch, a second prologue or a second forward kinematics
-  // (the closing FK of this step is the opening FK of the next).  Needs the split closing FK (fk_free_leaf scenes).
-  constexpr bool ROT = VARIANT == 5 || VARIANT == 8 || VARIANT == 9 || VARIANT == 11;
-  // (VARIANT 11, CPL = 1 = the rotated launch's first pass alone for a LIST of envs: the second half of the step for the envs of an
-  //  overflow run that are at most at 16 points -- one round of 40 KB workgroups beside VARIANT 9's list of the others)
-  constexpr bool FIRSTONLY = VARIANT == 9 || VARIANT == 11;
-  // VARIANT 9 / 10 (CPL = 3) = the two halves of a step with three contacts per lane, as TWO launches: what mir_step_begin launches for
-  // the whole batch while some env is above 16 points (an OVERFLOW RUN).  9 = the second half of this step from the scratch rows -- an
-  // env with 17 .. 48 contacts has its row in StepArgs::pre_big, written by the launch before -- up to the outputs and the terminated
-  // bytes (the rotated launch's first pass, then it returns); 10 = the first half of the next step with the 48-point capacity (VARIANT 3
-  // with three contacts per lane).  The bytes of EVERY env leave after a solver pass -- two rounds of short workgroups -- instead of
-  // after two rounds of whole steps (the heavy phase) or a fused pass of the list instantiation behind the main launch's bytes; the first
-  // halves run while the host is between two env.step calls.  (8 = both in one rotated launch: measured, no better than the heavy phase
-  // -- the second round's bytes wait for the first round's first halves -- and not instantiated.)
-  constexpr bool BIGV = (VARIANT >= 6 && VARIANT <= 10) || VARIANT == 13;  // three contacts per lane: the whole step in one pass (two waves, as VARIANT 0) ...
-  constexpr bool BIG2 = VARIANT == 6;                  // ... then the outputs, then the action-independent half of the next step (the list instantiation)
-  constexpr bool PRE = VARIANT == 3 || VARIANT == 10, POST = VARIANT == 4;
-  constexpr bool SINGLE = VARIANT == 0 || PRE || POST || ROT || BIGV;
-  constexpr bool DUAL = VARIANT == 0 || PRE || ROT || BIGV;
-  constexpr bool XR = VARIANT == 12 || VARIANT == 13;  // (mir_rollout_exact)
+// instantiation but STEP_XR48, and as the body of one pass of STEP_XR48's step loop (mir_step_pass).  Not a header of its own.
+  // the body's compile-time switches: all from the table of kinds (mir_step.h, where each kind is described)
+  constexpr bool ROT = step_rotated(VARIANT), FIRSTONLY = step_first_pass_only(VARIANT);
+  constexpr bool BIGV = step_big(VARIANT), BIG2 = step_fused_next_pre(VARIANT);
+  constexpr bool PRE = step_pre_only(VARIANT), POST = step_post_only(VARIANT);
+  constexpr bool SINGLE = !step_has_loop(VARIANT), DUAL = step_waves(VARIANT) == 2;
+  constexpr bool XR = step_exact_rollout(VARIANT);  // (mir_rollout_exact)
+  constexpr bool DEFER = step_defers(VARIANT);
   constexpr int MAXCON = G * CPL;
-  static_assert(CPL == 1 || BIGV, "several contacts per lane: the list instantiation only");
+  static_assert(CPL == step_cpl(VARIANT), "the kind fixes the contacts per lane");
   static_assert(JST == 52 && K16_PRE_STRIDE >= K16_PRE_JB + JST * K16_MAX_CONTACT, "pre-buffer layout");
   typedef EnvLdsT<CPL> EnvLds;
-  constexpr bool CONVEX = (FEAT & 1) != 0, SAP = (FEAT & 2) != 0, SPEC = (FEAT & 4) != 0;
+  constexpr bool CONVEX = (FEAT & FEAT_CONVEX) != 0, SAP = (FEAT & FEAT_SAP) != 0, SPEC = (FEAT & FEAT_SPEC) != 0;
   __shared__ __attribute__((aligned(16))) EnvLds s_env[EPB];
 #define CFB(Sx, c) (CPL == 1 ? (Sx).con.cfb[CPL == 1 ? (c) : 0] : (Sx).con.cpos[c])
   __shared__ __attribute__((aligned(16))) ModelTab T;  // dynamically indexed model tables, one copy per workgroup
   // hull vertices (MIR_GEOM_HULL), convex instantiations only: what is left of the workgroup's 40 KB
-  __shared__ __attribute__((aligned(16))) float s_hull[(FEAT & 1) ? K16_MAX_VERT : 1][4];
+  __shared__ __attribute__((aligned(16))) float s_hull[CONVEX ? K16_MAX_VERT : 1][4];
   // three contacts per lane: the collision wave HELPS in the Newton loop (it would wait at barrier (5) meanwhile) -- the contacts of the
   // slots above the first are its share of the gradient and of the Hessian update.  [0] request (iteration + 1, -1 = the loop is over),
   // [1] its gradient share of that iteration is in LDS, [2] its Hessian share is (see helper_newton)
@@ -58,21 +43,21 @@
     for (int k = 0; k < TAB_NPASS; k++) tabtmp[k] = src[min(tid + 64 * k, TAB_NQ - 1)];
   }
   f4 hulltmp = {0, 0, 0, 0};
-  if ((FEAT & 1) && wave == 0) hulltmp = reinterpret_cast<const f4*>(&m->hverts[0][0])[min(tid, K16_MAX_VERT - 1)];
+  if (CONVEX && wave == 0) hulltmp = reinterpret_cast<const f4*>(&m->hverts[0][0])[min(tid, K16_MAX_VERT - 1)];
   const int lane = tid & (G - 1);
   const int row4 = (tid & ~(G - 1)) << 2;  // byte offset of this env's first lane in the wave (lane_gather)
   const int grp = tid >> 4;
   const int jbs = (grp & 1) * JB_SKEW;  // (EnvLds::Jb_)
   const int env_raw = blockIdx.x * EPB + grp;
-  // (VARIANT 13: the list's length is on the device; a workgroup past it leaves before anything else -- both waves, no barrier yet)
-  const int xr_n = VARIANT == 13 ? *a.xr_count : a.B;
-  if (VARIANT == 13 && (int)blockIdx.x * EPB >= xr_n) return;
+  // (STEP_XR48: the list's length is on the device; a workgroup past it leaves before anything else -- both waves, no barrier yet)
+  const int xr_n = VARIANT == STEP_XR48 ? *a.xr_count : a.B;
+  if (VARIANT == STEP_XR48 && (int)blockIdx.x * EPB >= xr_n) return;
   bool valid = env_raw < xr_n;
   int env = valid ? env_raw : xr_n - 1;
   // (exact contacts: the action-independent half for a LIST of envs -- the ones the wave kernel has just stepped; see StepArgs::env_list)
-  if constexpr (VARIANT == 3 || VARIANT == 11 || BIGV) { if (a.env_list) env = a.env_list[env]; }
-  // (VARIANT 13: an env of the list takes this step once it has reached it and until it is handed on to the wave kernel)
-  if constexpr (VARIANT == 13) valid = valid && a.xr_start[env] <= a.xr_step;
+  if constexpr (step_reads_env_list(VARIANT)) { if (a.env_list) env = a.env_list[env]; }
+  // (STEP_XR48: an env of the list takes this step once it has reached it and until it is handed on to the wave kernel)
+  if constexpr (VARIANT == STEP_XR48) valid = valid && a.xr_start[env] <= a.xr_step;
   EnvLds& S = s_env[grp];
 
   // (SPEC: the headline scene's sizes and options are literals -- SpecPick, emitted by mir_compile into mir_spec_pick.h -- so
@@ -177,17 +162,16 @@
   // the task's object is a free body hanging off the world: its height -- all that `terminated` needs -- is a qpos entry, final as
   // soon as the translations are integrated, so the host-visible bytes can leave before the closing FK (wave-uniform)
   const int mdl_obj_qadr = SPEC ? SpecPick::obj_qadr : m->obj_qadr;
-  const bool term_early = VARIANT != 1 && fk_free_leaf && mdl_obj_qadr >= 0;
+  const bool term_early = step_sends_host_bytes(VARIANT) && fk_free_leaf && mdl_obj_qadr >= 0;
   // ... and before the solver has converged where the mask provably cannot change any more (see mir_model.h: term_bound_ok)
-  // (VARIANT 9, the second-half launch of an overflow run: two rounds of workgroups, and the step's bytes wait for the second round's --
+  // (STEP_POST48, the second-half launch of an overflow run: two rounds of workgroups, and the step's bytes wait for the second round's --
   //  from inside the solver loop they leave at the first gradient instead of behind the last Newton iteration of 17 - 48 contacts)
-  const bool term_bound = (VARIANT == 0 || VARIANT == 5 || VARIANT == 9 || VARIANT == 11) && term_early && m->term_bound_ok != 0 && a.term_host != nullptr && !a.no_early_mask;
+  const bool term_bound = step_early_bytes_in_solver(VARIANT) && term_early && m->term_bound_ok != 0 && a.term_host != nullptr && !a.no_early_mask;
   const int term_zlane = SPEC ? SpecPick::term_zlane : m->term_zlane;
   // exact contacts (StepArgs::exact): an env whose candidate contact points exceed this is DEFERRED to the wave kernel -- the launch
   // computes on (its lanes cannot leave the wave) but stores nothing for it and flags its terminated byte (wave-uniform; never without the flag)
   // (StepArgs::exact == 2, a test switch: EVERY env is deferred -- the whole batch then takes the list instantiation; the list
   //  instantiation itself defers what exceeds ITS capacity, to the wave-per-env kernel)
-  constexpr bool DEFER = VARIANT == 0 || VARIANT == 4 || VARIANT == 5 || VARIANT == 11 || VARIANT == 12 || BIGV;
   const int defer_above = BIGV ? MAXCON : ((DEFER && a.exact) ? (a.exact == 2 ? -1 : (max_contacts < MAXCON ? max_contacts : MAXCON)) : 0x7fffffff);
   bool ovf_env = false;  // this lane's env is deferred: set where the step reads the `coupled` word (uniform over the env's row)
   bool over_env = false; // (three contacts per lane: the env had more candidate points than StepArgs::over_cap -- bit 6 of its terminated byte)
@@ -1007,7 +991,7 @@
         // (the first-half launch of an overflow run tells the host which envs the next step finds above the one-contact-per-lane capacity
         //  -- a tagged byte per env, a word per workgroup, in pinned memory -- so that its second half can go out as two lists: those on
         //  the three-contacts-per-lane instantiation, the others in one round of the one-contact-per-lane kernel's workgroups)
-        if (VARIANT == 10 && a.next_host) {
+        if (VARIANT == STEP_PRE48 && a.next_host) {
           const unsigned long long fb = __ballot(valid && pts0 > a.over_cap && lane == 0);
           if (tid == 0) {
             const uint32_t bits = (uint32_t)(fb & 1u) | (uint32_t)(fb >> 16 & 1u) << 8 | (uint32_t)(fb >> 32 & 1u) << 16 | (uint32_t)(fb >> 48 & 1u) << 24;
@@ -1098,7 +1082,7 @@
 #pragma unroll
     for (int k = 0; k < TAB_NPASS; k++)
       if (tid + 64 * k < TAB_NQ) dst[tid + 64 * k] = tabtmp[k];
-    if ((FEAT & 1) && tid < K16_MAX_VERT) stv(s_hull[tid], hulltmp);
+    if (CONVEX && tid < K16_MAX_VERT) stv(s_hull[tid], hulltmp);
   }
   if (!DUAL || ROT) {
     if (lane < a.qst) S.qpos[lane] = q_lo;
@@ -1133,14 +1117,14 @@
   // (the action-independent half alone integrates nothing.  Of the scene-specialised instantiations the ROTATED launch stores poses too
   //  since round 5 -- the pointer test costs it nothing measurable, and the steps of the pixel modes keep the faster instantiation; the
   //  fused launch lost 2 % to the same code, so a fused launch that wants poses takes the generic-scene instantiation: launch() in mir_api.hip)
-  if (PRE || (SPEC && !ROT && !BIGV)) a.poses = nullptr;
-  if (SINGLE) { a.mode = 0; a.act_step = 0; if (VARIANT != 13) { a.rows_step = 0; a.ar.episode_len = nullptr; } a.out_M = a.out_bias = a.out_qas = a.out_qacc = a.out_xpos = a.out_xquat = nullptr;
+  if (PRE || (SPEC && !step_spec_stores_poses(VARIANT))) a.poses = nullptr;
+  if (SINGLE) { a.mode = 0; a.act_step = 0; if (VARIANT != STEP_XR48) { a.rows_step = 0; a.ar.episode_len = nullptr; } a.out_M = a.out_bias = a.out_qas = a.out_qacc = a.out_xpos = a.out_xquat = nullptr;
 #ifndef MIR_PROFILE_SINGLE  /* (a profiling build keeps the phase stamps in the single-step instantiation: tools/phase_profile.py) */
     a.prof = nullptr;
 #endif
   }
-  if (VARIANT == 13) { a.poses = nullptr; a.agent_pos = a.env_state = a.reward = nullptr; a.terminated = a.term_host = nullptr; a.done_ticket = nullptr; }
-  if (VARIANT == 1 || VARIANT == 12) { a.mode = 0; a.out_M = a.out_bias = a.out_qas = a.out_qacc = a.out_xpos = a.out_xquat = nullptr; a.prof = nullptr; a.agent_pos = a.env_state = a.reward = nullptr; a.terminated = a.term_host = nullptr; a.done_ticket = nullptr; }
+  if (VARIANT == STEP_XR48) { a.poses = nullptr; a.agent_pos = a.env_state = a.reward = nullptr; a.terminated = a.term_host = nullptr; a.done_ticket = nullptr; }
+  if (step_rows_only(VARIANT)) { a.mode = 0; a.out_M = a.out_bias = a.out_qas = a.out_qacc = a.out_xpos = a.out_xquat = nullptr; a.prof = nullptr; a.agent_pos = a.env_state = a.reward = nullptr; a.terminated = a.term_host = nullptr; a.done_ticket = nullptr; }
   // packed output row [agent_pos | env_state | reward | terminated] of the current kinematic state
   const int eb = mdl_eef, ob = mdl_obj;
   const int ad = 7 + mdl_ngrip;
@@ -1186,7 +1170,7 @@
   // launch after its first pass) -------------------------------------------------------------------------------------------
   auto emit_outputs = [&]() {
     STAMP(10);
-    if constexpr (VARIANT == 13) {  // (an env beyond this instantiation's capacity: on to the wave kernel from this step on, nothing stored)
+    if constexpr (VARIANT == STEP_XR48) {  // (an env beyond this instantiation's capacity: on to the wave kernel from this step on, nothing stored)
       if (valid && ovf_env && lane == 0) {
         a.xr_start[env] = a.xr_step | XR_TIER2;
         a.xr_list2[atomicAdd(a.xr_count2, 1)] = env;
@@ -1199,7 +1183,7 @@
     // state and observation stores below.  The tag changes from launch to launch, so the host recognises the bytes of THIS launch by
     // themselves (sync mode 3: no fence, no ticket, nothing waits).
     const bool term_now = valid && !ovf_env && above(S.xpos[ob][2], mdl_reward_z);
-    if (VARIANT != 1 && a.term_host && !term_early) {
+    if (step_sends_host_bytes(VARIANT) && a.term_host && !term_early) {
       const unsigned long long tb = __ballot(term_now && lane == 0), db = __ballot(ovf_env && valid && lane == 0), ob = BIGV ? __ballot(over_env && valid && lane == 0) : 0ull;
       if (tid == 0) {
         const uint32_t bits = (uint32_t)(tb & 1u) | (uint32_t)(tb >> 16 & 1u) << 8 | (uint32_t)(tb >> 32 & 1u) << 16 | (uint32_t)(tb >> 48 & 1u) << 24 |
@@ -1242,7 +1226,7 @@
         st4(&a.out_xquat[((size_t)env * nb + lane) * 4], ld4v(S.xquat[lane]));
       }
     }  // valid
-    if (VARIANT != 1 && a.done_ticket) {
+    if (step_sends_host_bytes(VARIANT) && a.done_ticket) {
       // Completion published by the kernel itself (mir_step_begin, sync mode 2): every wave waits for its host store to be
       // acknowledged (~3 us over PCIe), then takes a ticket; the wave that takes the last one knows that every terminated byte of the launch is in
       // host memory and writes the sequence number the host is spinning on.  (The host-side stores above are system-scope
@@ -1458,7 +1442,7 @@
     {
       f4 r0, r1, r2, r3;
       if (post_now) {
-        // the action-independent half of this step was computed by the previous launch (VARIANT 3): mass-matrix row and bias force
+        // the action-independent half of this step was computed by the previous launch (STEP_PRE): mass-matrix row and bias force
         // from the pre buffer, then the smooth force with THIS launch's targets (the expressions of the fused kernel)
         r0 = pre_m[0]; r1 = pre_m[1]; r2 = pre_m[2]; r3 = pre_m[3];
         qfrc_bias = pre_bias;
@@ -1591,10 +1575,10 @@
     const int nefc = 4 * ncon + __popc(limmask);
     // the Hessian is block diagonal by tree unless a contact joins the arm and the cube somewhere in this wave
     const int cpl = S.coupled;  // bit 0: some contact joins the trees; bits 1 .. 16: contact c belongs to the second tree; 20 .. 27: see contacts_build
-    if (DEFER && VARIANT != 12 && (!ROT || step == 0)) ovf_env = ((cpl >> 20) & 255) > defer_above;  // (exact contacts: more candidate points than lanes)
-    if constexpr (VARIANT == 12) {
+    if (DEFER && VARIANT != STEP_XR16 && (!ROT || step == 0)) ovf_env = ((cpl >> 20) & 255) > defer_above;  // (exact contacts: more candidate points than lanes)
+    if constexpr (VARIANT == STEP_XR16) {
       // hand-off (mir_rollout_exact): nothing of this step has touched the state rows in LDS yet -- they are the step's starting state,
-      // stored here once; the env's later steps are VARIANT 13's (or the wave kernel's), from step `step` on
+      // stored here once; the env's later steps are STEP_XR48's (or the wave kernel's), from step `step` on
       const bool now = ((cpl >> 20) & 255) > defer_above;
       if (valid && now && !ovf_env) {
         for (int i = lane; i < qst; i += G) a.qpos[(size_t)env * qst + i] = S.qpos[i];
@@ -2095,7 +2079,7 @@
       if (d_kind < 2) S.qpos[d_qadr] += dt * qd;
       else if (d_kind == 2) S.qpos[T.b_info[d_body][2] + d_axis_k] += dt * qd;
     }
-    if (VARIANT != 1 && a.term_host && term_early) {
+    if (step_sends_host_bytes(VARIANT) && a.term_host && term_early) {
       // GenesisEnv.step's D->H copy of `terminated`, done by the kernel: see the epilogue; here ~1 us earlier, so that the trip
       // over PCIe is over when the launch ends
       WSYNC();
@@ -2214,7 +2198,7 @@
       const int r = step_body(step);
       if (r == 2) return;
       if (r == 1) break;
-      if (VARIANT == 12 && !__any(valid && !ovf_env)) return;  // (every env of the wave handed off: nothing more to store)
+      if (VARIANT == STEP_XR16 && !__any(valid && !ovf_env)) return;  // (every env of the wave handed off: nothing more to store)
     }
     emit_outputs();
   }

@@ -1,4 +1,4 @@
-"""(-DMIR_PROFILE_SINGLE build) time line of one workgroup of the SECOND-HALF launch of an overflow run (mir_step_kernel<9, ., 3>: rows from
+"""(-DMIR_PROFILE_SINGLE build) time line of one workgroup of the SECOND-HALF launch of an overflow run (STEP_POST48, mir_step_kernel<9, ., 3>: rows from
 the scratch rows, solver, outputs) on the reference's expert episode at 4096 envs, envs in their natural order (MIR_EXACT_HEAVY_SORT=0):
 stamps of both waves in shader cycles after the kernel's entry, averaged over the profiled launches whose watched workgroup held at
 least `min_contacts` contacts in one of its envs.  Usage: python3 tools/probes/big_timeline.py [min_contacts]"""

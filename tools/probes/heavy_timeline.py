@@ -1,5 +1,5 @@
 """(-DMIR_PROFILE_SINGLE build) time line of one workgroup of the three-contacts-per-lane instantiation stepping the WHOLE batch (a HEAVY
-step of exact contacts, mir_step_kernel<7, ., 3>) on the reference's expert episode (examples/franka/pick_cube_state.py) at 4096 envs,
+step of exact contacts, STEP_HEAVY48, mir_step_kernel<7, ., 3>) on the reference's expert episode (examples/franka/pick_cube_state.py) at 4096 envs,
 MIR_EXACT_HEAVY=1,1: stamps of both waves in shader cycles after the kernel's entry, averaged over the profiled launches whose watched
 workgroup held at least `min_contacts` contacts in one of its envs.  Usage: python3 tools/probes/heavy_timeline.py [min_contacts]"""
 import ctypes as C, importlib.util, os, sys

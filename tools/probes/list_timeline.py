@@ -1,4 +1,4 @@
-"""(-DMIR_PROFILE_SINGLE build) time line of one workgroup of the LIST INSTANTIATION of exact contacts (mir_step_kernel<6, ., 3>): the
+"""(-DMIR_PROFILE_SINGLE build) time line of one workgroup of the LIST INSTANTIATION of exact contacts (STEP_LIST48, mir_step_kernel<6, ., 3>): the
 scripted grasp of tests/golden/grasp_targets.json on a scene whose every env takes the deferred envs' route (set_exact_contacts("all")),
 profiled in the closed-grasp stage (pads on the cube, fingertips on the floor: 20+ candidate points).  Every stamp both waves left in
 the FIRST pass (the whole step), sorted, in shader cycles after the kernel's entry; the end of the second pass (next step's

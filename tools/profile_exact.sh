@@ -1,7 +1,7 @@
 #!/bin/bash
 # Run on the GPU box from the repo root: kernel-trace stats of the scripted grasp through GenesisEnv.step with and without exact
 # contacts (tools/exact_time.py), then of the reference's expert (tools/expert_time.py): the launches of the three-contacts-per-lane
-# instantiation -- mir_step_kernel<6, 5, 3> on the list of deferred envs, mir_step_kernel<7, 5, 3> on the whole batch in a heavy phase --
+# instantiation -- STEP_LIST48 = mir_step_kernel<6, 5, 3> on the list of deferred envs, STEP_HEAVY48 = mir_step_kernel<7, 5, 3> on the whole batch in a heavy phase --
 # beside the rotated launches.  Summaries -> gpurun_out/exact_kernel_stats.csv, gpurun_out/expert_kernel_stats.csv, *.log.
 set -u
 R=$(pwd)
