@@ -193,13 +193,20 @@ struct Outs {
   int nlist = 0;
   uint32_t* next_host = nullptr;      // 16-lane kernel, STEP_PRE48 (StepArgs::next_host)
   unsigned long long* prof = nullptr;  // 16-lane kernel only (debug)
+  // contact force sensing (mir_contact_forces; StepArgs::cf_*)
+  int32_t *cf_ncon = nullptr, *cf_ids = nullptr;
+  uint8_t* cf_flags = nullptr;
+  float *cf_geom = nullptr, *cf_force = nullptr, *cf_link = nullptr;
 };
 
 int launch(MirScene* h, const Outs& o, void* stream) {
   int rc;
+  // (a contact sensor read moves no state and writes no scratch row: `pre` stays as valid as it was, so the rotated launches of
+  //  GenesisEnv.step go on undisturbed behind it)
+  const bool sense = o.mode == 1 && (o.cf_ncon || o.cf_flags || o.cf_ids || o.cf_geom || o.cf_force || o.cf_link);
   // (STEP_LIST48 -- the list instantiation of exact contacts -- steps the envs the pending step's launch deferred and writes THEIR scratch
   //  rows for the state it leaves: it completes that launch, the handle's bookkeeping is the pending step's)
-  if (!step_keeps_pre(o.kind) && o.mode != 2) h->pre_valid = 0;  // (whatever this launch is, the state it leaves is not the one `pre` was made from)
+  if (!step_keeps_pre(o.kind) && o.mode != 2 && !sense) h->pre_valid = 0;  // (whatever this launch is, the state it leaves is not the one `pre` was made from)
   // Link poses for the rasteriser.  Once a render has been asked for (poses_live), every launch that integrates also leaves the
   // link poses of its final state in h->poses -- its closing forward kinematics has them -- so that a render behind a step needs
   // no pose-refresh launch (6 us per 1024 envs).  poses_current: h->poses matches qpos for every env.
@@ -228,6 +235,8 @@ int launch(MirScene* h, const Outs& o, void* stream) {
     a.exact = o.exact; a.over_cap = o.over_cap;
     a.pre_big = step_uses_pre_big(o.kind) ? h->pre_big : nullptr;
     a.next_host = o.next_host;
+    a.cf_ncon = o.cf_ncon; a.cf_flags = o.cf_flags; a.cf_ids = o.cf_ids; a.cf_geom = o.cf_geom; a.cf_force = o.cf_force; a.cf_link = o.cf_link;
+    if (step_forward_only(o.kind)) a.features &= ~FEAT_SPEC;  // (off the hot path: the generic-scene instantiation)
     if (o.env_list) { a.env_list = o.env_list; a.B = o.nlist; }
     if (o.kind == STEP_LIST48) a.term_wstride = 1;  // (the terminated byte of list entry k is byte k of term_host)
     rc = mir_launch_step(&a, (hipStream_t)stream);
@@ -245,6 +254,7 @@ int launch(MirScene* h, const Outs& o, void* stream) {
     a.rows = o.rows; a.row_stride = o.row_stride; a.mode = o.mode; a.n_steps = o.n_steps; a.prof = o.prof;
     a.act_step = o.act_step; a.rows_step = o.rows_step; a.ar = o.ar;
     a.term_host = o.term_host; a.term_tag = o.term_tag;
+    a.cf_ncon = o.cf_ncon; a.cf_flags = o.cf_flags; a.cf_ids = o.cf_ids; a.cf_geom = o.cf_geom; a.cf_force = o.cf_force; a.cf_link = o.cf_link;
     auto order = [&]() {  // the single-step launches read one cost buffer and write the other
       if (!h->cost) return;
       a.cost_in = h->cost + (size_t)h->cost_par * h->cost_stride;
@@ -757,6 +767,10 @@ int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* en
     }
   } else {
     rc = launch(h, o, stream);
+    // (an overflow-run step whose envs are ALL at most at 16 points goes out as the one-contact-per-lane list alone: launch() takes
+    //  STEP_ROTATED_LIST for the second list of a step that the first list has counted -- here there is no first list, so the step is
+    //  counted here; it used to go uncounted, and an image cached on the state version survived it)
+    if (rc == MIR_OK && o.kind == STEP_ROTATED_LIST) h->state_version++;
   }
   if (rc != MIR_OK) return rc;
   TSTAMP(0);
@@ -1705,6 +1719,19 @@ int mir_forward(MirHandle h, float* M, float* qfrc_bias, float* qacc_smooth, flo
   Outs o;
   o.mode = 1;
   o.out_M = M; o.out_bias = qfrc_bias; o.out_qas = qacc_smooth; o.out_qacc = qacc;
+  return launch(h, o, stream);
+}
+
+int mir_contact_forces(MirHandle h, int32_t* n_contacts, uint8_t* flags, int32_t* ids, float* pos_normal_pen, float* force, float* link_force,
+                       void* stream) {
+  if (check(h)) return MIR_E_INVALID;
+  if (h->pending) return set_err(MIR_E_INVALID, "mir_contact_forces: a step is pending (mir_step_end first)");
+  if (!n_contacts && !flags && !ids && !pos_normal_pen && !force && !link_force) return MIR_OK;  // (nothing asked for)
+  DeviceGuard guard(h->device);
+  Outs o;
+  o.mode = 1; o.diag = false;  // (forward only; the diagnostics record stays the last step's)
+  o.kind = h->kernel == 16 ? STEP_SENSE48 : STEP_FULL;
+  o.cf_ncon = n_contacts; o.cf_flags = flags; o.cf_ids = ids; o.cf_geom = pos_normal_pen; o.cf_force = force; o.cf_link = link_force;
   return launch(h, o, stream);
 }
 

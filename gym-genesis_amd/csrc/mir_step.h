@@ -83,12 +83,19 @@ enum StepKind : int {
   // STEP_LOOP itself is untouched by either.
   STEP_XR16 = 12,
   STEP_XR48 = 13,
+  // (CPL = 3) CONTACT FORCE SENSING (mir_contact_forces): STEP_HEAVY48's first pass for the whole batch -- 48 points, 16 candidate pairs,
+  // two waves -- FORWARD ONLY: it stops behind the Newton solve, where every lane still holds the four pyramid-row forces of its
+  // contacts, forms the world force of each contact, stores the contact list and reduces the net force per link over the env's row
+  // (StepArgs::cf_*).  No integration, no state / target / warm-start / observation / terminated / host-byte stores, no diagnostics:
+  // a read is invisible to the steps around it.  An env beyond the capacity is not deferred but FLAGGED (bit 0 of its flag byte: the
+  // forces are those of the thinned manifold).  No launch of env.step(), of the rollouts or of bench.py takes this kind.
+  STEP_SENSE48 = 14,
 };
 
 // ---- the table: what each kind is.  Everything that depends on the kind -- launch bounds, occupancy hint, block size and CPL of
 // the launch, the body's compile-time switches, the host's bookkeeping -- asks here.
 // contacts per lane
-constexpr int step_cpl(int k) { return (k == STEP_LIST48 || k == STEP_HEAVY48 || k == STEP_POST48 || k == STEP_PRE48 || k == STEP_XR48) ? 3 : 1; }
+constexpr int step_cpl(int k) { return (k == STEP_LIST48 || k == STEP_HEAVY48 || k == STEP_POST48 || k == STEP_PRE48 || k == STEP_XR48 || k == STEP_SENSE48) ? 3 : 1; }
 // three contacts per lane: the whole step in one pass (two waves, as STEP_SINGLE) ...
 constexpr bool step_big(int k) { return step_cpl(k) > 1; }
 // ... then the outputs, then the action-independent half of the next step
@@ -100,6 +107,9 @@ constexpr bool step_first_pass_only(int k) { return k == STEP_POST48 || k == STE
 // the action-independent half alone (into `pre`); the action-dependent half alone on one wave (from `pre`)
 constexpr bool step_pre_only(int k) { return k == STEP_PRE || k == STEP_PRE48; }
 constexpr bool step_post_only(int k) { return k == STEP_POST; }
+// forward dynamics only, at the stored state with the stored targets: the pass ends behind the Newton solve with the contact-force
+// outputs (StepArgs::cf_*) and stores nothing else
+constexpr bool step_forward_only(int k) { return k == STEP_SENSE48; }
 // the body keeps its step loop (n_steps, rollout rows, autoreset); the others take one step per launch or pass
 constexpr bool step_has_loop(int k) { return k == STEP_LOOP || k == STEP_FULL || k == STEP_XR16; }
 // ... and of those, the ones that hand back packed rows only
@@ -125,14 +135,14 @@ constexpr bool step_defers(int k) { return k == STEP_SINGLE || k == STEP_POST ||
 // serves the envs of StepArgs::env_list where one is given
 constexpr bool step_reads_env_list(int k) { return k == STEP_PRE || k == STEP_ROTATED_LIST || step_big(k); }
 // stores host-visible terminated bytes / takes completion tickets where the launch asks for them
-constexpr bool step_sends_host_bytes(int k) { return k != STEP_LOOP; }
+constexpr bool step_sends_host_bytes(int k) { return k != STEP_LOOP && !step_forward_only(k); }
 // ... and may send the bytes from inside the solver loop, before it has converged (mir_model.h: term_bound_ok)
 constexpr bool step_early_bytes_in_solver(int k) { return k == STEP_SINGLE || k == STEP_ROTATED || k == STEP_POST48 || k == STEP_ROTATED_LIST; }
 // FEAT_SPEC: the instantiation still stores link poses for the rasteriser (the others leave that to the generic-scene one)
 constexpr bool step_spec_stores_poses(int k) { return step_rotated(k) || step_big(k); }
 // ---- what the launch does to the handle's state (launch() in mir_api.hip)
 // advances qpos / qvel (everything but the action-independent half alone)
-constexpr bool step_integrates(int k) { return !step_pre_only(k); }
+constexpr bool step_integrates(int k) { return !step_pre_only(k) && !step_forward_only(k); }
 // leaves `pre` as valid as it was: the first halves (their callers mark it valid), and the list launch, which writes the scratch
 // rows for the state it leaves itself
 constexpr bool step_keeps_pre(int k) { return step_pre_only(k) || k == STEP_LIST48; }
@@ -224,6 +234,14 @@ struct StepArgs {
   int32_t* xr_start;
   unsigned long long* xr_stats;  // STEP_XR48: [0] += env-steps taken (one device atomic per workgroup and pass)
   int xr_step;
+  // CONTACT FORCE SENSING (mir_contact_forces: STEP_SENSE48 alone reads these; at the END of the struct, so that no other field's
+  // kernel-argument offset moved when they came).  All nullable.  Contact rows in the solver's contact order, rows >= n_contacts zeroed.
+  int32_t* cf_ncon;   // (B)
+  uint8_t* cf_flags;  // (B) bit 0: more candidate points / pairs than the kind holds (forces of the thinned manifold)
+  int32_t* cf_ids;    // (B, MIR_MAX_CONTACT, 4): geom_a, geom_b, link_a, link_b
+  float* cf_geom;     // (B, MIR_MAX_CONTACT, 7): position, normal (a -> b), penetration
+  float* cf_force;    // (B, MIR_MAX_CONTACT, 3): world force on link b
+  float* cf_link;     // (B, nbody, 3): per link, sum over its contacts as b minus sum over its contacts as a
 };
 #ifndef XR_TIER2
 #define XR_TIER2 (1 << 20) /* xr_start: the env is on the second list (the wave-per-env kernel); the low bits keep its step */

@@ -31,7 +31,7 @@
 //     read of a launch (tables, per-lane record, model scalars, state, action, cached poses) leaves before the first LDS
 //     store -- one L2 round trip at the start.
 //   * instantiations: one step body serves every kind of launch -- single step, rollout loop, the halves of a split step, the
-//     rotated launch, the three-contacts-per-lane tier of exact contacts; StepKind and its table in mir_step.h name and describe them.
+//     rotated launch, the three-contacts-per-lane tier of exact contacts, the contact-force sensor read; StepKind and its table in mir_step.h name and describe them.
 #include <hip/hip_runtime.h>
 
 #include <type_traits>
@@ -347,6 +347,7 @@ static int launch_feat(const StepArgs& a, int kind, int blocks, hipStream_t stre
     case STEP_SINGLE: return launch_kind<STEP_SINGLE, FEAT>(a, blocks, stream);
     case STEP_LOOP: return launch_kind<STEP_LOOP, FEAT>(a, blocks, stream);
     case STEP_FULL: if constexpr ((FEAT & FEAT_SPEC) == 0) return launch_kind<STEP_FULL, FEAT>(a, blocks, stream); else break;
+    case STEP_SENSE48: if constexpr ((FEAT & FEAT_SPEC) == 0) return launch_kind<STEP_SENSE48, FEAT>(a, blocks, stream); else break;  // (off the hot path: generic sizes)
   }
   return (int)hipErrorInvalidValue;
 }
@@ -355,7 +356,7 @@ extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_convex(cons
   const StepArgs& a = *args;
   const int blocks = (a.B + EPB - 1) / EPB;
   // the headline scene's instantiation (FEAT_SPEC: mir_create found SpecPick::matches); the everything-variant stays generic
-  if ((a.features & FEAT_SPEC) && kind != STEP_FULL) return launch_feat<FEAT_CONVEX | FEAT_SPEC>(a, kind, blocks, stream);
+  if ((a.features & FEAT_SPEC) && kind != STEP_FULL && kind != STEP_SENSE48) return launch_feat<FEAT_CONVEX | FEAT_SPEC>(a, kind, blocks, stream);
   if (a.features & FEAT_SAP) return launch_feat<FEAT_CONVEX | FEAT_SAP>(a, kind, blocks, stream);  // sweep-and-prune scenes carry the convex code too
   return launch_feat<FEAT_CONVEX>(a, kind, blocks, stream);
 }

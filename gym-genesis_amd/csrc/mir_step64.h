@@ -61,6 +61,15 @@ struct StepArgs64 {
   const int32_t* list_count;
   const int32_t* env_start;
   unsigned long long* xr_stats;  // [1] += env-steps taken (list_count mode only)
+  // CONTACT FORCE SENSING (mir_contact_forces; mode 1 of the generic instantiation only -- the other two null them at the top like the
+  // per-stage outputs; at the END of the struct, so that no other field's kernel-argument offset moved).  All nullable; layouts as
+  // StepArgs::cf_* (mir_step.h).
+  int32_t* cf_ncon;
+  uint8_t* cf_flags;
+  int32_t* cf_ids;
+  float* cf_geom;
+  float* cf_force;
+  float* cf_link;
 };
 #ifndef XR_TIER2
 #define XR_TIER2 (1 << 20) /* (mir_step.h) env_start: the env is on the wave kernel's list; the low bits keep its step */

@@ -431,6 +431,7 @@ __global__ __launch_bounds__(VARIANT == STEP_SINGLE ? 128 : 64) __attribute__((a
 void mir_step64_kernel(StepArgs64 a) {
   constexpr bool SINGLE = VARIANT == STEP_SINGLE;
   constexpr bool DUAL = SINGLE;
+  constexpr bool SENSE = VARIANT == STEP_FULL;  // contact force sensing (mir_contact_forces): compiled into the generic instantiation alone
   __shared__ __attribute__((aligned(16))) Env64 S;
   const DevModel64* __restrict__ m = a.model;
   const int lane = threadIdx.x & 63;
@@ -1051,7 +1052,8 @@ void mir_step64_kernel(StepArgs64 a) {
         st3v(&S.con.cref[k][0], ref1); st3v(&S.con.cref[k][4], ref2);
         S.con.cmask[k][0] = (unsigned)dm1; S.con.cmask[k][1] = (unsigned)(dm1 >> 32);
         S.con.cmask[k][2] = (unsigned)dm2; S.con.cmask[k][3] = (unsigned)(dm2 >> 32);
-        S.con.cblk[k][0] = sg0; S.con.cblk[k][1] = sg1; S.con.cblk[k][2] = 0; S.con.cblk[k][3] = 0;
+        // (SENSE: the contact's geoms and links ride in the two pad words, for the contact list and the per-link sums)
+        S.con.cblk[k][0] = sg0; S.con.cblk[k][1] = sg1; S.con.cblk[k][2] = SENSE ? (g1 | g2 << 8) : 0; S.con.cblk[k][3] = SENSE ? (b1 | b2 << 8) : 0;
       }
     }
     WSYNC();  // col scratch is dead from here on
@@ -1198,6 +1200,7 @@ void mir_step64_kernel(StepArgs64 a) {
     a.prof = nullptr;
 #endif
   }
+  if (!SENSE) a.cf_ncon = nullptr, a.cf_flags = nullptr, a.cf_ids = nullptr, a.cf_geom = nullptr, a.cf_force = nullptr, a.cf_link = nullptr;
   if (VARIANT == STEP_LOOP) { a.mode = 0; a.out_M = a.out_bias = a.out_qas = a.out_qacc = a.out_xpos = a.out_xquat = nullptr; a.prof = nullptr; a.agent_pos = a.env_state = a.reward = nullptr; a.terminated = a.term_host = nullptr; }
   // packed output row [agent_pos | env_state | reward | terminated] of the current kinematic state
   const int eb = m->eef_body, ob = m->obj_body, ob2 = m->obj2_body;
@@ -1919,6 +1922,56 @@ void mir_step64_kernel(StepArgs64 a) {
       a.diag[(size_t)env * 4 + 1] = a.prof && a.prof[33] == 77ull ? S.pad1 : ((int)(__builtin_readcyclecounter() - t_entry) | (coupled ? 1 << 30 : 0));
 #endif
       a.diag[(size_t)env * 4 + 3] = ncand | (S.pad0 & 255) << 8;
+    }
+    if constexpr (SENSE) {
+      if (a.mode == 1 && (a.cf_ncon || a.cf_flags || a.cf_ids || a.cf_geom || a.cf_force || a.cf_link)) {
+        // ---- CONTACT FORCE SENSING (mir_contact_forces; the 16-lane kernel's STEP_SENSE48 has the derivation): lane = contact holds
+        // the rows J a - aref of its contact; f_r = -D min(0, jar_r), world force on link b = sum_r f_r (n + s_r mu t), link a takes
+        // the opposite.  All MIR_MAX_CONTACT rows of the env's list are written (zeros behind the last contact).  The per-link sums
+        // go through the base-force rows (dead behind the solve): lane = link walks the contacts in contact order -- one fixed order,
+        // no atomics.  Nothing else is stored for the read.
+        V3 F = v3(0, 0, 0);
+        int ga = 0, gb = 0, la = 0, lb = 0;
+        f4 pd = {0, 0, 0, 0};
+        V3 cn = v3(0, 0, 0);
+        if (iscon) {
+          float f[4];
+#pragma unroll
+          for (int r = 0; r < 4; r++) f[r] = jar[r] < 0.0f ? -cD * jar[r] : 0.0f;
+          cn = ld3v(&S.con.cfrm[lane][0]);
+          const V3 c1 = ld3v(&S.con.cfrm[lane][4]), c2 = ld3v(&S.con.cfrm[lane][8]);
+          F = (f[0] + f[1] + f[2] + f[3]) * cn + (cmu * (f[0] - f[1])) * c1 + (cmu * (f[2] - f[3])) * c2;
+          const int gw = S.con.cblk[lane][2], bw = S.con.cblk[lane][3];
+          ga = gw & 255; gb = gw >> 8 & 255; la = bw & 255; lb = bw >> 8 & 255;
+          pd = ldv(S.con.cpos[lane]);
+        }
+        WSYNC();
+        if (lane < MAXC) {
+          const size_t row = (size_t)env * MAXC + lane;
+          if (a.cf_ids) *reinterpret_cast<int4*>(a.cf_ids + row * 4) = make_int4(ga, gb, la, lb);
+          if (a.cf_geom) {
+            float* gp = a.cf_geom + row * 7;
+            gp[0] = pd.x; gp[1] = pd.y; gp[2] = pd.z; gp[3] = cn.x; gp[4] = cn.y; gp[5] = cn.z; gp[6] = -pd.w;
+          }
+          if (a.cf_force) st3(&a.cf_force[row * 3], F);
+          stv(S.con.cfb[lane], f4{F.x, F.y, F.z, __int_as_float(la | lb << 8)});
+        }
+        WSYNC();
+        if (a.cf_link) {
+          V3 acc = v3(0, 0, 0);
+          for (int c = 0; c < ncon; c++) {
+            const f4 v = ldv(S.con.cfb[c]);
+            const int bw = __float_as_int(v.w);
+            const float sg = ((bw >> 8 & 255) == lane ? 1.0f : 0.0f) - ((bw & 255) == lane ? 1.0f : 0.0f);
+            acc = acc + sg * v3(v.x, v.y, v.z);
+          }
+          if (lane < nb) st3(&a.cf_link[((size_t)env * nb + lane) * 3], acc);
+        }
+        if (lane == 0) {
+          if (a.cf_ncon) a.cf_ncon[env] = ncon;
+          if (a.cf_flags) a.cf_flags[env] = S.pad0 > (max_contacts < MAXC ? max_contacts : MAXC) ? 1 : 0;  // (more candidate points than the kernel holds: thinned)
+        }
+      }
     }
     if (a.mode != 0) break;
 

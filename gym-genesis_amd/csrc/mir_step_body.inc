@@ -7,6 +7,7 @@
   constexpr bool SINGLE = !step_has_loop(VARIANT), DUAL = step_waves(VARIANT) == 2;
   constexpr bool XR = step_exact_rollout(VARIANT);  // (mir_rollout_exact)
   constexpr bool DEFER = step_defers(VARIANT);
+  constexpr bool FWD = step_forward_only(VARIANT);  // (mir_contact_forces: the pass ends behind the Newton solve)
   constexpr int MAXCON = G * CPL;
   static_assert(CPL == step_cpl(VARIANT), "the kind fixes the contacts per lane");
   static_assert(JST == 52 && K16_PRE_STRIDE >= K16_PRE_JB + JST * K16_MAX_CONTACT, "pre-buffer layout");
@@ -625,10 +626,12 @@
     f4 pd[CPL], meta[CPL];
     V3 n[CPL], t1[CPL], t2[CPL], ref1[CPL], ref2[CPL];
     uint32_t dm1[CPL], dm2[CPL], chunks[CPL];
+    [[maybe_unused]] uint32_t cids[CPL];  // (FWD: geom_a | geom_b << 8 | link_a << 16 | link_b << 24, for the contact list and the per-link sums)
 #pragma unroll
     for (int sl = 0; sl < CPL; sl++) {
       const int k = lane + G * sl;
       mine[sl] = k < ncon_new;
+      if constexpr (FWD) cids[sl] = 0u;
       pd[sl] = f4{0, 0, 0, 0}; meta[sl] = f4{0, 0, 0, 0};
       n[sl] = v3(0, 0, 0); t1[sl] = n[sl]; t2[sl] = n[sl]; ref1[sl] = n[sl]; ref2[sl] = n[sl];
       dm1[sl] = 0u; dm2[sl] = 0u; chunks[sl] = 0u;
@@ -648,6 +651,7 @@
         const float sr0 = 0.5f * (s1a.x + s2a.x), sr1 = 0.5f * (s1a.y + s2a.y);
         const float si[5] = {0.5f * (s1a.z + s2a.z), 0.5f * (s1a.w + s2a.w), 0.5f * (s1b.x + s2b.x), 0.5f * (s1b.y + s2b.y), 0.5f * (s1b.z + s2b.z)};
         const int b1 = T.g_info[g1][0], b2 = T.g_info[g2][0];
+        if constexpr (FWD) cids[sl] = (uint32_t)g1 | (uint32_t)g2 << 8 | (uint32_t)b1 << 16 | (uint32_t)b2 << 24;
         const float wsum = T.b_invw[b1] + T.b_invw[b2];
         const float dmax = fminf(fmaxf(si[1], 1e-4f), 0.9999f);
         const float tc = fmaxf(sr0, 2.0f * dt);
@@ -696,7 +700,23 @@
         st3v(&S.con.cfrm[k][0], n[sl]); st3v(&S.con.cfrm[k][4], t1[sl]); st3v(&S.con.cfrm[k][8], t2[sl]);
         stv(S.con.cmeta[k], meta[sl]);
         st3v(&S.con.cref[k][0], ref1[sl]); st3v(&S.con.cref[k][4], ref2[sl]);
-        S.con.cmask[k][0] = dm1[sl]; S.con.cmask[k][1] = dm2[sl]; S.con.cmask[k][2] = chunks[sl]; S.con.cmask[k][3] = 0u;
+        S.con.cmask[k][0] = dm1[sl]; S.con.cmask[k][1] = dm2[sl]; S.con.cmask[k][2] = chunks[sl];
+        if constexpr (FWD) S.con.cmask[k][3] = cids[sl]; else S.con.cmask[k][3] = 0u;
+      }
+      if constexpr (FWD) {
+        // the contact list's geometry leaves from here (this wave has it in registers; the positions' LDS rows become the solver's
+        // base forces): every one of the MIR_MAX_CONTACT rows of the env is written, the ones behind the last contact with zeros
+        static_assert(!FWD || MAXCON == MIR_MAX_CONTACT, "the contact list has MIR_MAX_CONTACT rows");
+        if (valid) {
+          const size_t row = (size_t)env * MAXCON + k;
+          if (a.cf_ids) *reinterpret_cast<int4*>(a.cf_ids + row * 4) = make_int4((int)(cids[sl] & 255u), (int)(cids[sl] >> 8 & 255u), (int)(cids[sl] >> 16 & 255u), (int)(cids[sl] >> 24));
+          if (a.cf_geom) {
+            float* gp = a.cf_geom + row * 7;
+            gp[0] = pd[sl].x; gp[1] = pd[sl].y; gp[2] = pd[sl].z;
+            gp[3] = n[sl].x; gp[4] = n[sl].y; gp[5] = n[sl].z;
+            gp[6] = -pd[sl].w;
+          }
+        }
       }
     }
   }
@@ -1009,6 +1029,7 @@
     HSTAMP(47);
     __syncthreads();  // (4) all-rows-active Hessian handed to the main wave
     helper_newton();
+    if (FWD) return;  // (forward only: nothing is integrated, no closing FK)
     if (fksplit) {
       // the closing forward kinematics of the jointed bodies, beside the main wave's quaternion integration of the free bodies
       // and its state stores (the four quads of lane constants are fetched again: nothing of the opening FK was kept in registers)
@@ -2057,6 +2078,47 @@
     }
     if (DUAL && (!post_now || ROT) && !met4) __syncthreads();  // (4) (no Hessian was needed: the collision wave is let go)
     if constexpr (CPL > 1) { if (tid == 0) __hip_atomic_store(&s_help[0], -1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }  // (the helper wave leaves the Newton loop)
+    if constexpr (FWD) {
+      // ---- CONTACT FORCE SENSING (mir_contact_forces): the solve is over and every lane holds the rows J a - aref of its contacts.  The
+      // solver's force of pyramid row r is f_r = -D min(0, jar_r); the rows of a contact are n + mu t1, n - mu t1, n + mu t2, n - mu t2
+      // of the motion of link b relative to link a, so the world force on link b is sum_r f_r (n + s_r mu t) -- the base-force triple
+      // of the gradient loop on the contact frame -- and link a takes the opposite.  The per-link sums go through LDS (the contacts'
+      // reference points are dead since the Jacobian build): lane = link walks the env's contacts in contact order, so the sum has one
+      // fixed order and needs no atomics (one workgroup owns the env's links).  Nothing else is stored: the read is invisible.
+      WSYNC();
+#pragma unroll
+      for (int sl = 0; sl < CPL; sl++) {
+        const int k = lane + G * sl;
+        V3 F = v3(0, 0, 0);
+        uint32_t ids = 0u;
+        if (iscon[sl]) {
+          float f[4];
+#pragma unroll
+          for (int r = 0; r < 4; r++) f[r] = jar[sl][r] < 0.0f ? -cD[sl] * jar[sl][r] : 0.0f;
+          const V3 cn = ld3v(&S.con.cfrm[k][0]), c1 = ld3v(&S.con.cfrm[k][4]), c2 = ld3v(&S.con.cfrm[k][8]);
+          F = (f[0] + f[1] + f[2] + f[3]) * cn + (cmu[sl] * (f[0] - f[1])) * c1 + (cmu[sl] * (f[2] - f[3])) * c2;
+          ids = S.con.cmask[k][3];
+        }
+        if (valid && a.cf_force) st3(&a.cf_force[((size_t)env * MAXCON + k) * 3], F);
+        stv(&S.con.cref[k][0], f4{F.x, F.y, F.z, __uint_as_float(ids)});
+      }
+      WSYNC();
+      if (a.cf_link) {
+        V3 acc = v3(0, 0, 0);
+        for (int c = 0; c < ncon; c++) {
+          const f4 v = ldv(&S.con.cref[c][0]);
+          const uint32_t ids = __float_as_uint(v.w);
+          const float sg = ((int)(ids >> 24) == lane ? 1.0f : 0.0f) - ((int)(ids >> 16 & 255u) == lane ? 1.0f : 0.0f);
+          acc = acc + sg * v3(v.x, v.y, v.z);
+        }
+        if (valid && lane < nb) st3(&a.cf_link[((size_t)env * nb + lane) * 3], acc);
+      }
+      if (valid && lane == 0) {
+        if (a.cf_ncon) a.cf_ncon[env] = ncon;
+        if (a.cf_flags) a.cf_flags[env] = ovf_env ? 1 : 0;  // (more candidate points than MIR_MAX_CONTACT, or more candidate pairs than lanes)
+      }
+      return 2;
+    }
     if (a.out_qacc && valid && isdof && step == 0) a.out_qacc[(size_t)env * nv + lane] = qacc;
     if (a.diag && valid && !ovf_env && lane == 0) {
       a.diag[(size_t)env * 4 + 0] = ncon;

@@ -88,6 +88,8 @@ def load_library() -> C.CDLL:
     lib.mir_set_diag.argtypes = [vp, i32]
     lib.mir_set_diag.restype = C.c_int
     lib.mir_forward.argtypes = [vp, vp, vp, vp, vp, vp]
+    lib.mir_contact_forces.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_contact_forces.restype = C.c_int
     lib.mir_debug_render_path.argtypes = [vp, i32, i32]
     lib.mir_debug_render_path.restype = C.c_int
     lib.mir_debug_spec_active.argtypes = [vp]
@@ -322,6 +324,8 @@ class MirScene(StepHelpers):
         self._go, self._devidx = self.lib.mir_step_go, self.device.index  # (looked up once: they sit in front of every API launch)
         self.nu = sum(1 for i in range(spec.ndof) if spec.dof[i].ctrl_mode == 1)
         self.n_arm = sum(1 for b in range(1, spec.nbody) if spec.body[b].jtype in (1, 2))
+        # contact force sensing (contact_forces / contact_sensor): launches so far, the cached read and the counter of PD-target writes
+        self.contact_force_launches, self._contact_sensor, self._targets_version = 0, None, 0
 
     # -- helpers -----------------------------------------------------------------------------
     def _check(self, rc: int) -> None:
@@ -420,6 +424,7 @@ class MirScene(StepHelpers):
 
     def set_pd_targets(self, tgt) -> None:
         t = self._f32(tgt, self.nu)
+        self._targets_version += 1  # (the PD targets enter the contact forces: contact_sensor())
         self._check(self.lib.mir_set_pd_targets(self.h, _ptr(t), self._stream()))
 
     def step(self, n_steps: int = 1) -> None:
@@ -606,6 +611,39 @@ class MirScene(StepHelpers):
         qas, qacc = self.empty(self.nv), self.empty(self.nv)
         self._check(self.lib.mir_forward(self.h, _ptr(M), _ptr(bias), _ptr(qas), _ptr(qacc), self._stream()))
         return M, bias, qas, qacc
+
+    MAX_CONTACT = 48  # MIR_MAX_CONTACT: rows of the contact list
+
+    def contact_forces(self, contacts: bool = True, link_force: bool = True) -> dict:
+        """mir_contact_forces: ONE forward-dynamics evaluation at the current state with the current PD targets -- the contact forces
+        the next step applies if the targets stay as they are (Genesis reports those of the step just taken) -- that changes nothing a
+        later call can see.  Fresh device tensors on the current stream: n_contacts (B,) int32, flags (B,) uint8 (bit 0: more candidate
+        points than the kernel holds, forces of the thinned manifold), and with `contacts` the list in the solver's contact order,
+        rows >= n_contacts zeroed -- ids (B,48,4) int32 [geom_a, geom_b, link_a, link_b], pos_normal_pen (B,48,7) [position, normal
+        a -> b, penetration], force (B,48,3) on link b (link a gets the opposite) -- and with `link_force` the net contact force per
+        link (B,nbody,3), the world included.  The tensors are allocated per call, not reused: contact_sensor() hands a read out to
+        several callers, and a reused buffer would change under them."""
+        out = {"n_contacts": self.empty(dtype=torch.int32), "flags": self.empty(dtype=torch.uint8)}
+        if contacts:
+            out["ids"] = self.empty(self.MAX_CONTACT, 4, dtype=torch.int32)
+            out["pos_normal_pen"] = self.empty(self.MAX_CONTACT, 7)
+            out["force"] = self.empty(self.MAX_CONTACT, 3)
+        if link_force:
+            out["link_force"] = self.empty(self.nbody, 3)
+        self._check(self.lib.mir_contact_forces(self.h, _ptr(out["n_contacts"]), _ptr(out["flags"]), _ptr(out.get("ids")), _ptr(out.get("pos_normal_pen")),
+                                                _ptr(out.get("force")), _ptr(out.get("link_force")), self._stream()))
+        self.contact_force_launches += 1
+        return out
+
+    def contact_sensor(self) -> dict:
+        """contact_forces() of the current state, shared: one launch serves every getter of every entity view until the state moves
+        (mir_get_state_version: steps, resets, state writes) or the PD targets are set (set_pd_targets).  The tensors are handed out as
+        they are: treat them as read-only."""
+        key = (self.state_version, self._targets_version)
+        last = self._contact_sensor
+        if last is None or last[0] != key:
+            last = self._contact_sensor = (key, self.contact_forces())
+        return last[1]
 
     def render(self, cam: MirCameraSpec, vis: MirVisualSpec, mode: int = 0, env_offset: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:

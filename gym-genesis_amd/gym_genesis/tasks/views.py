@@ -58,6 +58,62 @@ class EntityView:
         self._qcols = list(self.dof_idx)
         ctrl = [i for i, d in enumerate(builder.dofs) if d["ctrl_mode"] == 1]
         self._ucols = [ctrl.index(i) for i in self.dof_idx if i in ctrl]
+        # the links of this entity: its root and everything below it, in body order
+        self.link_idx = [self.root]
+        for i, b in enumerate(builder.bodies):
+            if i > self.root and b["parent"] in self.link_idx:
+                self.link_idx.append(i)
+
+    @property
+    def n_links(self) -> int:
+        return len(self.link_idx)
+
+    # ---- contact force sensing (Genesis: RigidEntity.get_links_net_contact_force / get_contacts).  The forces are those of a forward
+    # evaluation at the CURRENT state with the CURRENT PD targets -- what the next scene.step() applies if the targets stay -- where
+    # Genesis reports the forces of the step just taken.  One launch per state serves every getter of every entity (MirScene.contact_sensor).
+    def _sensor(self) -> dict:
+        sensor = getattr(self._mir, "contact_sensor", None)
+        if sensor is None:
+            raise NotImplementedError("this scene has no contact force sensing (MirScene.contact_sensor / mir_contact_forces)")
+        return sensor()
+
+    def _links_t(self, device) -> torch.Tensor:
+        ix = self.__dict__.get("_link_idx_t")
+        if ix is None or ix.device != device:
+            ix = self._link_idx_t = torch.as_tensor(self.link_idx, dtype=torch.long, device=device)
+        return ix
+
+    def get_links_net_contact_force(self, envs_idx=None) -> torch.Tensor:
+        """(B, n_links, 3) float32, device: the net contact force on each link of this entity, world frame."""
+        lf = self._sensor()["link_force"]
+        return _rows(lf.index_select(1, self._links_t(lf.device)), envs_idx)
+
+    def get_contacts(self, with_entity=None, envs_idx=None) -> dict:
+        """The contacts that involve this entity (and `with_entity`, when given), padded to 48 rows per env in the solver's contact
+        order: geom_a, geom_b, link_a, link_b (B,48) int32 (-1 in the rows that are not valid), position, force_a, force_b (B,48,3),
+        penetration (B,48), valid_mask (B,48) bool.  force_b is the force on link_b, force_a = -force_b the one on link_a."""
+        s = self._sensor()
+        ids, gp, force = s["ids"], s["pos_normal_pen"], s["force"]
+        B, K = ids.shape[0], ids.shape[1]
+        valid = torch.arange(K, device=ids.device)[None, :] < s["n_contacts"][:, None]
+
+        def touches(ent):
+            lk = ent._links_t(ids.device)
+            return (ids[:, :, 2, None] == lk).any(-1), (ids[:, :, 3, None] == lk).any(-1)
+
+        a_me, b_me = touches(self)
+        mask = valid & (a_me | b_me)
+        if with_entity is not None:
+            a_ot, b_ot = touches(with_entity)
+            mask = valid & ((a_me & b_ot) | (b_me & a_ot))
+        neg = torch.full_like(ids[:, :, 0], -1)
+        fb = torch.where(mask[:, :, None], force, torch.zeros_like(force))
+        out = {"geom_a": torch.where(mask, ids[:, :, 0], neg), "geom_b": torch.where(mask, ids[:, :, 1], neg),
+               "link_a": torch.where(mask, ids[:, :, 2], neg), "link_b": torch.where(mask, ids[:, :, 3], neg),
+               "position": torch.where(mask[:, :, None], gp[:, :, 0:3], torch.zeros_like(force)),
+               "force_a": -fb, "force_b": fb,
+               "penetration": torch.where(mask, gp[:, :, 6], torch.zeros_like(gp[:, :, 6])), "valid_mask": mask}
+        return {k: _rows(v, envs_idx) for k, v in out.items()}
 
     @property
     def n_dofs(self) -> int:

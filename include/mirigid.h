@@ -414,6 +414,31 @@ int mir_get_bad(MirHandle h, uint8_t* bad, uint32_t* env_steps, int32_t reset, v
  * qacc_smooth (B,nv), qacc (B,nv); nullable */
 int mir_forward(MirHandle h, float* M, float* qfrc_bias, float* qacc_smooth, float* qacc, void* stream);
 
+/* ---- contact force sensing -----------------------------------------------------------------------
+ * entity.get_links_net_contact_force() / entity.get_contacts() of Genesis (RigidEntity; the reference's tasks do not call them --
+ * gym_genesis/tasks/franka/cube_pick.py:140-163 reads poses only -- but they are what its users reach for next: grasp detection,
+ * force rewards, tactile observations).
+ * One forward-dynamics evaluation AT THE CURRENT STATE WITH THE CURRENT PD TARGETS (as mir_forward: poses, dynamics, collision,
+ * constraint rows, Newton solve, no integration): the contact forces that the next step applies if the targets stay as they are.
+ * (Genesis and MuJoCo report the forces of the step just taken, i.e. of the state BEFORE the last step.)
+ * The read changes nothing a later call can see: state, targets, warm start, episode bookkeeping, the state version, link poses,
+ * diagnostics and all counters stay as they were, and the steps around it are bit for bit those of a run without it.
+ *   n_contacts (B) i32; flags (B) u8 -- bit 0: the narrowphase found more candidate points (or pairs) than the serving kernel holds
+ *     (MIR_MAX_CONTACT points; 16 candidate pairs on the 16-lane kernel), the forces are those of the thinned manifold;
+ *   ids (B, MIR_MAX_CONTACT, 4) i32: geom_a, geom_b, link_a, link_b (indices of the spec), in the solver's contact order; the
+ *     pointer must be 16-byte aligned (a row is one vector store);
+ *   pos_normal_pen (B, MIR_MAX_CONTACT, 7): position (world), normal (world, from a to b), penetration depth (> 0 = overlap);
+ *   force (B, MIR_MAX_CONTACT, 3): world force ON LINK b (link a receives the opposite), sum over the contact's four friction-pyramid
+ *     rows of f_r (n + s_r mu t), f_r = -D min(0, J_r a - aref_r);
+ *   link_force (B, nbody, 3): per link the sum of `force` over its contacts as b minus the sum over its contacts as a (the world,
+ *     link 0, included: the links of an env sum to zero).  Joint-limit rows contribute to neither output.
+ * Rows >= n_contacts of the three lists are zeroed.  Every output is nullable, each is written only when asked for (link_force alone
+ * costs no list traffic).  Scenes on the 16-lane kernel are served by a launch of their own with 48 points per env whatever the
+ * scene's max_contacts (every point a step with exact contacts keeps); scenes on the wave-per-env kernel by its forward mode.
+ * MIR_E_INVALID while a mir_step_begin is open.  (An added entry point: MIR_VERSION and every struct stay as they are.) */
+int mir_contact_forces(MirHandle h, int32_t* n_contacts, uint8_t* flags, int32_t* ids, float* pos_normal_pen, float* force,
+                       float* link_force, void* stream);
+
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
