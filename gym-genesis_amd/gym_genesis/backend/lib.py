@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirSceneSpec, MirVisualSpec
+from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirKinQuery, MirSceneSpec, MirVisualSpec, make_kin_query
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -125,12 +125,17 @@ def load_library() -> C.CDLL:
     lib.mir_inverse_kinematics.restype = C.c_int
     lib.mir_inverse_kinematics_rows.argtypes = [vp, i32, C.POINTER(MirIkRows), vp, vp, vp, C.POINTER(MirIkOptions), vp, vp, vp]
     lib.mir_inverse_kinematics_rows.restype = C.c_int
+    lib.mir_kin_query_sizeof.restype = C.c_int
+    lib.mir_link_kinematics.argtypes = [vp, C.POINTER(MirKinQuery), vp, i32, vp, vp, vp, vp, vp]
+    lib.mir_link_kinematics.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
         getattr(lib, name).restype = C.c_int
     if lib.mir_spec_sizeof() != C.sizeof(MirSceneSpec) or lib.mir_version() != MIR_VERSION or lib.mir_visual_sizeof() != C.sizeof(MirVisualSpec):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec (rebuild the library)")
+    if lib.mir_kin_query_sizeof() != C.sizeof(MirKinQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirKinQuery (rebuild the library)")
     _lib = lib
     _bind_fast(lib)
     return lib
@@ -644,6 +649,35 @@ class MirScene(StepHelpers):
         if last is None or last[0] != key:
             last = self._contact_sensor = (key, self.contact_forces())
         return last[1]
+
+    def link_kinematics(self, links, local_points=None, env_idx=None, dof0: int = 0, n_dofs: Optional[int] = None, pos: bool = True,
+                        quat: bool = True, vel: bool = True, jac: bool = True) -> dict:
+        """mir_link_kinematics: poses, velocities and geometric Jacobians of the links `links` (body indices of the spec, repeats allowed)
+        in ONE launch of a kernel of its own, for the envs `env_idx` (int64 device tensor, any order, repeats allowed; None: all envs).
+        With p = the link's origin + R_link local_point (local_points (3,) or (n_links, 3); None: the origins), R rows and L links:
+        pos (R,L,3) = p, quat (R,L,4) wxyz, vel (R,L,6) = world linear velocity of p and world angular velocity of the link,
+        jac (R,L,6,n_dofs) = the columns of the scene dofs [dof0, dof0 + n_dofs) (n_dofs None: up to nv) of the map qvel -> vel.
+        Only the outputs asked for are computed and returned: fresh device tensors on the current stream.  The read changes nothing."""
+        nd = self.nv - int(dof0) if n_dofs is None else int(n_dofs)
+        q = make_kin_query(links, local_points, dof0, nd)
+        idx = None
+        if env_idx is not None:
+            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        R, L = (self.num_envs if idx is None else int(idx.numel())), q.n_links
+        new = lambda *shape: torch.empty((R, L, *shape), dtype=torch.float32, device=self.device)  # noqa: E731
+        out = {}
+        if pos:
+            out["pos"] = new(3)
+        if quat:
+            out["quat"] = new(4)
+        if vel:
+            out["vel"] = new(6)
+        if jac:
+            out["jac"] = new(6, max(nd, 0))
+        self._check(self.lib.mir_link_kinematics(self.h, C.byref(q), _ptr(idx), R, _ptr(out.get("pos")), _ptr(out.get("quat")), _ptr(out.get("vel")),
+                                                 _ptr(out.get("jac")), self._stream()))
+        self.link_kinematics_launches = self.__dict__.get("link_kinematics_launches", 0) + 1
+        return out
 
     def render(self, cam: MirCameraSpec, vis: MirVisualSpec, mode: int = 0, env_offset: Optional[torch.Tensor] = None,
                out: Optional[torch.Tensor] = None) -> torch.Tensor:

@@ -197,6 +197,40 @@ class MirIkRows(C.Structure):
 
 IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, IK_INIT_BY_ENV = 1, 2, 4, 8
 
+
+class MirKinQuery(C.Structure):
+    """include/mirigid.h: MirKinQuery (mir_link_kinematics)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_links", C.c_int32),
+        ("link_body", C.c_int32 * MIR_MAX_BODY),
+        ("local_point", (C.c_float * 3) * MIR_MAX_BODY),
+        ("dof0", C.c_int32),
+        ("n_dofs", C.c_int32),
+    ]
+
+
+def make_kin_query(links: Sequence[int], local_points=None, dof0: int = 0, n_dofs: int = 0) -> MirKinQuery:
+    """links: body indices of the spec; local_points: one point (3,) for every link, or one per link (n_links, 3); None = the origins."""
+    q = MirKinQuery()
+    q.struct_size = C.sizeof(MirKinQuery)
+    links = [int(b) for b in links]
+    if not 1 <= len(links) <= MIR_MAX_BODY:
+        raise ValueError(f"link_kinematics takes 1 .. {MIR_MAX_BODY} links, got {len(links)}")
+    q.n_links = len(links)
+    q.link_body[:len(links)] = links
+    if local_points is not None:
+        pts = local_points.tolist() if hasattr(local_points, "tolist") else list(local_points)
+        if pts and not isinstance(pts[0], (list, tuple)):
+            pts = [pts] * len(links)
+        pts = [[float(v) for v in p] for p in pts]
+        if len(pts) != len(links) or any(len(p) != 3 for p in pts):
+            raise ValueError("local_points must be (3,) or (n_links, 3)")
+        for i, p in enumerate(pts):
+            q.local_point[i][:] = p
+    q.dof0, q.n_dofs = int(dof0), int(n_dofs)
+    return q
+
 IK_DEFAULTS = dict(max_iters=20, respect_joint_limit=1, damping=0.05, pos_tol=5e-4, rot_tol=5e-3, max_step=0.5)
 
 RENDER_PER_ENV, RENDER_GLOBAL = 0, 1

@@ -35,9 +35,48 @@ CHECK_IK_IDX = False
 from ..backend.spec import IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE  # noqa: E402
 
 
+def _env_index(mir, envs_idx):
+    """`envs_idx` of a getter as the row list of MirScene.link_kinematics: None for all envs in order (also the experts' arange(B)), else
+    an int64 tensor.  Indices given on the host are checked here (IndexError); a device tensor is not read back -- the kernel clamps it."""
+    if envs_idx is None:
+        return None
+    B = mir.num_envs
+    if isinstance(envs_idx, slice):
+        envs_idx = np.arange(B)[envs_idx]
+    if isinstance(envs_idx, torch.Tensor) and envs_idx.is_cuda:
+        return envs_idx.long().reshape(-1)
+    host = np.asarray(envs_idx.cpu() if isinstance(envs_idx, torch.Tensor) else envs_idx).reshape(-1)
+    if host.size and not np.issubdtype(host.dtype, np.integer):
+        raise IndexError(f"envs_idx must be integers, got {host.dtype}")
+    host = host.astype(np.int64)
+    if host.size and (host.min() < -B or host.max() >= B):
+        raise IndexError(f"envs_idx outside the batch of {B} envs")
+    host = np.where(host < 0, host + B, host)
+    if host.size == B and np.array_equal(host, np.arange(B)):
+        return None
+    return torch.as_tensor(host, device=mir.device)
+
+
+def _kinematics(mir, **kw) -> dict:
+    fn = getattr(mir, "link_kinematics", None)
+    if fn is None:
+        raise NotImplementedError("this scene has no link kinematics (MirScene.link_kinematics / mir_link_kinematics)")
+    return fn(**kw)
+
+
 class LinkView:
     def __init__(self, mir, body_index: int, name: str):
         self._mir, self.idx, self.name = mir, body_index, name
+
+    def get_vel(self, envs_idx=None) -> torch.Tensor:
+        """(B, 3): world linear velocity of the link's origin (Genesis: RigidLink.get_vel)."""
+        k = _kinematics(self._mir, links=[self.idx], env_idx=_env_index(self._mir, envs_idx), pos=False, quat=False, jac=False)
+        return k["vel"][:, 0, 0:3].contiguous()
+
+    def get_ang(self, envs_idx=None) -> torch.Tensor:
+        """(B, 3): world angular velocity of the link (Genesis: RigidLink.get_ang)."""
+        k = _kinematics(self._mir, links=[self.idx], env_idx=_env_index(self._mir, envs_idx), pos=False, quat=False, jac=False)
+        return k["vel"][:, 0, 3:6].contiguous()
 
     def get_pos(self, envs_idx=None) -> torch.Tensor:
         return _rows(self._mir.get_links()[0][:, self.idx, :].contiguous(), envs_idx)
@@ -118,6 +157,77 @@ class EntityView:
     @property
     def n_dofs(self) -> int:
         return len(self.dof_idx)
+
+    # ---- differential kinematics (Genesis: RigidEntity.get_jacobian / get_links_pos / get_links_quat / get_links_vel / get_links_ang).
+    # One launch of mir_link_kinematics per call, for the links and envs asked for only; links_kinematics() returns several of the
+    # get_links_* results from ONE launch.
+    def _jac_dofs(self) -> list:
+        """The scene dofs behind the Jacobian's columns, in this entity's dof order: its named dofs (the Panda's nine), or -- an entity
+        built without dof names, a free cube -- the dofs of its links in body order (the cube's six)."""
+        cols = self.__dict__.get("_jac_cols")
+        if cols is None:
+            cols = list(self.dof_idx)
+            if not cols:
+                first, nd = 0, {0: 0, 1: 1, 2: 1, 3: 6}
+                for i, b in enumerate(self._b.bodies):
+                    n = nd[b["jtype"]] if i > 0 else 0
+                    if i in self.link_idx:
+                        cols.extend(range(first, first + n))
+                    first += n
+            self._jac_cols = cols
+        return cols
+
+    def _link_body(self, link) -> int:
+        """a LinkView of this entity, or a local link index -> body index of the scene"""
+        if isinstance(link, LinkView):
+            if link.idx not in self.link_idx:
+                raise ValueError(f"link {link.name!r} does not belong to this entity")
+            return link.idx
+        i = int(link)
+        if not -self.n_links <= i < self.n_links:
+            raise IndexError(f"local link index {i} outside the entity's {self.n_links} links")
+        return self.link_idx[i]
+
+    def _link_bodies(self, links_idx_local) -> list:
+        if links_idx_local is None:
+            return list(self.link_idx)
+        return [self._link_body(i) for i in np.asarray(links_idx_local).reshape(-1).tolist()]
+
+    def get_jacobian(self, link, local_point=None, envs_idx=None) -> torch.Tensor:
+        """``robot.get_jacobian(link)`` -> (B, 6, n): rows 0-2 map this entity's dof velocities to the world linear velocity of the link's
+        origin (of `local_point`, given in the link's frame), rows 3-5 to the link's world angular velocity; the columns are the entity's
+        own dofs in its dof order (9 for the Panda, 6 for a free cube)."""
+        cols = self._jac_dofs()
+        run = bool(cols) and cols == list(range(cols[0], cols[0] + len(cols)))
+        kw = dict(dof0=cols[0], n_dofs=len(cols)) if run else {}
+        k = _kinematics(self._mir, links=[self._link_body(link)], local_points=None if local_point is None else [float(v) for v in np.asarray(local_point).reshape(3)],
+                        env_idx=_env_index(self._mir, envs_idx), pos=False, quat=False, vel=False, **kw)
+        jac = k["jac"][:, 0]
+        if not run:
+            jac = jac.index_select(2, torch.as_tensor(cols, dtype=torch.long, device=jac.device))
+        return jac.contiguous()
+
+    def links_kinematics(self, links_idx_local=None, envs_idx=None, pos=True, quat=True, vel=True) -> dict:
+        """pos (B,n,3), quat (B,n,4), vel (B,n,3), ang (B,n,3) of this entity's links (all, or the local indices given) from ONE launch."""
+        k = _kinematics(self._mir, links=self._link_bodies(links_idx_local), env_idx=_env_index(self._mir, envs_idx), pos=pos, quat=quat, vel=vel, jac=False)
+        out = {n: k[n] for n in ("pos", "quat") if n in k}
+        if "vel" in k:
+            out["vel"], out["ang"] = k["vel"][:, :, 0:3].contiguous(), k["vel"][:, :, 3:6].contiguous()
+        return out
+
+    def get_links_pos(self, links_idx_local=None, envs_idx=None) -> torch.Tensor:
+        return self.links_kinematics(links_idx_local, envs_idx, quat=False, vel=False)["pos"]
+
+    def get_links_quat(self, links_idx_local=None, envs_idx=None) -> torch.Tensor:
+        return self.links_kinematics(links_idx_local, envs_idx, pos=False, vel=False)["quat"]
+
+    def get_links_vel(self, links_idx_local=None, envs_idx=None) -> torch.Tensor:
+        """(B, n_links, 3): world linear velocity of each link's origin"""
+        return self.links_kinematics(links_idx_local, envs_idx, pos=False, quat=False)["vel"]
+
+    def get_links_ang(self, links_idx_local=None, envs_idx=None) -> torch.Tensor:
+        """(B, n_links, 3): world angular velocity of each link"""
+        return self.links_kinematics(links_idx_local, envs_idx, pos=False, quat=False)["ang"]
 
     def get_link(self, name: str) -> LinkView:
         return LinkView(self._mir, self._b.body_index(name), name)

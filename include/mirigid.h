@@ -439,6 +439,48 @@ int mir_forward(MirHandle h, float* M, float* qfrc_bias, float* qacc_smooth, flo
 int mir_contact_forces(MirHandle h, int32_t* n_contacts, uint8_t* flags, int32_t* ids, float* pos_normal_pen, float* force,
                        float* link_force, void* stream);
 
+/* ---- link poses, velocities and Jacobians -----------------------------------------------------------
+ * robot.get_jacobian(link) / entity.get_links_pos / get_links_quat / get_links_vel / get_links_ang / link.get_vel() / link.get_ang()
+ * of Genesis (RigidEntity, RigidLink; the reference's tasks read poses only -- gym_genesis/tasks/franka/cube_pick.py:140-146 -- but
+ * these are what operational-space, resolved-rate and impedance controllers and velocity observations are written on).
+ * ONE launch of a kernel of its own for a LIST of links of a LIST of envs: it reads qpos / qvel and the compiled model and writes only
+ * its outputs (mir_get_links, the other way to a link pose, runs the step kernel over every body of every env).
+ *   R = n_rows, or num_envs when env_idx is NULL; row k belongs to env env_idx[k] (int64, device; repeats and any order allowed; an
+ *   index outside the batch is clamped as in mir_inverse_kinematics_rows).  L = q->n_links.
+ * Definitions (the oracle's conventions: oracle/orc_rigid.c orc_fk for the poses; MIR_JNT_FREE above for the free joint -- qvel = world
+ * linear velocity of the body origin, then world angular velocity; the integrator's q <- exp(w dt) (x) q).  With o_b, R_b the world pose
+ * of body b from the forward kinematics of the current qpos, and p = o_link + R_link local_point:
+ *   pos  (R, L, 3) = p;   quat (R, L, 4) = the link's world quaternion (wxyz), normalised, with the sign the forward kinematics gives it;
+ *   jac  (R, L, 6, n_dofs) row-major: rows 0-2 map qvel to the world linear velocity of p, rows 3-5 to the link's world angular
+ *        velocity; its columns are the scene dofs [dof0, dof0 + n_dofs).  The column of scene dof d, which belongs to body b:
+ *            b on the path world -> link, revolute with world axis a = R_b axis:   [a x (p - o_b); a]
+ *            b on the path, prismatic:                                             [a; 0]
+ *            b on the path, free, linear dof k:                                    [e_k; 0]
+ *            b on the path, free, angular dof k:                                   [e_k x (p - o_b); e_k]
+ *            b not on the path:                                                    zeros (written, not left as they were)
+ *   vel  (R, L, 6) = J_full qvel over ALL scene dofs on the path: world linear velocity of p, then world angular velocity of the link.
+ *        It does not depend on dof0 / n_dofs.
+ * Every output is nullable and written only when asked for; all four NULL, or R == 0, or an empty result: MIR_OK without a launch.
+ * jac should be 16-byte aligned (a block then leaves as 16-byte stores; any 4-byte aligned address works).
+ * A read changes nothing: state, targets, warm start, state version, pose cache, diagnostics, counters and the scratch row of a split
+ * step stay as they are, and the steps around it are bit for bit those of a run without it.  Between two steps of any stepping path
+ * the poses are those of the state mir_get_links sees at that moment.
+ * MIR_E_INVALID: a NULL handle or query, struct_size != sizeof(MirKinQuery), n_links outside 1 .. MIR_MAX_BODY, a link outside
+ * 1 .. nbody - 1, columns outside [0, nv], a call while a mir_step_begin is open (the state is between the two halves of a step: the
+ * rule of mir_contact_forces).  MIR_E_CAPACITY: a path world -> link of more than 16 bodies (the limit of mir_inverse_kinematics).
+ * None of them launches anything.  (An added struct and entry point: MIR_VERSION and every other struct stay as they are.) */
+typedef struct MirKinQuery {
+  int32_t struct_size;                  /* = sizeof(MirKinQuery) */
+  int32_t n_links;                      /* 1 .. MIR_MAX_BODY */
+  int32_t link_body[MIR_MAX_BODY];      /* body indices of the spec, 1 .. nbody-1, repeats allowed */
+  float local_point[MIR_MAX_BODY][3];   /* per queried link: point in the link's frame (0 = link origin) */
+  int32_t dof0, n_dofs;                 /* Jacobian columns = scene dofs [dof0, dof0 + n_dofs) */
+} MirKinQuery;
+int mir_kin_query_sizeof(void);
+int mir_link_kinematics(MirHandle h, const MirKinQuery* q, const int64_t* env_idx /* device, nullable */, int32_t n_rows,
+                        float* pos /* (R, L, 3) */, float* quat /* (R, L, 4) wxyz */, float* vel /* (R, L, 6) lin, ang */,
+                        float* jac /* (R, L, 6, n_dofs) */, void* stream);
+
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
