@@ -510,6 +510,7 @@ int mir_destroy(MirHandle h) {
   if (h->pre) (void)hipFree(h->pre);
   if (h->pre_big) (void)hipFree(h->pre_big);
   if (h->xr_stats) (void)hipFree(h->xr_stats);
+  if (h->ray_tab) (void)hipFree(h->ray_tab);
   if (h->main_event) (void)hipEventDestroy((hipEvent_t)h->main_event);
   if (h->light_event) (void)hipEventDestroy((hipEvent_t)h->light_event);
   if (h->next_host) (void)hipHostFree(h->next_host);

@@ -122,6 +122,9 @@ struct MirScene {
   int32_t* xr_count;
   int32_t *xr_list, *xr_list2, *xr_start;
   unsigned long long xr_calls;  // calls that went the device-resident way (host counter)
+  // RANGE SENSING (mir_raycast, mir_ray.hip): the geometry table with the hulls' face planes, built by the first call
+  void* ray_tab;            // device
+  int ray_state;            // 0 not built yet, 1 built, -1 the scene has a hull without volume (every call fails)
 };
 
 // library-internal helpers implemented in mir_api.hip

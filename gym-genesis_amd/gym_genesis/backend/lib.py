@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirKinQuery, MirSceneSpec, MirVisualSpec, make_kin_query
+from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirKinQuery, MirRayQuery, MirSceneSpec, MirVisualSpec, make_kin_query, make_ray_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -128,6 +128,9 @@ def load_library() -> C.CDLL:
     lib.mir_kin_query_sizeof.restype = C.c_int
     lib.mir_link_kinematics.argtypes = [vp, C.POINTER(MirKinQuery), vp, i32, vp, vp, vp, vp, vp]
     lib.mir_link_kinematics.restype = C.c_int
+    lib.mir_ray_query_sizeof.restype = C.c_int
+    lib.mir_raycast.argtypes = [vp, C.POINTER(MirRayQuery), vp, vp, i32, vp, vp, vp, vp, vp]
+    lib.mir_raycast.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
@@ -136,6 +139,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec (rebuild the library)")
     if lib.mir_kin_query_sizeof() != C.sizeof(MirKinQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirKinQuery (rebuild the library)")
+    if lib.mir_ray_query_sizeof() != C.sizeof(MirRayQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRayQuery (rebuild the library)")
     _lib = lib
     _bind_fast(lib)
     return lib
@@ -677,6 +682,42 @@ class MirScene(StepHelpers):
         self._check(self.lib.mir_link_kinematics(self.h, C.byref(q), _ptr(idx), R, _ptr(out.get("pos")), _ptr(out.get("quat")), _ptr(out.get("vel")),
                                                  _ptr(out.get("jac")), self._stream()))
         self.link_kinematics_launches = self.__dict__.get("link_kinematics_launches", 0) + 1
+        return out
+
+    def raycast(self, dirs, link: int = 0, pos_offset=(0.0, 0.0, 0.0), quat_offset=(1.0, 0.0, 0.0, 0.0), min_range: float = 0.0,
+                max_range: float = 100.0, skip_geoms=(), env_idx=None, world_frame: bool = False, distance: bool = True,
+                points: bool = True, geom: bool = False, normal: bool = False) -> dict:
+        """mir_raycast: the range along the N rays `dirs` ((N,3) float32, sensor frame, any length; a device tensor is used as it is)
+        of ONE sensor that rides on body `link` (0: the world) at `pos_offset` / `quat_offset` (wxyz) in the link's frame, for the envs
+        `env_idx` (int64, any order, repeats allowed; None: all envs), in ONE launch of a kernel of its own.  Every geom not in
+        `skip_geoms` (indices, or the bit mask) is tested; hulls as the polytope of their vertices; a solid that contains the origin
+        is not seen.  distance (R,N) = clamp(range, min_range, max_range), max_range on a miss; points (R,N,3) = distance x the unit
+        direction in the sensor's frame, or origin + that in world axes with `world_frame`; geom (R,N) int32, -1 on a miss; normal
+        (R,N,3) unit outward normal in the axes of points, 0 on a miss.  Only the outputs asked for are computed and returned: fresh
+        device tensors on the current stream.  The read changes nothing a later call can see."""
+        if not isinstance(dirs, torch.Tensor):
+            dirs = torch.as_tensor(np.ascontiguousarray(dirs, dtype=np.float32))
+        d = dirs.to(device=self.device, dtype=torch.float32).contiguous()
+        if d.dim() != 2 or d.shape[1] != 3 or d.shape[0] < 1:
+            raise ValueError(f"dirs must be (N, 3) with N >= 1, got {tuple(d.shape)}")
+        N = int(d.shape[0])
+        q = make_ray_query(N, link, pos_offset, quat_offset, min_range, max_range, skip_geoms, world_frame)
+        idx = None
+        if env_idx is not None:
+            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        R = self.num_envs if idx is None else int(idx.numel())
+        out = {}
+        if distance:
+            out["distance"] = torch.empty((R, N), dtype=torch.float32, device=self.device)
+        if points:
+            out["points"] = torch.empty((R, N, 3), dtype=torch.float32, device=self.device)
+        if geom:
+            out["geom"] = torch.empty((R, N), dtype=torch.int32, device=self.device)
+        if normal:
+            out["normal"] = torch.empty((R, N, 3), dtype=torch.float32, device=self.device)
+        self._check(self.lib.mir_raycast(self.h, C.byref(q), _ptr(d), _ptr(idx), R, _ptr(out.get("distance")), _ptr(out.get("points")),
+                                         _ptr(out.get("geom")), _ptr(out.get("normal")), self._stream()))
+        self.raycast_launches = self.__dict__.get("raycast_launches", 0) + 1
         return out
 
     def render(self, cam: MirCameraSpec, vis: MirVisualSpec, mode: int = 0, env_offset: Optional[torch.Tensor] = None,

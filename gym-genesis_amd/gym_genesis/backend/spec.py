@@ -231,6 +231,46 @@ def make_kin_query(links: Sequence[int], local_points=None, dof0: int = 0, n_dof
     q.dof0, q.n_dofs = int(dof0), int(n_dofs)
     return q
 
+MIR_RAY_POINTS_WORLD = 1  # MirRayQuery.flags: points / normal in world axes (include/mirigid.h)
+
+
+class MirRayQuery(C.Structure):
+    """include/mirigid.h: MirRayQuery (mir_raycast)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("link_body", C.c_int32),
+        ("pos_offset", C.c_float * 3),
+        ("quat_offset", C.c_float * 4),
+        ("min_range", C.c_float),
+        ("max_range", C.c_float),
+        ("n_rays", C.c_int32),
+        ("flags", C.c_uint32),
+        ("skip_geoms", C.c_uint64),
+    ]
+
+
+def make_ray_query(n_rays: int, link: int = 0, pos_offset=(0.0, 0.0, 0.0), quat_offset=(1.0, 0.0, 0.0, 0.0), min_range: float = 0.0,
+                   max_range: float = 100.0, skip_geoms=(), world_frame: bool = False) -> MirRayQuery:
+    """link: body index of the spec the sensor rides on (0: the world); skip_geoms: geom indices that are not tested, or the bit mask."""
+    q = MirRayQuery()
+    q.struct_size = C.sizeof(MirRayQuery)
+    q.link_body, q.n_rays = int(link), int(n_rays)
+    q.pos_offset[:] = [float(v) for v in pos_offset]
+    q.quat_offset[:] = [float(v) for v in quat_offset]
+    q.min_range, q.max_range = float(min_range), float(max_range)
+    q.flags = MIR_RAY_POINTS_WORLD if world_frame else 0
+    if isinstance(skip_geoms, int):
+        q.skip_geoms = skip_geoms
+    else:
+        mask = 0
+        for g in skip_geoms:
+            if not 0 <= int(g) < 64:
+                raise ValueError(f"skip_geoms: geom index {g} outside 0 .. 63")
+            mask |= 1 << int(g)
+        q.skip_geoms = mask
+    return q
+
+
 IK_DEFAULTS = dict(max_iters=20, respect_joint_limit=1, damping=0.05, pos_tol=5e-4, rot_tol=5e-3, max_step=0.5)
 
 RENDER_PER_ENV, RENDER_GLOBAL = 0, 1

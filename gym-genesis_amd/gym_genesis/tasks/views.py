@@ -559,3 +559,10 @@ class SceneView:
 
     def step(self) -> None:
         self._mir.step(1)
+
+    def add_sensor(self, options):
+        """``scene.add_sensor(gs.sensors.Lidar(...))``: a ray-cast range sensor (tasks/sensors.py: Raycaster / Lidar / DepthCamera options)
+        on a link or fixed in the world; ``sensor.read()`` -> (points, distances) in one launch (mir_raycast)."""
+        from .sensors import make_sensor
+
+        return make_sensor(self._mir, options)

@@ -481,6 +481,57 @@ int mir_link_kinematics(MirHandle h, const MirKinQuery* q, const int64_t* env_id
                         float* pos /* (R, L, 3) */, float* quat /* (R, L, 4) wxyz */, float* vel /* (R, L, 6) lin, ang */,
                         float* jac /* (R, L, 6, n_dofs) */, void* stream);
 
+/* ---- range sensing: batched ray casts ------------------------------------------------------------------
+ * scene.add_sensor(gs.sensors.Lidar / Raycaster / DepthCamera(...)) + sensor.read() -> points, distances of Genesis (parity with
+ * Genesis unpinned: the reference's tasks cast no rays and the package is not in the reference tree; the names follow its sensor API
+ * as far as it is remembered).  Obstacle distances, wrist range finders, height scans, clearance rewards.  cam.render(depth=True),
+ * the other way to a distance, is tied to a pinhole raster, reports planar depth and draws every hull as its bounding box.
+ * ONE launch of a kernel of its own for N rays of ONE sensor on R rows: it reads the link poses and the compiled model and writes only
+ * its outputs.
+ *   R = n_rows, or num_envs when env_idx is NULL; row k belongs to env env_idx[k] (int64, device; repeats and any order allowed; an
+ *   index outside the batch is clamped as in mir_link_kinematics).  N = q->n_rays; dirs (N, 3) is shared by all rows.
+ * Ray.  With o_link, R_link the world pose of body q->link_body (0: the world, identity):  sensor origin o = o_link + R_link pos_offset,
+ *   sensor axes R_s = R_link R(quat_offset);  ray i is  o + t R_s d_i / |d_i|,  t >= 0 -- t is Euclidean range.  A zero direction
+ *   reports no hit.
+ * Surfaces.  Every geom of the spec whose bit in skip_geoms is clear, in the env's own frame (no env offsets).  Plane: two-sided,
+ *   unbounded.  Box, sphere, capsule: exact (a sphere is a capsule with hl = 0).  Hull: the exact convex polytope of its vertices, not
+ *   its bounding box (face planes by brute force over vertex triples, once per handle, at the first call).  A solid that contains the
+ *   origin is not seen (the rasteriser's rule for a camera inside a solid: a sensor inside its own link's capsule works without
+ *   skip_geoms).  The nearest entry wins, ties go to the lower geom index.
+ * Outputs.  With t_hit the winning entry (no hit, or a hit beyond max_range: a miss):
+ *   distance (R, N)    = clamp(t_hit, min_range, max_range); max_range on a miss;
+ *   geom     (R, N)    = the hit's geom index of the spec, -1 on a miss (a hit nearer than min_range keeps its geom and normal);
+ *   points   (R, N, 3) = distance x the unit direction in the sensor's frame (distance d^), or with MIR_RAY_POINTS_WORLD the origin plus
+ *                        that, in world axes;
+ *   normal   (R, N, 3) = the unit outward normal at the hit in the axes of `points`, 0 on a miss; a plane's normal faces the origin.
+ * Every output is nullable and written only when asked for; all four NULL, or R == 0: MIR_OK without a launch.  points / normal leave
+ * as 16-byte stores whatever their alignment (any 4-byte aligned address works).
+ * A read changes nothing a later call can see: state, targets, warm start, state version, diagnostics, counters and the scratch row of
+ * a split step stay as they are, and the steps around it are bit for bit those of a run without it.  The link poses come from the
+ * rasteriser's pose cache: when the state has moved since the cache was written the call first refreshes it, exactly as mir_render
+ * does (one forward-kinematics launch; tests/test_gpu_raycast.py holds the steps around it to the bits).  Unlike mir_render it does not
+ * make the step launches write the cache themselves: they stay the launches they were.
+ * MIR_E_INVALID: a NULL handle, query or dirs; struct_size != sizeof(MirRayQuery); n_rays < 1; a link outside 0 .. nbody - 1; ranges
+ * that are not finite or not 0 <= min_range < max_range; an unknown flag bit; a skip_geoms bit at or above ngeom; an offset that is not
+ * finite or a zero quat_offset; a call while a mir_step_begin is open (the rule of the two other sensing calls); a hull without volume.
+ * MIR_E_CAPACITY: R x N, or the R x ceil(N / 256) workgroups, do not fit 2^31 - 1.  None of them launches anything.
+ * (An added struct and entry point: MIR_VERSION and every other struct stay as they are.) */
+#define MIR_RAY_POINTS_WORLD 1u   /* points / normal in world axes (default: the sensor's frame) */
+typedef struct MirRayQuery {
+  int32_t  struct_size;           /* = sizeof(MirRayQuery) */
+  int32_t  link_body;             /* 0 = fixed in the world, else body 1 .. nbody-1 the sensor rides on */
+  float    pos_offset[3], quat_offset[4]; /* sensor frame in the link's frame (wxyz, normalised by the library) */
+  float    min_range, max_range;  /* 0 <= min_range < max_range, finite */
+  int32_t  n_rays;                /* N >= 1 */
+  uint32_t flags;
+  uint64_t skip_geoms;            /* bit g set: geom g is not tested (MIR_MAX_GEOM = 40 < 64) */
+} MirRayQuery;
+int mir_ray_query_sizeof(void);
+int mir_raycast(MirHandle h, const MirRayQuery* q, const float* dirs /* (N,3) device, sensor frame, shared by all rows */,
+                const int64_t* env_idx /* device, nullable */, int32_t n_rows,
+                float* distance /* (R,N) */, float* points /* (R,N,3) */, int32_t* geom /* (R,N) */, float* normal /* (R,N,3) */,
+                void* stream);
+
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
