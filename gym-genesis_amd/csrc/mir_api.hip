@@ -11,40 +11,21 @@
 #include <ctime>
 #include <new>
 
+#include "mir_host.h"
 #include "mir_model.h"
 #include "mir_scene.h"
 #include "mir_spec_pick.h"
 #include "mir_step.h"
 #include "mir_step64.h"
 
+using namespace mir_host;
+
+static_assert((int)RK_FULL == (int)STEP_FULL && (int)RK_POST == (int)STEP_POST && (int)RK_ROTATED == (int)STEP_ROTATED && (int)RK_HEAVY48 == (int)STEP_HEAVY48 &&
+              (int)RK_POST48 == (int)STEP_POST48 && (int)RK_ROTATED_LIST == (int)STEP_ROTATED_LIST, "mir_route.h numbers its launches like StepKind");
+
 namespace {
 
 thread_local char g_err[512] = "";
-
-int set_err(int code, const char* fmt, const char* detail = "") {
-  snprintf(g_err, sizeof g_err, fmt, detail);
-  return code;
-}
-int hip_fail(hipError_t e, const char* what) {
-  snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
-  return MIR_E_HIP;
-}
-#define HIPCHK(call)                                   \
-  do {                                                 \
-    hipError_t _e = (call);                            \
-    if (_e != hipSuccess) return hip_fail(_e, #call);  \
-  } while (0)
-
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-};
 
 constexpr int TPB = 256;
 inline int nblk(long n) { return (int)((n + TPB - 1) / TPB); }
@@ -171,35 +152,18 @@ __global__ void k_get_bad(const int32_t* diag, uint8_t* bad, int B) {
   if (e < B) bad[e] = (uint8_t)((diag[(long)e * 4 + 3] >> 30) & 1);
 }
 
-// launch arguments common to both kernels
-struct Outs {
-  const float* action = nullptr;
-  float *agent_pos = nullptr, *env_state = nullptr, *reward = nullptr;
-  uint8_t* terminated = nullptr;
-  uint8_t* term_host = nullptr;
-  uint32_t *done_ticket = nullptr, *done_flag = nullptr;
-  uint32_t done_seq = 0, term_tag = 0;
-  float *out_M = nullptr, *out_bias = nullptr, *out_qas = nullptr, *out_qacc = nullptr, *out_xpos = nullptr, *out_xquat = nullptr;
-  float* rows = nullptr;
-  int row_stride = 0, mode = 0, n_steps = 1;
-  long act_step = 0, rows_step = 0;
-  AutoResetArgs ar = {nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0};
-  bool diag = true;
-  bool poses = false;  // 16-lane kernel: also write the link poses into h->poses (the rasteriser reads them)
-  int kind = STEP_FULL;  // 16-lane kernel: which launch (StepKind, mir_step.h); STEP_FULL = a whole step, narrowed by mir_launch_step
-  int exact = 0;       // 16-lane kernel: defer the envs with more candidate points than lanes (StepArgs::exact)
-  int over_cap = 0;    // 16-lane kernel, STEP_LIST48 / STEP_HEAVY48 (StepArgs::over_cap)
-  const int32_t* env_list = nullptr;  // 16-lane kernel, the kinds of step_reads_env_list: serve the envs env_list[0 .. nlist) (StepArgs::env_list)
-  int nlist = 0;
-  uint32_t* next_host = nullptr;      // 16-lane kernel, STEP_PRE48 (StepArgs::next_host)
-  unsigned long long* prof = nullptr;  // 16-lane kernel only (debug)
-  // contact force sensing (mir_contact_forces; StepArgs::cf_*)
-  int32_t *cf_ncon = nullptr, *cf_ids = nullptr;
-  uint8_t* cf_flags = nullptr;
-  float *cf_geom = nullptr, *cf_force = nullptr, *cf_link = nullptr;
-};
+}  // namespace
 
-int launch(MirScene* h, const Outs& o, void* stream) {
+int mir_host::set_err(int code, const char* fmt, const char* detail) {
+  snprintf(g_err, sizeof g_err, fmt, detail);
+  return code;
+}
+int mir_host::hip_fail(hipError_t e, const char* what) {
+  snprintf(g_err, sizeof g_err, "%s: %s", what, hipGetErrorString(e));
+  return MIR_E_HIP;
+}
+
+int mir_host::launch(MirScene* h, const Outs& o, void* stream) {
   int rc;
   // (a contact sensor read moves no state and writes no scratch row: `pre` stays as valid as it was, so the rotated launches of
   //  GenesisEnv.step go on undisturbed behind it)
@@ -233,7 +197,7 @@ int launch(MirScene* h, const Outs& o, void* stream) {
     a.term_host = o.term_host; a.term_tag = o.term_tag; a.done_ticket = o.done_ticket; a.done_flag = o.done_flag; a.done_seq = o.done_seq;
     a.kind = o.kind; a.pre = h->pre;
     a.exact = o.exact; a.over_cap = o.over_cap;
-    a.pre_big = step_uses_pre_big(o.kind) ? h->pre_big : nullptr;
+    a.pre_big = step_uses_pre_big(o.kind) ? h->xc.res.pre_big : nullptr;
     a.next_host = o.next_host;
     a.cf_ncon = o.cf_ncon; a.cf_flags = o.cf_flags; a.cf_ids = o.cf_ids; a.cf_geom = o.cf_geom; a.cf_force = o.cf_force; a.cf_link = o.cf_link;
     if (step_forward_only(o.kind)) a.features &= ~FEAT_SPEC;  // (off the hot path: the generic-scene instantiation)
@@ -285,17 +249,16 @@ int launch(MirScene* h, const Outs& o, void* stream) {
   return MIR_OK;
 }
 
-int check(MirHandle h) {
-  if (!h) return set_err(MIR_E_INVALID, "null MirHandle");
-  return MIR_OK;
-}
+namespace {
 
 // words of the early-mask counters: mismatches + one `sent` counter per workgroup of the 16-lane kernel (mir_step.h)
 size_t early_words(const MirScene* h) { return 2 + ((size_t)h->B + 3) / 4; }
 
 // The sticky word a step kernel raises when terminated bytes it sent early differ from the integrated state (mir_step.hip).  Checked
 // by every entry point of the env.step path: fails ONCE with MIR_E_MASK and switches the handle to late bytes.
-int check_mask(MirScene* h) {
+}  // namespace
+
+int mir_host::check_mask(MirScene* h) {
   if (!h->pin_host) return MIR_OK;
   volatile uint32_t* bad = reinterpret_cast<volatile uint32_t*>(h->pin_host + h->pin_flag_off + 16);
   if (*bad == 0u) return MIR_OK;
@@ -304,6 +267,8 @@ int check_mask(MirScene* h) {
   return set_err(MIR_E_MASK, "terminated bytes sent before the solve had finished differ from the integrated state: a mask returned since the last "
                              "successful call was wrong; early bytes are now off for this handle (MIR_NO_EARLY_MASK=1 avoids them from the start)");
 }
+
+namespace {
 
 // device half of mir_create: every allocation lands in the handle at once, so the caller can release a partially built
 // scene with mir_destroy whichever call failed
@@ -508,16 +473,9 @@ int mir_destroy(MirHandle h) {
   if (h->done_ticket) (void)hipFree(h->done_ticket);
   if (h->scratch_row) (void)hipFree(h->scratch_row);
   if (h->pre) (void)hipFree(h->pre);
-  if (h->pre_big) (void)hipFree(h->pre_big);
-  if (h->xr_stats) (void)hipFree(h->xr_stats);
   if (h->ray_tab) (void)hipFree(h->ray_tab);
-  if (h->main_event) (void)hipEventDestroy((hipEvent_t)h->main_event);
-  if (h->light_event) (void)hipEventDestroy((hipEvent_t)h->light_event);
-  if (h->next_host) (void)hipHostFree(h->next_host);
   if (h->pin_host) (void)hipHostFree(h->pin_host);
-  if (h->ovf_list_host) (void)hipHostFree(h->ovf_list_host);
-  if (h->ovf_event) (void)hipEventDestroy((hipEvent_t)h->ovf_event);
-  if (h->ovf_stream) (void)hipStreamDestroy((hipStream_t)h->ovf_stream);
+  exact_destroy(h);
   delete h;
   return MIR_OK;
 }
@@ -546,7 +504,7 @@ int mir_reset(MirHandle h, const float* obj_pos, const float* obj_quat, const fl
   }
   if (int rc = check_mask(h)) return rc;
   h->pre_valid = 0;
-  if (!env_mask) { h->heavy = 0; h->perm_next = -1; h->bigmode = 0; }  // (exact contacts: a full reset ends a heavy phase -- every env is back at its start)
+  if (!env_mask) { h->xc.phase.heavy = 0; h->xc.phase.perm_next = -1; h->xc.phase.bigmode = 0; }  // (exact contacts: a full reset ends a heavy phase and an overflow run -- every env is back at its start)
   h->poses_current = 0;
   h->state_version++;
   DeviceGuard guard(h->device);
@@ -582,7 +540,7 @@ int mir_set_pd_targets(MirHandle h, const float* tgt, void* stream) {
 int mir_step(MirHandle h, int32_t n_steps, void* stream) {
   if (check(h)) return MIR_E_INVALID;
   if (n_steps <= 0) return MIR_OK;
-  if (h->exact) {  // (exact contacts: every step is closed on the host, where the deferred envs are handed to the wave kernel)
+  if (h->xc.on) {  // (exact contacts: every step is closed on the host, where the deferred envs are handed to the wave kernel)
     for (int i = 0; i < n_steps; i++) {
       int rc = mir_step_begin(h, nullptr, nullptr, nullptr, nullptr, nullptr, stream);
       if (rc == MIR_OK) rc = mir_step_end(h, nullptr);
@@ -598,7 +556,7 @@ int mir_step(MirHandle h, int32_t n_steps, void* stream) {
 
 int mir_step_fused(MirHandle h, const float* action, float* agent_pos, float* env_state, float* reward, uint8_t* terminated, void* stream) {
   if (check(h)) return MIR_E_INVALID;
-  if (h->exact) {  // (exact contacts: begin + end -- the call then waits for the step's terminated bytes)
+  if (h->xc.on) {  // (exact contacts: begin + end -- the call then waits for the step's terminated bytes)
     const int rc = mir_step_begin(h, action, agent_pos, env_state, reward, terminated, stream);
     return rc != MIR_OK ? rc : mir_step_end(h, nullptr);
   }
@@ -618,45 +576,6 @@ static int g_timing = -1;
 static double g_t0 = 0.0, g_ts[6];
 #define TSTAMP(i) do { if (g_timing > 0) g_ts[i] = wall_us() - g_t0; } while (0)
 
-/* A step of an overflow run whose predecessor's first-half launch has said which envs are above the one-contact-per-lane capacity NOW
- * (h->next_host, tagged h->rt_tag, in the order of perm_host[h->rt_perm]): the order of this step's launches -- those envs first, padded to
- * whole workgroups with others, then the rest -- into perm_host[*buf]; *nh = how many go to the three-contacts-per-lane list. */
-static int split_lists(MirScene* h, int* buf, int* nh_out) {
-  const size_t B = (size_t)h->B, nwg = (B + 3) / 4;
-  const uint32_t want4 = 0x01010101u * (uint8_t)h->rt_tag, tagm4 = 0x1f1f1f1fu;
-  const int32_t* const pp = h->rt_perm >= 0 ? h->perm_host[h->rt_perm] : nullptr;
-  const volatile uint32_t* w = h->next_host;
-  // (straight into the pinned order: the envs above the capacity from the front, the others from the back)
-  const int nxt = h->rt_perm == 0 ? 1 : 0;
-  int32_t* const out = h->perm_host[nxt];
-  size_t nh = 0, lo = B;
-  unsigned long polls = 0;
-  for (size_t g = 0; g < nwg;) {
-    const uint32_t v = w[g];
-    if (((v >> 1) & tagm4) == want4) {
-      for (size_t k = 0; k < 4 && 4 * g + k < B; k++) {
-        const int32_t e = pp ? pp[4 * g + k] : (int32_t)(4 * g + k);
-        if (v >> (8 * k) & 1u) out[nh++] = e; else out[--lo] = e;
-      }
-      g++;
-      continue;
-    }
-    __builtin_ia32_pause();
-    if ((++polls & 0xfffffu) == 0) {
-      hipError_t e = hipStreamQuery((hipStream_t)h->ovf_stream);
-      if (e != hipSuccess && e != hipErrorNotReady) return hip_fail(e, "mir_step_begin: side stream (exact contacts)");
-      if (e == hipSuccess && polls > 0x4000000u) return set_err(MIR_E_HIP, "mir_step_begin: the first-half launch finished without saying which envs are above 16 points");
-    }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  // (whole workgroups: the first of the others join the list of the bigger instantiation, which steps an env with few contacts to the same
-  //  bits -- they sit right behind it in the array already)
-  while ((nh & 3) && nh < B) nh++;
-  __atomic_thread_fence(__ATOMIC_RELEASE);
-  *buf = nxt;
-  *nh_out = (int)nh;
-  return MIR_OK;
-}
 int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* env_state, float* reward, uint8_t* terminated, void* stream) {
   if (check(h)) return MIR_E_INVALID;
   // a step left open (an exception between the two calls on the Python side) is closed here: its bytes are waited for and dropped
@@ -666,84 +585,57 @@ int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* en
   }
   if (int rc = check_mask(h)) return rc;
   DeviceGuard guard(h->device);
+  ExactRoute& x = h->xc;
   uint32_t* flag_dev = reinterpret_cast<uint32_t*>(h->pin_dev + h->pin_flag_off);
   Outs o;
   o.action = action; o.agent_pos = agent_pos; o.env_state = env_state; o.reward = reward; o.terminated = terminated;
   o.term_host = h->pin_dev;
   const uint32_t seq = h->seq + 1u;
-  // The tag has a counter of its own that nothing else advances (h->seq is shared with mir_debug_null_roundtrip and wraps): 1 .. 63,
+  // The tag has a counter of its own that nothing else advances (h->seq is shared with mir_debug_null_roundtrip and wraps): 1 .. 31,
   // never 0 (fresh memory), and a launch's tag differs from those of the 30 launches before it -- each of which overwrote every byte.
   // (Five bits: bit 7 of a byte says "deferred" -- exact contacts, StepArgs::exact -- and bit 6 "more points than the one-contact-per-lane
   //  kernel holds", from the launches that step the whole batch with three contacts per lane, StepArgs::over_cap.)
   const uint32_t tag = h->tag % 31u + 1u;
   o.term_tag = tag;
   if (h->sync_mode == 2) { o.done_ticket = h->done_ticket; o.done_flag = flag_dev; o.done_seq = seq; }
-  // split step: if the previous mir_step_begin left the action-independent half of THIS step in `pre` (same stream, nothing
-  // touched the state since), only the other half is launched now
-  // exact contacts, HEAVY phase (mir_step_end decides): most envs of the last step had more points than the one-contact-per-lane kernel
-  // holds, so the whole batch takes the three-contacts-per-lane instantiation's first pass in ONE launch (STEP_HEAVY48) -- no
-  // launch that defers, no list launch behind it, no scratch rows (the first light step afterwards is launched like the one behind a reset)
-  // exact contacts, an OVERFLOW RUN in a loop that leaves room between two steps (mir_scene.h): the step as TWO launches of the
-  // three-contacts-per-lane instantiation for the whole batch -- second half (-> terminated bytes), then, on the side stream, the first
-  // half of the next step, which runs beside whatever the caller queues between two steps (the policy, its IK).  Costs GPU time (rows
-  // through HBM, two rounds of workgroups twice) and saves time to the bytes; otherwise the heavy phase / the list launch behind the
-  // bytes, which cost less GPU time.
   if (g_timing < 0) g_timing = (getenv("MIR_EXACT_TIMING") && atoi(getenv("MIR_EXACT_TIMING")) != 0) ? 1 : 0;
   if (g_timing > 0) { g_t0 = wall_us(); for (int i = 0; i < 6; i++) g_ts[i] = 0.0; }
-  bool bigrot = false;
-  if (h->exact == 1 && h->exact_big && h->bigmode && h->pre_big != nullptr && h->sync_mode == 3 && h->ovf_stream && h->split_step && h->pre_valid &&
-      h->pre_stream == stream && h->hm.fk_free_leaf != 0) {
-    // (does the caller leave the first-half launch room to hide?  The time it spent between mir_step_end's return and this call: the
-    //  policy and its IK in the reference's expert loop, ~90 us; a loop that does nothing between two steps, 2 - 5 us)
-    if (h->big_on == 2) bigrot = true;  // (MIR_EXACT_BIG=2: whenever the rows are there)
-    else bigrot = h->t_end_us > 0.0 && wall_us() - h->t_end_us >= h->big_gap_us;
-  }
-  const bool heavy = h->exact && h->exact_big && h->heavy && h->sync_mode == 3 && !bigrot;
-  const bool split = h->split_step && h->sync_mode != 2 && !heavy;
-  const bool have_pre = split && h->pre_valid && h->pre_stream == stream;
-  // (one rotated launch -- this step's second half, then the next step's first half -- where the closing FK can be shared between
-  //  the waves; otherwise two launches)
-  const bool rotated = have_pre && h->hm.fk_free_leaf != 0 && h->split_step != 2 && !bigrot;
-  o.kind = heavy ? STEP_HEAVY48 : (bigrot ? STEP_POST48 : (rotated ? STEP_ROTATED : (have_pre ? STEP_POST : STEP_FULL)));
-  o.exact = h->exact;
-  if (bigrot) {
-    o.over_cap = h->hm.max_contacts < K16_MAX_CONTACT ? h->hm.max_contacts : K16_MAX_CONTACT;
-    h->ex_big_steps++;
-  }
-  h->pend_big = bigrot ? 1 : 0;
-  h->pend_perm = -1;
-  if (heavy) {
-    o.over_cap = h->hm.max_contacts < K16_MAX_CONTACT ? h->hm.max_contacts : K16_MAX_CONTACT;
-    h->ex_heavy_steps++;
-    // (the envs in the order mir_step_end left: the ones above 16 points first -- workgroups of like cost, the expensive ones early)
-    if (h->perm_next >= 0) { o.env_list = h->perm_dev[h->perm_next]; o.nlist = h->B; h->pend_perm = h->perm_next; }
-  }
-  // (a step of an overflow run serves the envs in the order mir_step_end left too: the ones above 16 points first -- their workgroups are
-  //  the long ones, and the step's terminated bytes wait for the last of them)
+  // Which launches the step gets (mir_route.h).  Split step: if the previous mir_step_begin left the action-independent half of THIS
+  // step in `pre` (same stream, nothing touched the state since), only the other half is launched now; exact contacts add the heavy
+  // step and the two launches / two lists of an overflow run.
+  BeginFacts f;
+  f.exact = x.on; f.sync_mode = h->sync_mode; f.split_step = h->split_step;
+  f.pre_valid = h->pre_valid != 0; f.same_stream = h->pre_stream == stream; f.fk_free_leaf = h->hm.fk_free_leaf != 0;
+  f.has_pre_big = x.res.pre_big != nullptr; f.has_side_stream = x.res.ovf_stream != nullptr; f.has_next_host = x.res.next_host != nullptr;
+  f.gap_us = (x.phase.bigmode && x.phase.t_end_us > 0.0) ? wall_us() - x.phase.t_end_us : -1.0;  // (the clock is read only inside an overflow run, where the gap can matter)
+  BeginPlan p = plan_begin(x.cfg, x.phase, f);
+  const bool bigrot = p.bigrot, rotated = p.rotated;
+  o.exact = x.on;
+  if (p.heavy || bigrot) o.over_cap = h->hm.max_contacts < K16_MAX_CONTACT ? h->hm.max_contacts : K16_MAX_CONTACT;
+  if (bigrot) x.stats.big_steps++;
+  if (p.heavy) x.stats.heavy_steps++;
+  x.pend.big = bigrot ? 1 : 0;
+  x.pend.heavy = p.heavy ? 1 : 0;
+  x.pend.rotated = rotated ? 1 : 0;
+  x.pend.perm = -1;
+  x.phase.rt_ok = 0;
   int nh_split = -1;  // (>= 0: the step's second half goes out as two lists, perm[0 .. nh) and perm[nh .. B))
-  const int rt_ok_prev = h->rt_ok;
-  h->rt_ok = 0;
-  if (bigrot && rt_ok_prev && h->big_side && h->next_host && h->big_lists) {
-    int buf = -1;
-    if (int rc = split_lists(h, &buf, &nh_split)) return rc;
-    h->pend_perm = buf;
-    if (nh_split == 0 || nh_split >= h->B) {  // (one list after all)
-      o.kind = nh_split == 0 ? STEP_ROTATED_LIST : STEP_POST48;
-      o.env_list = h->perm_dev[buf]; o.nlist = h->B;
-      nh_split = -1;
-    }
-  } else if (bigrot && h->perm_next >= 0) { o.env_list = h->perm_dev[h->perm_next]; o.nlist = h->B; h->pend_perm = h->perm_next; }
-  h->pend_heavy = heavy ? 1 : 0;
-  // (exact contacts, ADVICE r5: the launches for the deferred envs of an earlier step ran on the library's side stream, and only the stream
-  //  of THAT step was made to wait for them; a step on another stream waits for them here -- state rows, scratch rows and the pinned
-  //  list are theirs until then)
-  if (h->ovf_event_live && h->ovf_waited_stream != stream) {
-    HIPCHK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)h->ovf_event, 0));
-    h->ovf_waited_stream = stream;
+  if (p.lists) {
+    int nh = 0;
+    if (int rc = split_lists(h, &p.perm, &nh)) return rc;
+    if (plan_lists(p, nh, h->B)) nh_split = nh;
   }
-  h->pend_action = action;
-  h->pend_out[0] = agent_pos; h->pend_out[1] = env_state; h->pend_out[2] = reward; h->pend_out[3] = terminated;
-  h->pend_rotated = rotated ? 1 : 0;
+  o.kind = p.kind;
+  x.pend.perm = p.perm;
+  if (p.perm >= 0) { o.env_list = x.res.perm_dev[p.perm]; o.nlist = h->B; }
+  // (the launches for the deferred envs of an earlier step ran on the library's side stream, and only the stream of THAT step was made
+  //  to wait for them; a step on another stream waits for them here -- state rows, scratch rows and the pinned list are theirs until then)
+  if (x.res.ovf_event_live && x.res.ovf_waited_stream != stream) {
+    HIPCHK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)x.res.ovf_event, 0));
+    x.res.ovf_waited_stream = stream;
+  }
+  x.pend.action = action;
+  x.pend.out[0] = agent_pos; x.pend.out[1] = env_state; x.pend.out[2] = reward; x.pend.out[3] = terminated;
   o.prof = h->dbg_prof;
   h->dbg_prof = nullptr;
   int rc;
@@ -751,26 +643,26 @@ int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* en
     // the envs above 16 points on the three-contacts-per-lane instantiation (80 KB workgroups, the long ones: first, on the step's stream),
     // the others in ONE round of the one-contact-per-lane kernel's 40 KB workgroups on the side stream; the step's stream waits for those
     Outs oh = o, ol = o;
-    oh.env_list = h->perm_dev[h->pend_perm]; oh.nlist = nh_split;
+    oh.nlist = nh_split;
     ol.kind = STEP_ROTATED_LIST; ol.over_cap = 0; ol.prof = nullptr;
-    ol.env_list = h->perm_dev[h->pend_perm] + nh_split; ol.nlist = h->B - nh_split;
+    ol.env_list = o.env_list + nh_split; ol.nlist = h->B - nh_split;
     ol.term_host = h->pin_dev + (size_t)(nh_split / 4) * h->term_wstride * sizeof(uint32_t);
     // (the side stream's launch reads the caller's action too: behind whatever produced it on the step's stream -- an event recorded
     //  there IN FRONT of the first list's launch, or the second list would wait for the first)
-    HIPCHK(hipEventRecord((hipEvent_t)h->main_event, (hipStream_t)stream));
+    HIPCHK(hipEventRecord((hipEvent_t)x.res.main_event, (hipStream_t)stream));
     rc = launch(h, oh, stream);
     if (rc != MIR_OK) return rc;
-    HIPCHK(hipStreamWaitEvent((hipStream_t)h->ovf_stream, (hipEvent_t)h->main_event, 0));
-    rc = launch(h, ol, h->ovf_stream);
+    HIPCHK(hipStreamWaitEvent((hipStream_t)x.res.ovf_stream, (hipEvent_t)x.res.main_event, 0));
+    rc = launch(h, ol, x.res.ovf_stream);
     if (rc == MIR_OK) {
-      HIPCHK(hipEventRecord((hipEvent_t)h->light_event, (hipStream_t)h->ovf_stream));
-      HIPCHK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)h->light_event, 0));
+      HIPCHK(hipEventRecord((hipEvent_t)x.res.light_event, (hipStream_t)x.res.ovf_stream));
+      HIPCHK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)x.res.light_event, 0));
     }
   } else {
     rc = launch(h, o, stream);
     // (an overflow-run step whose envs are ALL at most at 16 points goes out as the one-contact-per-lane list alone: launch() takes
     //  STEP_ROTATED_LIST for the second list of a step that the first list has counted -- here there is no first list, so the step is
-    //  counted here; it used to go uncounted, and an image cached on the state version survived it)
+    //  counted here)
     if (rc == MIR_OK && o.kind == STEP_ROTATED_LIST) h->state_version++;
   }
   if (rc != MIR_OK) return rc;
@@ -785,31 +677,30 @@ int mir_step_begin(MirHandle h, const float* action, float* agent_pos, float* en
     hipError_t e = hipStreamWriteValue32((hipStream_t)stream, flag_dev, seq, 0);
     if (e != hipSuccess) { (void)hipGetLastError(); h->sync_mode = 0; }  // not supported on this stack: wait on the stream instead
   }
-  if (split && !rotated) {
+  if (p.split && !rotated) {
     // ... and the action-independent half of the NEXT step goes out right behind it: it runs while the host is between two calls
-    Outs p;
-    p.kind = bigrot ? STEP_PRE48 : STEP_PRE; p.diag = false;
-    if (bigrot && h->big_side) {
+    Outs n;
+    n.kind = bigrot ? STEP_PRE48 : STEP_PRE; n.diag = false;
+    if (bigrot && x.pend.perm >= 0) { n.env_list = x.res.perm_dev[x.pend.perm]; n.nlist = h->B; }
+    if (bigrot && x.cfg.big_side) {
       // (... on the side stream, behind the launch above: beside the caller's work between two steps; the next mir_step_begin -- and the
       //  launches for envs this step defers -- come behind it through ovf_event)
-      if (h->pend_perm >= 0) { p.env_list = h->perm_dev[h->pend_perm]; p.nlist = h->B; }
-      if (h->next_host) {  // (... and says which envs the next step finds above the one-contact-per-lane capacity: split_lists)
-        memset(h->next_host, 0, ((size_t)h->B + 3) / 4 * sizeof(uint32_t));  // (tags come round every 31 steps)
+      if (x.res.next_host) {  // (... and says which envs the next step finds above the one-contact-per-lane capacity: split_lists)
+        memset(x.res.next_host, 0, ((size_t)h->B + 3) / 4 * sizeof(uint32_t));  // (tags come round every 31 steps)
         __atomic_thread_fence(__ATOMIC_RELEASE);
-        p.next_host = h->next_dev; p.term_tag = tag;
-        p.over_cap = h->hm.max_contacts < K16_MAX_CONTACT ? h->hm.max_contacts : K16_MAX_CONTACT;
+        n.next_host = x.res.next_dev; n.term_tag = tag;
+        n.over_cap = h->hm.max_contacts < K16_MAX_CONTACT ? h->hm.max_contacts : K16_MAX_CONTACT;
       }
-      HIPCHK(hipEventRecord((hipEvent_t)h->main_event, (hipStream_t)stream));
-      HIPCHK(hipStreamWaitEvent((hipStream_t)h->ovf_stream, (hipEvent_t)h->main_event, 0));
-      rc = launch(h, p, h->ovf_stream);
+      HIPCHK(hipEventRecord((hipEvent_t)x.res.main_event, (hipStream_t)stream));
+      HIPCHK(hipStreamWaitEvent((hipStream_t)x.res.ovf_stream, (hipEvent_t)x.res.main_event, 0));
+      rc = launch(h, n, x.res.ovf_stream);
       if (rc != MIR_OK) return rc;
-      if (h->next_host) { h->rt_ok = 1; h->rt_perm = h->pend_perm; h->rt_tag = tag; }
-      HIPCHK(hipEventRecord((hipEvent_t)h->ovf_event, (hipStream_t)h->ovf_stream));
-      h->ovf_event_live = 1;
-      h->ovf_waited_stream = reinterpret_cast<void*>(~(uintptr_t)0);  // (no stream has been made to wait yet -- the null stream is a stream)
+      if (x.res.next_host) { x.phase.rt_ok = 1; x.phase.rt_perm = x.pend.perm; x.phase.rt_tag = tag; }
+      HIPCHK(hipEventRecord((hipEvent_t)x.res.ovf_event, (hipStream_t)x.res.ovf_stream));
+      x.res.ovf_event_live = 1;
+      x.res.ovf_waited_stream = reinterpret_cast<void*>(~(uintptr_t)0);  // (no stream has been made to wait yet -- the null stream is a stream)
     } else {
-      if (bigrot && h->pend_perm >= 0) { p.env_list = h->perm_dev[h->pend_perm]; p.nlist = h->B; }
-      rc = launch(h, p, stream);
+      rc = launch(h, n, stream);
     }
     if (rc != MIR_OK) return rc;  // (the step itself is queued and pending: the caller may still close it, or the next begin does)
     h->pre_valid = 1;
@@ -837,121 +728,6 @@ int mir_step_go(MirHandle h, const float* action, void* stream) {
   return rc;
 }
 
-/* exact contacts: the n envs of h->ovf_list_host were deferred by the launch(es) of the pending mir_step_begin (their state rows are
- * those of the step's start).  They are stepped here by the LIST INSTANTIATION of the 16-lane kernel (STEP_LIST48, mir_step.h: three
- * contacts per lane, 48 points, four envs per workgroup) -- one launch that takes the action and the output pointers of the pending
- * step, stores state, observations and the terminated byte of list entry k into ovf_term_host[k], and then writes the envs' scratch
- * rows for the NEXT step (which also say whether they are deferred again).  An env beyond THAT kernel's capacity (more than 48 points,
- * or more than 16 candidate pairs: its byte comes back with bit 7 set, nothing stored) goes on a second list and takes the route every
- * deferred env took in round 5: the wave-per-env kernel in list mode (the same scene compiled for it, 64 candidates, reading and
- * writing the 16-lane kernel's rows) followed by the action-independent half of the 16-lane kernel over that list.  MIR_EXACT_WAVE=1
- * (read by mir_set_exact_contacts), or a scene without the split closing FK, sends every deferred env that way.
- * The launches go on a stream of the library's own, BESIDE the launch that deferred these envs (which is still running its second
- * half: the host is here because that launch's terminated bytes -- early bytes -- have arrived): that launch stores nothing for
- * them, and everything queued before it on the step's stream has finished, or it would not be running.  The step's stream then
- * waits for an event recorded behind them, so that whatever the caller queues after mir_step_end -- the next step, a
- * policy network reading the observations -- comes after them. */
-static int exact_wait(MirScene* h, const uint8_t* term, const int32_t* list, int n, uint8_t* terminated_host, int32_t* again, int* n_again) {
-  const uint8_t want = (uint8_t)h->tag;
-  unsigned long polls = 0;
-  for (int k = 0; k < n;) {
-    const uint8_t b = __atomic_load_n(term + k, __ATOMIC_RELAXED);
-    if ((uint8_t)((b >> 1) & 0x1fu) == want) {
-      if ((b & 0x80u) && again) again[(*n_again)++] = list[k];
-      else if (terminated_host) terminated_host[list[k]] = b & 1u;
-      k++;
-      continue;
-    }
-    __builtin_ia32_pause();
-    if ((++polls & 0xfffffu) == 0) {
-      hipError_t e = hipStreamQuery((hipStream_t)h->pending_stream);
-      if (e != hipSuccess && e != hipErrorNotReady) return hip_fail(e, "mir_step_end: stream (exact contacts)");
-      if (e == hipSuccess && polls > 0x4000000u) return set_err(MIR_E_HIP, "mir_step_end: the launch for the deferred envs finished without delivering its terminated bytes");
-    }
-  }
-  __atomic_thread_fence(__ATOMIC_ACQUIRE);
-  return MIR_OK;
-}
-
-static int exact_finish(MirScene* h, int n, uint8_t* terminated_host) {
-  DeviceGuard guard(h->device);
-  h->ex_ovf_steps++;
-  h->ex_ovf_envs += (unsigned long long)n;
-  if ((unsigned long long)n > h->ex_ovf_max) h->ex_ovf_max = (unsigned long long)n;
-  // (not beside a step that was launched as two kernels -- a fused launch, or the second half alone, followed by the first half of the
-  //  next step for ALL envs: that second kernel writes the scratch rows of the deferred envs too, from their old state, and must come
-  //  BEFORE the one below that writes them from the new state: stream order does that)
-  void* const side = (h->ovf_stream && (h->pend_rotated || h->pend_big)) ? h->ovf_stream : h->pending_stream;  // (pend_big: behind the first-half launch, which is there)
-  const size_t B = (size_t)h->B;
-  int32_t* const list2_host = reinterpret_cast<int32_t*>(h->ovf_term_host + (B + 63) / 64 * 64);
-  int32_t* const list2_dev = reinterpret_cast<int32_t*>(h->ovf_term_dev + (B + 63) / 64 * 64);
-  uint8_t* const term2_host = reinterpret_cast<uint8_t*>(list2_host + B);
-  uint8_t* const term2_dev = reinterpret_cast<uint8_t*>(list2_dev + B);
-  const int32_t* wlist_host = h->ovf_list_host;
-  const int32_t* wlist_dev = h->ovf_list_dev;
-  const uint8_t* wterm_host = h->ovf_term_host;
-  uint8_t* wterm_dev = h->ovf_term_dev;
-  int nw = n;  // envs for the wave-per-env kernel
-  if (h->pend_heavy) {
-    // (a heavy step: these envs were beyond the three-contacts-per-lane capacity already -- straight to the wave-per-env kernel; the
-    //  statistics of a heavy step count the envs above the one-contact-per-lane capacity, mir_step_end)
-    h->ex_ovf_steps--; h->ex_ovf_envs -= (unsigned long long)n;
-  } else if (h->exact_big) {
-    // (a step of an overflow run: envs whose big row the launch before could not write -- the fused pass of the list instantiation, which
-    //  hands on what is beyond its capacity too; the step's statistics come from bit 6 of the bytes, mir_step_end)
-    if (h->pend_big) { h->ex_ovf_steps--; h->ex_ovf_envs -= (unsigned long long)n; }
-    memset(h->ovf_term_host, 0, (size_t)n);  // (tags come round every 63 steps: a byte of an older step must not pass for this one's)
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    Outs o;
-    o.action = h->pend_action;
-    o.agent_pos = (float*)h->pend_out[0]; o.env_state = (float*)h->pend_out[1]; o.reward = (float*)h->pend_out[2]; o.terminated = (uint8_t*)h->pend_out[3];
-    o.term_host = h->ovf_term_dev; o.term_tag = h->tag;
-    o.kind = STEP_LIST48; o.env_list = h->ovf_list_dev; o.nlist = n;
-    o.prof = h->dbg_prof_list;
-    h->dbg_prof_list = nullptr;
-    int rc = launch(h, o, side);
-    if (rc != MIR_OK) return rc;
-    h->ex_big_envs += (unsigned long long)n;
-    nw = 0;
-    rc = exact_wait(h, h->ovf_term_host, h->ovf_list_host, n, terminated_host, list2_host, &nw);
-    if (rc != MIR_OK) return rc;
-    wlist_host = list2_host; wlist_dev = list2_dev; wterm_host = term2_host; wterm_dev = term2_dev;
-  }
-  if (nw) {
-    memset(const_cast<uint8_t*>(wterm_host), 0, (size_t)nw);
-    __atomic_thread_fence(__ATOMIC_RELEASE);
-    StepArgs64 a;
-    memset(&a, 0, sizeof a);
-    a.model = h->dm64;
-    a.qpos = h->qpos; a.qvel = h->qvel; a.target = h->target; a.qacc_ws = h->qacc_ws;
-    a.diag = h->diag_on ? h->diag : nullptr;
-    a.bad_count = h->early_stats;
-    a.B = nw; a.nu = h->hm64.nu; a.convex = h->hm64.has_convex;
-    a.action = h->pend_action;
-    a.agent_pos = (float*)h->pend_out[0]; a.env_state = (float*)h->pend_out[1]; a.reward = (float*)h->pend_out[2]; a.terminated = (uint8_t*)h->pend_out[3];
-    a.term_host = wterm_dev; a.term_tag = h->tag;
-    a.mode = 0; a.n_steps = 1;
-    a.env_list = wlist_dev; a.lay16_qst = h->hm.qstride;
-    h->ex_wave_envs += (unsigned long long)nw;
-    int rc = mir_launch_step64(&a, (hipStream_t)side);
-    if (rc != 0) return hip_fail((hipError_t)rc, "wave kernel launch (exact contacts)");
-    h->poses_current = 0;  // (these envs' link poses were not written)
-    if (h->pre_valid) {  // (split step: the scratch rows of the coming step, for the envs that have only now reached its starting state)
-      Outs p;
-      p.kind = STEP_PRE; p.diag = false; p.env_list = wlist_dev; p.nlist = nw;
-      rc = launch(h, p, side);
-      if (rc != MIR_OK) return rc;
-    }
-  }
-  if (side != h->pending_stream) {
-    HIPCHK(hipEventRecord((hipEvent_t)h->ovf_event, (hipStream_t)side));
-    HIPCHK(hipStreamWaitEvent((hipStream_t)h->pending_stream, (hipEvent_t)h->ovf_event, 0));
-    h->ovf_event_live = 1;
-    h->ovf_waited_stream = h->pending_stream;
-  }
-  if (nw) return exact_wait(h, wterm_host, wlist_host, nw, terminated_host, nullptr, nullptr);
-  return MIR_OK;
-}
 
 int mir_step_end(MirHandle h, uint8_t* terminated_host) {
   if (check(h)) return MIR_E_INVALID;
@@ -960,31 +736,34 @@ int mir_step_end(MirHandle h, uint8_t* terminated_host) {
   //  pending and is closed by the next call)
   if (int rc = check_mask(h)) return rc;
   h->pending = 0;
+  ExactRoute& x = h->xc;
   volatile uint32_t* flag = reinterpret_cast<volatile uint32_t*>(h->pin_host + h->pin_flag_off);
   const uint8_t* bytes = h->pin_host;
   const size_t B = (size_t)h->B;
+  static const char* const no_bytes = "mir_step_end: the launch finished without delivering its terminated bytes";
   if (h->sync_mode == 0) {
     DeviceGuard guard(h->device);
     HIPCHK(hipStreamSynchronize((hipStream_t)h->pending_stream));
   } else if (h->sync_mode == 3 && h->term_wstride) {
     // 16-lane kernel: one 32-bit word (4 envs) per workgroup, `term_wstride` words apart; every byte carries this launch's tag.  One
     // pass: wait for a word, take its bits, go on to the next (the pointer stands still at the first workgroup that has not delivered)
-    // (exact contacts: bit 7 of a byte = the env was deferred by the launch -- collected here, stepped by exact_finish)
+    // (exact contacts: bit 7 of a byte = the env was deferred by the launch -- collected here, stepped by exact_finish; bit 6 = above 16 points)
     const uint32_t want4 = 0x01010101u * (uint8_t)h->tag, tagm4 = 0x1f1f1f1fu;
     const volatile uint32_t* w = reinterpret_cast<const volatile uint32_t*>(bytes);
     const size_t nwg = (B + 3) / 4, ws = (size_t)h->term_wstride;
-    unsigned long polls = 0;
     int ndefer = 0, nover = 0;
     TSTAMP(2);
-    h->ex_steps++;
-    // (a launch of a heavy phase may have served the envs in a permuted order: byte k of workgroup g is env pp[4 g + k])
-    const int32_t* const pp = (h->exact && h->pend_perm >= 0) ? h->perm_host[h->pend_perm] : nullptr;
-    for (size_t g = 0; g < nwg;) {
-      uint32_t v = w[g * ws];
-      if (((v >> 1) & tagm4) == want4) {
-        if ((v & 0x80808080u) && h->exact) {
+    x.stats.steps++;
+    // (a heavy or two-launch step may have served the envs in a permuted order: byte k of workgroup g is env pp[4 g + k])
+    const int32_t* const pp = (x.on && x.pend.perm >= 0) ? x.res.perm_host[x.pend.perm] : nullptr;
+    size_t g = 0;
+    int rc = spin_until(h, h->pending_stream, "mir_step_end: stream", no_bytes, true, [&]() {
+      for (; g < nwg; g++) {
+        uint32_t v = w[g * ws];
+        if (((v >> 1) & tagm4) != want4) return false;
+        if ((v & 0x80808080u) && x.on) {
           for (size_t k = 0; k < 4 && 4 * g + k < B; k++)
-            if (v >> (8 * k + 7) & 1u) h->ovf_list_host[ndefer++] = pp ? pp[4 * g + k] : (int32_t)(4 * g + k);
+            if (v >> (8 * k + 7) & 1u) x.res.ovf_list_host[ndefer++] = pp ? pp[4 * g + k] : (int32_t)(4 * g + k);
         }
         nover += __builtin_popcount(v & 0x40404040u);
         if (terminated_host) {
@@ -995,64 +774,29 @@ int mir_step_end(MirHandle h, uint8_t* terminated_host) {
             memcpy(terminated_host + 4 * g, &v, 4 * g + 4 <= B ? 4 : B - 4 * g);
           }
         }
-        g++;
-        continue;
       }
-      __builtin_ia32_pause();
-      if ((++polls & 0xfffffu) == 0) {
-        DeviceGuard guard(h->device);
-        hipError_t e = hipStreamQuery((hipStream_t)h->pending_stream);
-        if (e != hipSuccess && e != hipErrorNotReady) return hip_fail(e, "mir_step_end: stream");
-        if (e == hipSuccess && polls > 0x4000000u)
-          return set_err(MIR_E_HIP, "mir_step_end: the launch finished without delivering its terminated bytes");
-      }
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+      return true;
+    });
+    if (rc != MIR_OK) return rc;
     TSTAMP(3);
-    if (h->exact && h->exact_big) {
-      // light -> heavy when this step deferred at least heavy_enter envs; heavy -> light when fewer than heavy_leave had more points than
-      // the one-contact-per-lane kernel holds (MIR_EXACT_HEAVY="enter,leave"; enter <= 0: never heavy).  The cost model behind the
-      // defaults: a light step with a deferred list costs launch + list launch, a heavy one two rounds of the bigger kernel.
-      if (h->pend_heavy || h->pend_big) { h->ex_ovf_envs += (unsigned long long)nover; if (nover) h->ex_ovf_steps++; if ((unsigned long long)nover > h->ex_ovf_max) h->ex_ovf_max = nover; }
-      // an overflow run starts behind the first step that deferred an env and ends with the first of its steps in which no env is above 16 points
-      if (h->big_on) {
-        if (!h->bigmode && ndefer > 0) h->bigmode = 1;
-        else if (h->pend_big && nover == 0 && ndefer == 0) h->bigmode = 0;
-      }
-      const int cnt = h->pend_heavy ? nover : ndefer;
-      if (!h->heavy && h->heavy_enter > 0 && cnt >= h->heavy_enter) h->heavy = 1;
-      else if (h->heavy && cnt < h->heavy_leave) h->heavy = 0;
-      // the order of the NEXT heavy launch: the envs that were above 16 points in this step first (bit 6 of a heavy launch's bytes, bit
-      // 7 -- deferred -- of a light one's), the others behind them.  A workgroup serves four consecutive entries and lasts as long as its
-      // slowest env: with 70 % of the envs at 20 - 38 points and the rest at 4 - 12, unsorted 99 % of the workgroups hold a slow env;
-      // sorted, 30 % of them are done in half the time, and the expensive ones are dispatched first (the words are in this core's
-      // cache: the loop above has just read them)
-      h->perm_next = -1;
-      if ((h->heavy || h->bigmode) && h->heavy_sort && !(h->pend_big && h->rt_ok && !h->heavy)) {  // (rt_ok: the next step of the run takes its order from the first-half launch's words)
-        const int nxt = h->pend_perm == 0 ? 1 : 0;
-        int32_t* const out = h->perm_host[nxt];
-        const uint32_t bit = (h->pend_heavy || h->pend_big) ? 0x40u : 0x80u;
-        size_t nh = 0, nl = B;
-        for (size_t g = 0; g < nwg; g++) {
-          const uint32_t v = w[g * ws];
-          for (size_t k = 0; k < 4 && 4 * g + k < B; k++) {
-            const int32_t e = pp ? pp[4 * g + k] : (int32_t)(4 * g + k);
-            if (v >> (8 * k) & bit) out[nh++] = e; else out[--nl] = e;
-          }
-        }
-        h->perm_next = nxt;
+    if (x.on) {
+      // the step's statistics and the phase of the next one (mir_route.h); then the order of the NEXT heavy or two-launch step: the envs
+      // that were above 16 points in this one first (the words are in this core's cache: the loop above has just read them)
+      const CloseResult c = close_step(x.cfg, x.phase, x.pend, x.stats, ndefer, nover);
+      if (c.sort) {
+        const int nxt = x.pend.perm == 0 ? 1 : 0;
+        partition_by_bit(w, ws, pp, B, c.bit, x.res.perm_host[nxt]);
+        x.phase.perm_next = nxt;
       }
     }
-    if (h->big_on) {
-      const int rc = ndefer ? exact_finish(h, ndefer, terminated_host) : MIR_OK;
-      h->t_end_us = wall_us();
-      if (g_timing > 0 && (h->pend_big || ndefer))
+    rc = ndefer ? exact_finish(h, ndefer, terminated_host) : MIR_OK;
+    if (x.cfg.big_on) {
+      x.phase.t_end_us = wall_us();
+      if (g_timing > 0 && (x.pend.big || ndefer))
         fprintf(stderr, "[exact timing] two launches %d, above 16 points %d, deferred %d | main launch queued %.1f, mir_step_begin returns %.1f, mir_step_end called %.1f, "
-                "last byte %.1f, mir_step_end returns %.1f us\n", h->pend_big, nover, ndefer, g_ts[0], g_ts[1], g_ts[2], g_ts[3], h->t_end_us - g_t0);
-      return rc;
+                "last byte %.1f, mir_step_end returns %.1f us\n", x.pend.big, nover, ndefer, g_ts[0], g_ts[1], g_ts[2], g_ts[3], x.phase.t_end_us - g_t0);
     }
-    if (ndefer) return exact_finish(h, ndefer, terminated_host);
-    return MIR_OK;
+    return rc;
   } else if (h->sync_mode == 3) {
     // the bytes announce themselves: wait until every one of them carries this launch's tag
     // (a pointer that walks the buffer once, eight bytes at a time: it stands still at the first workgroup that has not delivered
@@ -1063,34 +807,21 @@ int mir_step_end(MirHandle h, uint8_t* terminated_host) {
     const volatile uint64_t* w8 = reinterpret_cast<const volatile uint64_t*>(bytes);
     const size_t nw = B / 8;
     size_t i = 0;  // in 8-byte words, then the tail bytes
-    unsigned long polls = 0;
-    while (i < nw + (B - nw * 8)) {
-      const bool ok = i < nw ? (((w8[i] >> 1) & tagm) == want8)
-                             : ((uint8_t)((__atomic_load_n(bytes + nw * 8 + (i - nw), __ATOMIC_RELAXED) >> 1) & 0x1fu) == want);
-      if (ok) { i++; continue; }
-      __builtin_ia32_pause();
-      if ((++polls & 0xfffffu) == 0) {
-        DeviceGuard guard(h->device);
-        hipError_t e = hipStreamQuery((hipStream_t)h->pending_stream);
-        if (e != hipSuccess && e != hipErrorNotReady) return hip_fail(e, "mir_step_end: stream");
-        if (e == hipSuccess && polls > 0x4000000u)
-          return set_err(MIR_E_HIP, "mir_step_end: the launch finished without delivering its terminated bytes");
+    int rc = spin_until(h, h->pending_stream, "mir_step_end: stream", no_bytes, true, [&]() {
+      for (; i < nw + (B - nw * 8); i++) {
+        const bool ok = i < nw ? (((w8[i] >> 1) & tagm) == want8)
+                               : ((uint8_t)((__atomic_load_n(bytes + nw * 8 + (i - nw), __ATOMIC_RELAXED) >> 1) & 0x1fu) == want);
+        if (!ok) return false;
       }
-    }
-    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+      return true;
+    });
+    if (rc != MIR_OK) return rc;
   } else {
-    // spin on the pinned completion word; every 2^20 polls make sure the stream has not died under us
-    unsigned long polls = 0;
-    while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != h->seq) {
-      __builtin_ia32_pause();
-      if ((++polls & 0xfffffu) == 0) {
-        DeviceGuard guard(h->device);
-        hipError_t e = hipStreamQuery((hipStream_t)h->pending_stream);
-        if (e != hipSuccess && e != hipErrorNotReady) return hip_fail(e, "mir_step_end: stream");
-        if (e == hipSuccess && __atomic_load_n(flag, __ATOMIC_ACQUIRE) != h->seq)
-          return set_err(MIR_E_HIP, "mir_step_end: the launch finished without publishing its completion word");
-      }
-    }
+    // spin on the pinned completion word (the stream writes it behind the launch: a stream that has finished has written it)
+    const uint32_t seq = h->seq;
+    int rc = spin_until(h, h->pending_stream, "mir_step_end: stream", "mir_step_end: the launch finished without publishing its completion word", false,
+                        [&]() { return __atomic_load_n(flag, __ATOMIC_ACQUIRE) == seq; });
+    if (rc != MIR_OK) return rc;
   }
   if (terminated_host && h->term_wstride) {  // (sync modes 0 - 2 on the 16-lane kernel: one word per workgroup, term_wstride words apart)
     const uint32_t* w = reinterpret_cast<const uint32_t*>(bytes);
@@ -1113,131 +844,12 @@ int mir_step_end(MirHandle h, uint8_t* terminated_host) {
 
 int mir_get_sync_mode(MirHandle h) { return check(h) ? MIR_E_INVALID : h->sync_mode; }
 
-int mir_set_exact_contacts(MirHandle h, const MirSceneSpec* spec, int32_t on) {
-  if (check(h)) return MIR_E_INVALID;
-  if (h->pending) return set_err(MIR_E_INVALID, "mir_set_exact_contacts: a step is pending");
-  // (a scratch row whose head says "above 16 points, the contacts are elsewhere" means something to the launches of this mode only: the
-  //  next step starts from the state, not from the rows)
-  h->pre_valid = 0;
-  h->bigmode = 0;
-  if (!on) { h->exact = 0; return MIR_OK; }
-  if (h->kernel != 16) return set_err(MIR_E_INVALID, "mir_set_exact_contacts: the scene already runs on the wave-per-env kernel (48 contact points, never thinned below that)");
-  if (h->sync_mode != 3 || !h->term_wstride) return set_err(MIR_E_INVALID, "mir_set_exact_contacts: needs the tagged terminated bytes (sync mode 3)");
-  if (!spec) return set_err(MIR_E_INVALID, "mir_set_exact_contacts: the scene's spec is needed once (it is compiled for the wave kernel)");
-  if (!h->ovf_list_host) {
-    // the same scene for the wave-per-env kernel, with that kernel's contact capacity
-    MirSceneSpec* s2 = new (std::nothrow) MirSceneSpec(*spec);
-    if (!s2) return set_err(MIR_E_INVALID, "out of host memory");
-    s2->opt.max_contacts = MIR_MAX_CONTACT;
-    HostConsts hc;
-    char err[256] = "";
-    const int rc = mir_compile_model64(s2, &h->hm64, &hc, err);
-    delete s2;
-    if (rc != MIR_OK) return set_err(rc, "mir_set_exact_contacts: %s", err);
-    if (h->hm64.nv != h->hm.nv || h->hm64.nq != h->hm.nq || h->hm64.nu != h->hm.nu || h->hm64.agent_dim != h->agent_dim || h->hm64.env_dim != h->env_dim)
-      return set_err(MIR_E_INVALID, "mir_set_exact_contacts: the spec is not the one this scene was created from");
-    DeviceGuard guard(h->device);
-    HIPCHK(hipMemcpy(h->dm64, &h->hm64, sizeof(DevModel64), hipMemcpyHostToDevice));
-    // [list of the deferred envs (B x i32) | their terminated bytes (B, padded to 64)] twice: the envs the list instantiation could not
-    // hold either go on the second list (exact_finish)
-    // ... and two permutations of the envs for the launches of a heavy phase (B x i32 each, see mir_step_end)
-    const size_t B = (size_t)h->B, bytes = 2 * (B * sizeof(int32_t) + ((B + 63) / 64) * 64) + 2 * ((B + 15) / 16 * 16) * sizeof(int32_t);
-    HIPCHK(hipHostMalloc((void**)&h->ovf_list_host, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(h->ovf_list_host, 0, bytes);
-    HIPCHK(hipHostGetDevicePointer((void**)&h->ovf_list_dev, h->ovf_list_host, 0));
-    h->ovf_term_host = reinterpret_cast<uint8_t*>(h->ovf_list_host + B);
-    h->ovf_term_dev = reinterpret_cast<uint8_t*>(h->ovf_list_dev + B);
-    {
-      const size_t half = B * sizeof(int32_t) + ((B + 63) / 64) * 64, pn = (B + 15) / 16 * 16;
-      for (int i = 0; i < 2; i++) {
-        h->perm_host[i] = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(h->ovf_list_host) + 2 * half) + i * pn;
-        h->perm_dev[i] = reinterpret_cast<int32_t*>(reinterpret_cast<uint8_t*>(h->ovf_list_dev) + 2 * half) + i * pn;
-      }
-      h->perm_next = -1; h->pend_perm = -1;
-    }
-    if (!getenv("MIR_EXACT_ONE_STREAM")) {  // (the side stream of exact_finish; MIR_EXACT_ONE_STREAM=1: everything on the step's stream)
-      int lo = 0, hi = 0;
-      (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-      hipStream_t st = nullptr;
-      hipEvent_t ev = nullptr;
-      HIPCHK(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, hi));
-      HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-      h->ovf_stream = st; h->ovf_event = ev;
-    }
-  }
-  // the list instantiation of the 16-lane kernel takes the deferred envs where the scene has the split closing forward kinematics (every
-  // free body a childless child of the world: the reference's scenes); MIR_EXACT_WAVE=1: the wave-per-env kernel takes them all (round 5)
-  h->exact_big = (h->hm.fk_free_leaf != 0 && !(getenv("MIR_EXACT_WAVE") && atoi(getenv("MIR_EXACT_WAVE")) != 0)) ? 1 : 0;
-  // (1, the default: when the caller spent at least MIR_EXACT_BIG_GAP microseconds -- 40 -- between the last mir_step_end and this
-  //  mir_step_begin: the two launches of such a step take a third more GPU time than the heavy phase's one -- rows through HBM, less
-  //  overlap of the two waves -- which a loop with nothing between its steps pays in full; 2: whenever the rows are there; 0: never)
-  h->big_on = (h->exact_big && on != 2 && h->ovf_stream) ? (getenv("MIR_EXACT_BIG") ? atoi(getenv("MIR_EXACT_BIG")) : 1) : 0;
-  h->big_gap_us = getenv("MIR_EXACT_BIG_GAP") ? atof(getenv("MIR_EXACT_BIG_GAP")) : 40.0;
-  h->big_lists = !(getenv("MIR_EXACT_BIG_LISTS") && atoi(getenv("MIR_EXACT_BIG_LISTS")) == 0);  // (0: the second half always as one launch for the whole batch)
-  h->big_side = !(getenv("MIR_EXACT_BIG_SIDE") && atoi(getenv("MIR_EXACT_BIG_SIDE")) == 0);  // (0, a test switch: the first-half launch on the step's stream)
-  h->t_end_us = 0.0;
-  h->bigmode = 0;
-  if (h->big_on && !h->main_event) {
-    DeviceGuard guard(h->device);
-    hipEvent_t ev = nullptr, ev2 = nullptr;
-    HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&ev2, hipEventDisableTiming));
-    h->main_event = ev; h->light_event = ev2;
-    const size_t nb = (((size_t)h->B + 3) / 4 * sizeof(uint32_t) + 63) / 64 * 64;
-    HIPCHK(hipHostMalloc((void**)&h->next_host, nb, hipHostMallocMapped | hipHostMallocCoherent));
-    memset(h->next_host, 0, nb);
-    HIPCHK(hipHostGetDevicePointer((void**)&h->next_dev, h->next_host, 0));
-  }
-  h->rt_ok = 0;
-  if (!h->xr_stats) {  // (mir_rollout_exact's lists and counters: see mir_scene.h)
-    DeviceGuard guard(h->device);
-    const size_t B = (size_t)h->B, bytes = 4 * sizeof(unsigned long long) + 16 * sizeof(int32_t) + 3 * B * sizeof(int32_t);
-    HIPCHK(hipMalloc((void**)&h->xr_stats, bytes));
-    HIPCHK(hipMemset(h->xr_stats, 0, bytes));
-    h->xr_count = reinterpret_cast<int32_t*>(h->xr_stats + 4);
-    h->xr_list = h->xr_count + 16;
-    h->xr_list2 = h->xr_list + B;
-    h->xr_start = h->xr_list2 + B;
-  }
-  if (h->big_on && !h->pre_big) {
-    DeviceGuard guard(h->device);
-    HIPCHK(hipMalloc((void**)&h->pre_big, (size_t)h->B * K48_STRIDE * sizeof(float)));
-    HIPCHK(hipMemset(h->pre_big, 0, (size_t)h->B * K48_STRIDE * sizeof(float)));
-  }
-  h->exact = on == 2 ? 2 : 1;
-  h->heavy = 0;
-  h->perm_next = -1; h->pend_perm = -1;
-  h->heavy_sort = !(getenv("MIR_EXACT_HEAVY_SORT") && atoi(getenv("MIR_EXACT_HEAVY_SORT")) == 0);
-  h->heavy_enter = (h->B + 15) / 16; h->heavy_leave = (h->B + 31) / 32;  // (6 % / 3 % of the batch)
-  if (const char* e = getenv("MIR_EXACT_HEAVY")) {
-    int a = 0, b = 0;
-    const int k = sscanf(e, "%d,%d", &a, &b);
-    if (k >= 1) { h->heavy_enter = a; h->heavy_leave = k >= 2 ? b : a / 2; }
-  }
-  if (on == 2) h->heavy_enter = 0;  // (the twin of the tests: every env on the list instantiation, every step)
-  return MIR_OK;
-}
-
-int mir_get_exact_contacts(MirHandle h) { return check(h) ? MIR_E_INVALID : h->exact; }
-
-int mir_get_exact_stats(MirHandle h, uint64_t* out4, int32_t reset) {
-  if (check(h) || !out4) return set_err(MIR_E_INVALID, "mir_get_exact_stats: null argument");
-  out4[0] = h->ex_steps; out4[1] = h->ex_ovf_steps; out4[2] = h->ex_ovf_envs; out4[3] = h->ex_ovf_max;
-  if (reset) h->ex_steps = h->ex_ovf_steps = h->ex_ovf_envs = h->ex_ovf_max = h->ex_big_envs = h->ex_wave_envs = h->ex_heavy_steps = h->ex_big_steps = 0;
-  return MIR_OK;
-}
-
-int mir_get_exact_route(MirHandle h, uint64_t* out2) {
-  if (check(h) || !out2) return set_err(MIR_E_INVALID, "mir_get_exact_route: null argument");
-  out2[0] = h->ex_big_envs; out2[1] = h->ex_wave_envs; out2[2] = h->ex_heavy_steps; out2[3] = h->ex_big_steps;
-  return MIR_OK;
-}
 /* debug aid (bench.py's roofline): n back-to-back launches of the rotated step kernel (what mir_step_begin launches in split mode 1)
  * cycling through n_actions action blocks of (B, nu) and without observation outputs, so that two events around the call time that kernel the way the fused one is
  * timed.  Advances the state by n steps. */
 extern "C" int mir_debug_rotated_launches(MirHandle h, const float* actions, int32_t n_actions, int32_t n, void* const* outputs, void* stream) {
   if (check(h)) return MIR_E_INVALID;
-  if (h->kernel != 16 || h->split_step != 1 || !h->hm.fk_free_leaf || h->exact) return set_err(MIR_E_INVALID, "mir_debug_rotated_launches: the scene does not use rotated launches (or exact contacts are on)");
+  if (h->kernel != 16 || h->split_step != 1 || !h->hm.fk_free_leaf || h->xc.on) return set_err(MIR_E_INVALID, "mir_debug_rotated_launches: the scene does not use rotated launches (or exact contacts are on)");
   DeviceGuard guard(h->device);
   if (!(h->pre_valid && h->pre_stream == stream)) {
     Outs f; f.action = actions; f.diag = false;
@@ -1271,7 +883,7 @@ extern "C" int mir_debug_rotated_launches(MirHandle h, const float* actions, int
  * nothing is handed to the host, no outputs).  It is the rollout launch without rows.  actions (n, B, nu). */
 extern "C" int mir_debug_resident_steps(MirHandle h, const float* actions, int32_t n, void* stream) {
   if (check(h) || !actions || n <= 0) return set_err(MIR_E_INVALID, "mir_debug_resident_steps: bad argument");
-  if (h->exact) return set_err(MIR_E_INVALID, "mir_debug_resident_steps: not available with exact contacts");
+  if (h->xc.on) return set_err(MIR_E_INVALID, "mir_debug_resident_steps: not available with exact contacts");
   DeviceGuard guard(h->device);
   Outs o;
   o.action = actions; o.n_steps = n; o.act_step = (long)h->B * h->nu; o.diag = false;
@@ -1335,7 +947,7 @@ int mir_get_early_mask(MirHandle h) { return check(h) ? MIR_E_INVALID : (h->no_e
 int mir_step_packed(MirHandle h, const float* action, float* rows, int32_t row_stride, void* stream) {
   if (check(h) || !rows) return set_err(MIR_E_INVALID, "mir_step_packed: null argument");
   if (row_stride < h->agent_dim + h->env_dim + 2) return set_err(MIR_E_INVALID, "mir_step_packed: row_stride too small");
-  if (h->exact) return set_err(MIR_E_INVALID, "mir_step_packed: not available with exact contacts (the step has to be closed on the host: mir_step_begin / mir_step_end)");
+  if (h->xc.on) return set_err(MIR_E_INVALID, "mir_step_packed: not available with exact contacts (the step has to be closed on the host: mir_step_begin / mir_step_end)");
   DeviceGuard guard(h->device);
   Outs o;
   o.action = action; o.rows = rows; o.row_stride = row_stride;
@@ -1346,7 +958,7 @@ int mir_rollout(MirHandle h, const float* actions, int32_t n_steps, float* rows,
   if (check(h) || !actions || !rows) return set_err(MIR_E_INVALID, "mir_rollout: null argument");
   if (n_steps <= 0) return MIR_OK;
   if (row_stride < h->agent_dim + h->env_dim + 2) return set_err(MIR_E_INVALID, "mir_rollout: row_stride too small");
-  if (h->exact) return set_err(MIR_E_INVALID, "mir_rollout: not available with exact contacts (every step has to be closed on the host)");
+  if (h->xc.on) return set_err(MIR_E_INVALID, "mir_rollout: not available with exact contacts (every step has to be closed on the host)");
   DeviceGuard guard(h->device);
   Outs o;
   o.action = actions; o.rows = rows; o.row_stride = row_stride; o.n_steps = n_steps;
@@ -1354,128 +966,6 @@ int mir_rollout(MirHandle h, const float* actions, int32_t n_steps, float* rows,
   return launch(h, o, stream);
 }
 
-/* Device-resident K-step rollout that keeps every contact point (mirigid.h: mir_rollout_exact).  A fixed chain on the caller's stream:
- *   memset of the two list counters;
- *   the one-wave step loop with hand-off (STEP_XR16) for the whole batch -- an env stays on it until its first step above the
- *     one-contact-per-lane capacity, then stores its state of that step's start and appends itself to list 1 (exact == 2: every env at
- *     step 0, the twin route of the tests);
- *   the three-contacts-per-lane step loop (STEP_XR48) over list 1 -- fixed grid, a workgroup past the list's device count exits at
- *     once -- each env from its own start step to the end of the call, which hands an env beyond 48 points or 16 candidate pairs on to
- *     list 2 (scenes whose host-closed route has no list instantiation: list 1 is list 2);
- *   the wave-per-env kernel in list mode over list 2, each env resuming at its own step (the 16-lane layout in and out);
- *   a one-thread kernel that folds list 1's count into the statistics.
- * No host read, no pinned memory, no host wait.  Every kernel of the chain runs the same step body as the route of mir_step_begin /
- * mir_step_end, so the bits are that route's (see mirigid.h for the one exception). */
-__global__ void k_xr_close(const int32_t* count, unsigned long long* stats) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    const unsigned long long n = (unsigned long long)count[0];
-    if (n > stats[2]) stats[2] = n;
-  }
-}
-
-static int rollout_exact(MirScene* h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, const AutoResetArgs& ar, void* stream, const char* who) {
-  if (h->pending) {  // (a step left open: closed first, as mir_reset does)
-    int rc = mir_step_end(h, nullptr);
-    if (rc != MIR_OK) return rc;
-  }
-  if (int rc = check_mask(h)) return rc;
-  if (!h->xr_stats) return set_err(MIR_E_INVALID, "%s: exact contacts were never switched on", who);
-  if (n_steps >= XR_TIER2) return set_err(MIR_E_INVALID, "%s: n_steps must be below 2^20", who);
-  DeviceGuard guard(h->device);
-  // (the side-stream launches of an earlier host-closed overflow step own the state and the scratch rows until ovf_event: mir_step_begin)
-  if (h->ovf_event_live && h->ovf_waited_stream != stream) {
-    HIPCHK(hipStreamWaitEvent((hipStream_t)stream, (hipEvent_t)h->ovf_event, 0));
-    h->ovf_waited_stream = stream;
-  }
-  h->pre_valid = 0;
-  h->poses_current = 0;
-  h->state_version++;
-  h->xr_calls++;
-  const hipStream_t st = (hipStream_t)stream;
-  HIPCHK(hipMemsetAsync(h->xr_count, 0, 2 * sizeof(int32_t), st));
-  StepArgs a;
-  memset(&a, 0, sizeof a);
-  a.model = h->dm;
-  a.qpos = h->qpos; a.qvel = h->qvel; a.target = h->target; a.qacc_ws = h->qacc_ws;
-  a.diag = h->diag_on ? h->diag : nullptr;
-  a.early_stats = h->early_stats; a.no_early_mask = 1;
-  a.term_wstride = h->term_wstride;
-  a.B = h->B; a.qst = h->hm.qstride; a.nu = h->hm.nu;
-  a.features = (h->hm.has_convex ? FEAT_CONVEX : 0) | (h->hm.use_sap ? FEAT_CONVEX | FEAT_SAP : 0) | (h->spec_pick ? FEAT_SPEC : 0);
-  a.row_stride = row_stride; a.mode = 0;
-  a.ar = ar;
-  a.exact = h->exact;
-  // (without the list instantiation the hand-off of (1) goes to list 2 directly: the step index it records carries no tier bit, which
-  //  only STEP_XR48 reads)
-  a.xr_list = h->exact_big ? h->xr_list : h->xr_list2; a.xr_count = h->exact_big ? h->xr_count : h->xr_count + 1;
-  a.xr_list2 = h->xr_list2; a.xr_count2 = h->xr_count + 1;
-  a.xr_start = h->xr_start; a.xr_stats = h->xr_stats;
-  const long as = (long)h->B * h->nu, rs = (long)h->B * row_stride;
-  // (1) the whole batch on the one-wave step loop, every env until its hand-off
-  a.kind = STEP_XR16; a.action = actions; a.rows = rows; a.n_steps = n_steps; a.act_step = as; a.rows_step = rs;
-  int rc = mir_launch_step(&a, st);
-  if (rc != 0) return hip_fail((hipError_t)rc, who);
-  // (2) list 1 on the three-contacts-per-lane step loop, each env from its own step (scenes whose host-closed route sends the deferred
-  //     envs to the wave-per-env kernel instead -- no split closing FK, or MIR_EXACT_WAVE -- hand them straight to list 2 in (1))
-  if (h->exact_big) {
-    a.kind = STEP_XR48; a.env_list = h->xr_list; a.n_steps = n_steps; a.action = actions; a.rows = rows; a.act_step = as; a.rows_step = rs;
-    rc = mir_launch_step(&a, st);
-    if (rc != 0) return hip_fail((hipError_t)rc, who);
-  }
-  // (3) list 2 on the wave-per-env kernel, each env from its own step to the end of the call
-  StepArgs64 w;
-  memset(&w, 0, sizeof w);
-  w.model = h->dm64;
-  w.qpos = h->qpos; w.qvel = h->qvel; w.target = h->target; w.qacc_ws = h->qacc_ws;
-  w.diag = h->diag_on ? h->diag : nullptr;
-  w.bad_count = h->early_stats;
-  w.B = h->B; w.nu = h->hm64.nu; w.convex = h->hm64.has_convex;
-  w.action = actions; w.rows = rows; w.row_stride = row_stride; w.act_step = as; w.rows_step = rs; w.ar = ar;
-  w.mode = 0; w.n_steps = n_steps;
-  w.env_list = h->xr_list2; w.lay16_qst = h->hm.qstride;
-  w.list_count = h->xr_count + 1; w.env_start = h->xr_start; w.xr_stats = h->xr_stats;
-  rc = mir_launch_step64(&w, st);
-  if (rc != 0) return hip_fail((hipError_t)rc, who);
-  hipLaunchKernelGGL(k_xr_close, dim3(1), dim3(64), 0, st, h->xr_count, h->xr_stats);
-  HIPCHK(hipGetLastError());
-  return MIR_OK;
-}
-
-int mir_rollout_exact(MirHandle h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, void* stream) {
-  if (check(h) || !actions || !rows) return set_err(MIR_E_INVALID, "mir_rollout_exact: null argument");
-  if (h->kernel != 16) return set_err(MIR_E_INVALID, "mir_rollout_exact: the scene runs on the wave-per-env kernel (48 points, nothing to switch): use mir_rollout");
-  if (row_stride < h->agent_dim + h->env_dim + 2) return set_err(MIR_E_INVALID, "mir_rollout_exact: row_stride too small");
-  if (!h->exact) return mir_rollout(h, actions, n_steps, rows, row_stride, stream);
-  if (n_steps <= 0) return MIR_OK;
-  return rollout_exact(h, actions, n_steps, rows, row_stride, AutoResetArgs{nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0}, stream, "mir_rollout_exact");
-}
-
-int mir_rollout_autoreset_exact(MirHandle h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, int32_t* episode_len,
-                                int32_t max_len, const float* spawn_pool, int32_t pool_len, int32_t* cursor, const float* obj_quat,
-                                const float* arm_qpos, void* stream) {
-  if (check(h) || !actions || !rows) return set_err(MIR_E_INVALID, "mir_rollout_autoreset_exact: null argument");
-  if (!episode_len || !spawn_pool || !cursor || !obj_quat || !arm_qpos || pool_len <= 0) return set_err(MIR_E_INVALID, "mir_rollout_autoreset_exact: null argument");
-  if (h->kernel != 16) return set_err(MIR_E_INVALID, "mir_rollout_autoreset_exact: the scene runs on the wave-per-env kernel (48 points, nothing to switch): use mir_rollout_autoreset");
-  if (row_stride < h->agent_dim + h->env_dim + 3) return set_err(MIR_E_INVALID, "mir_rollout_autoreset_exact: row_stride too small (needs the truncated column)");
-  if (!h->exact) return mir_rollout_autoreset(h, actions, n_steps, rows, row_stride, episode_len, max_len, spawn_pool, pool_len, cursor, obj_quat, arm_qpos, stream);
-  if (n_steps <= 0) return MIR_OK;
-  return rollout_exact(h, actions, n_steps, rows, row_stride, AutoResetArgs{episode_len, cursor, spawn_pool, obj_quat, arm_qpos, pool_len, max_len}, stream,
-                       "mir_rollout_autoreset_exact");
-}
-
-int mir_get_rollout_exact_stats(MirHandle h, uint64_t* out4, int32_t reset) {
-  if (check(h) || !out4) return set_err(MIR_E_INVALID, "mir_get_rollout_exact_stats: null argument");
-  unsigned long long dev[4] = {0, 0, 0, 0};
-  if (h->xr_stats) {  // (synchronises the device: the counters are written by the launches)
-    DeviceGuard guard(h->device);
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(dev, h->xr_stats, sizeof dev, hipMemcpyDeviceToHost));
-    if (reset) HIPCHK(hipMemset(h->xr_stats, 0, sizeof dev));
-  }
-  out4[0] = h->xr_calls; out4[1] = dev[0]; out4[2] = dev[1]; out4[3] = dev[2];
-  if (reset) h->xr_calls = 0;
-  return MIR_OK;
-}
 
 int mir_rollout_autoreset(MirHandle h, const float* actions, int32_t n_steps, float* rows, int32_t row_stride, int32_t* episode_len,
                           int32_t max_len, const float* spawn_pool, int32_t pool_len, int32_t* cursor, const float* obj_quat,
@@ -1484,7 +974,7 @@ int mir_rollout_autoreset(MirHandle h, const float* actions, int32_t n_steps, fl
   if (!episode_len || !spawn_pool || !cursor || !obj_quat || !arm_qpos || pool_len <= 0) return set_err(MIR_E_INVALID, "mir_rollout_autoreset: null argument");
   if (n_steps <= 0) return MIR_OK;
   if (row_stride < h->agent_dim + h->env_dim + 3) return set_err(MIR_E_INVALID, "mir_rollout_autoreset: row_stride too small (needs the truncated column)");
-  if (h->exact) return set_err(MIR_E_INVALID, "mir_rollout_autoreset: not available with exact contacts (every step has to be closed on the host)");
+  if (h->xc.on) return set_err(MIR_E_INVALID, "mir_rollout_autoreset: not available with exact contacts (every step has to be closed on the host)");
   DeviceGuard guard(h->device);
   Outs o;
   o.action = actions; o.rows = rows; o.row_stride = row_stride; o.n_steps = n_steps;

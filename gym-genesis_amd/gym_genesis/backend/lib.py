@@ -755,7 +755,8 @@ class MirScene(StepHelpers):
         self._check(self.lib.mir_set_exact_contacts(self.h, C.byref(self.spec), 2 if on == "all" else (1 if on else 0)))
 
     def exact_route(self) -> dict:
-        """mir_get_exact_route: deferred env-steps handed to the list instantiation / env-steps stepped by the wave-per-env kernel."""
+        """mir_get_exact_route: deferred env-steps handed to the list instantiation / env-steps stepped by the wave-per-env kernel /
+        heavy steps / two-launch steps of overflow runs."""
         out = (C.c_uint64 * 4)()
         self._check(self.lib.mir_get_exact_route(self.h, out))
         return {"list_env_steps": int(out[0]), "wave_env_steps": int(out[1]), "heavy_steps": int(out[2]), "big_steps": int(out[3])}

@@ -298,6 +298,52 @@ def test_heavy_phase_from_the_first_overflow_on_and_a_batch_that_is_not_a_multip
     assert n_def > 20 and st["overflow_env_steps"] == n_def and r["wave_env_steps"] == 0 and (r["heavy_steps"] > 3 if route == "heavy" else r["big_steps"] > 3), (n_def, st, r)
 
 
+ROUTE_SETTINGS = {   # (settings under which the route of a step does not depend on the wall clock)
+    "list_launches": {"MIR_EXACT_BIG": "0"},
+    "heavy_from_the_first_overflow": {"MIR_EXACT_BIG": "0", "MIR_EXACT_HEAVY": "1,1"},
+    "two_launches_always": {"MIR_EXACT_BIG": "2"},
+}
+
+
+def _route_counts(spec):
+    """The 30-env scripted grasp (the last workgroup holds two envs) through step_begin / step_end, the host synchronised behind every
+    step; the environment is the caller's.  Returns the two counter dictionaries of the handle."""
+    from gym_genesis.backend.lib import MirScene
+
+    n = 30
+    sc = MirScene(spec, n)
+    sc.set_exact_contacts(True)
+    pos, acts = _grasp_workload(32)
+    pos, acts = pos[:n], acts[:, :n]
+    sc.reset(pos, np.tile(np.array([0, 0, 0, 1], np.float32), (n, 1)), np.tile(HOME, (n, 1)))
+    bufs = _bufs(sc)
+    dacts = torch.as_tensor(acts, device=sc.device)
+    sc.exact_stats(reset=True)
+    for t in range(acts.shape[0]):
+        sc.step_begin(dacts[t], *bufs)
+        sc.step_end()
+        torch.cuda.synchronize()
+    return {"exact_stats": sc.exact_stats(), "exact_route": sc.exact_route()}
+
+
+@pytest.mark.parametrize("setting", sorted(ROUTE_SETTINGS))
+def test_route_counters_are_the_parents(franka_spec, monkeypatch, setting):
+    """Every route computes the same bits, so the twin tests above cannot see WHICH route a step took; a wrong one shows only as a slower
+    step.  This pins it: the full counter dictionaries of the 30-env grasp equal tests/golden/exact_route_counts.json, which was recorded
+    with this same loop on the library of the commit BEFORE the routing decisions moved into csrc/mir_route.h (two runs per setting, equal
+    in every counter, so none is left out)."""
+    monkeypatch.setenv("MIR_SPLIT_STEP", "1")
+    for k in ("MIR_EXACT_BIG", "MIR_EXACT_HEAVY", "MIR_EXACT_BIG_GAP", "MIR_EXACT_BIG_LISTS", "MIR_EXACT_BIG_SIDE", "MIR_EXACT_HEAVY_SORT",
+              "MIR_EXACT_WAVE", "MIR_EXACT_ONE_STREAM"):
+        monkeypatch.delenv(k, raising=False)
+    for k, v in ROUTE_SETTINGS[setting].items():
+        monkeypatch.setenv(k, v)
+    want = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "exact_route_counts.json")))[setting]
+    got = _route_counts(franka_spec)
+    print(setting, got)
+    assert got == want
+
+
 @pytest.mark.parametrize("big", [False, True])
 def test_so101_scene_with_a_low_capacity_random_actions_every_env_equals_its_twin_bit_for_bit(monkeypatch, big):
     """The other articulation (BASELINE configs[3]) and another way to overflow: the SO-101 pick scene with the capacity of the
