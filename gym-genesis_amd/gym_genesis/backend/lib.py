@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirKinQuery, MirRayQuery, MirSceneSpec, MirVisualSpec, make_kin_query, make_ray_query  # noqa: F401
+from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirVisualSpec, make_dyn_query, make_kin_query, make_ray_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -128,6 +128,9 @@ def load_library() -> C.CDLL:
     lib.mir_kin_query_sizeof.restype = C.c_int
     lib.mir_link_kinematics.argtypes = [vp, C.POINTER(MirKinQuery), vp, i32, vp, vp, vp, vp, vp]
     lib.mir_link_kinematics.restype = C.c_int
+    lib.mir_dyn_query_sizeof.restype = C.c_int
+    lib.mir_dynamics.argtypes = [vp, C.POINTER(MirDynQuery), vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_dynamics.restype = C.c_int
     lib.mir_ray_query_sizeof.restype = C.c_int
     lib.mir_raycast.argtypes = [vp, C.POINTER(MirRayQuery), vp, vp, i32, vp, vp, vp, vp, vp]
     lib.mir_raycast.restype = C.c_int
@@ -139,6 +142,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec (rebuild the library)")
     if lib.mir_kin_query_sizeof() != C.sizeof(MirKinQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirKinQuery (rebuild the library)")
+    if lib.mir_dyn_query_sizeof() != C.sizeof(MirDynQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirDynQuery (rebuild the library)")
     if lib.mir_ray_query_sizeof() != C.sizeof(MirRayQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRayQuery (rebuild the library)")
     _lib = lib
@@ -682,6 +687,48 @@ class MirScene(StepHelpers):
         self._check(self.lib.mir_link_kinematics(self.h, C.byref(q), _ptr(idx), R, _ptr(out.get("pos")), _ptr(out.get("quat")), _ptr(out.get("vel")),
                                                  _ptr(out.get("jac")), self._stream()))
         self.link_kinematics_launches = self.__dict__.get("link_kinematics_launches", 0) + 1
+        return out
+
+    def dynamics(self, env_idx=None, dof0: int = 0, n_dofs: Optional[int] = None, qpos=None, qvel=None, qacc=None, mass: bool = True,
+                 bias: bool = True, gravity: bool = False, tau: bool = False, ctrl_force: bool = False) -> dict:
+        """mir_dynamics: joint-space dynamics of the scene dofs [dof0, dof0 + n_dofs) (n_dofs None: up to nv) in ONE launch of a kernel
+        of its own, for the envs `env_idx` (int64 device tensor, any order, repeats allowed; None: all envs).  With R rows and n dofs:
+        mass (R,n,n) = the composite-rigid-body mass matrix with armature on the diagonal, bias (R,n) = Coriolis + centrifugal + gravity
+        forces (M qacc + bias = applied torque), gravity (R,n) = bias at qvel = 0, tau (R,n) = the window of M qacc + bias for the
+        full-length `qacc` (R,nv), ctrl_force (R,n) = the clamped PD torque of the current targets.  `qpos` (R,nq) / `qvel` (R,nv), in
+        the layout of get_state(), replace the rows' current state for this evaluation only.  Only the outputs asked for are computed
+        and returned: fresh device tensors on the current stream.  The read changes nothing."""
+        nd = self.nv - int(dof0) if n_dofs is None else int(n_dofs)
+        q = make_dyn_query(dof0, nd)
+        idx = None
+        if env_idx is not None:
+            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        R = self.num_envs if idx is None else int(idx.numel())
+
+        def rows(t, width, name):
+            if t is None:
+                return None
+            t = torch.as_tensor(t, device=self.device).to(torch.float32).contiguous()
+            if tuple(t.shape) != (R, width):
+                raise ValueError(f"{name} must be ({R}, {width}), got {tuple(t.shape)}")
+            return t
+
+        qpos, qvel, qacc = rows(qpos, self.nq, "qpos"), rows(qvel, self.nv, "qvel"), rows(qacc, self.nv, "qacc")
+        if tau and qacc is None:
+            raise ValueError("tau needs qacc")
+        n = max(nd, 0)
+        new = lambda *shape: torch.empty((R, *shape), dtype=torch.float32, device=self.device)  # noqa: E731
+        out = {}
+        if mass:
+            out["mass"] = new(n, n)
+        for name, want in (("bias", bias), ("gravity", gravity), ("tau", tau), ("ctrl_force", ctrl_force)):
+            if want:
+                out[name] = new(n)
+        self._check(self.lib.mir_dynamics(self.h, C.byref(q), _ptr(idx), R, _ptr(qpos), _ptr(qvel), _ptr(qacc), _ptr(out.get("mass")),
+                                          _ptr(out.get("bias")), _ptr(out.get("gravity")), _ptr(out.get("tau")), _ptr(out.get("ctrl_force")),
+                                          self._stream()))
+        if out and R > 0 and n > 0:
+            self.dynamics_launches = self.__dict__.get("dynamics_launches", 0) + 1
         return out
 
     def raycast(self, dirs, link: int = 0, pos_offset=(0.0, 0.0, 0.0), quat_offset=(1.0, 0.0, 0.0, 0.0), min_range: float = 0.0,

@@ -231,6 +231,30 @@ def make_kin_query(links: Sequence[int], local_points=None, dof0: int = 0, n_dof
     q.dof0, q.n_dofs = int(dof0), int(n_dofs)
     return q
 
+
+class MirDynQuery(C.Structure):
+    """include/mirigid.h: MirDynQuery (mir_dynamics)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("dof0", C.c_int32),
+        ("n_dofs", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
+def make_dyn_query(dof0: int = 0, n_dofs: int = 0, flags: int = 0) -> MirDynQuery:
+    """The window of scene dofs [dof0, dof0 + n_dofs) of a dynamics query; no flag bit is defined yet."""
+    dof0, n_dofs, flags = int(dof0), int(n_dofs), int(flags)
+    if dof0 < 0 or n_dofs < 0 or dof0 + n_dofs > MIR_MAX_DOF:
+        raise ValueError(f"dynamics window [{dof0}, {dof0 + n_dofs}) outside [0, {MIR_MAX_DOF}]")
+    if flags != 0:
+        raise ValueError(f"unknown MirDynQuery flag bits {flags:#x}")
+    q = MirDynQuery()
+    q.struct_size = C.sizeof(MirDynQuery)
+    q.dof0, q.n_dofs, q.flags = dof0, n_dofs, flags
+    return q
+
+
 MIR_RAY_POINTS_WORLD = 1  # MirRayQuery.flags: points / normal in world axes (include/mirigid.h)
 
 

@@ -229,6 +229,86 @@ class EntityView:
         """(B, n_links, 3): world angular velocity of each link"""
         return self.links_kinematics(links_idx_local, envs_idx, pos=False, quat=False)["ang"]
 
+    # ---- rigid-body dynamics queries (MirScene.dynamics / mir_dynamics): one launch per call, for this entity's dofs and the envs asked
+    # for only.  get_mass_mat and get_dofs_control_force are Genesis names (RigidEntity); get_dofs_bias_force, get_dofs_gravity_force and
+    # inverse_dynamics are this package's own, and parity with Genesis is unpinned for all of them (the reference's tasks call none).
+    def _dynamics(self, envs_idx, dofs_idx_local, name: str, **kw) -> torch.Tensor:
+        fn = getattr(self._mir, "dynamics", None)
+        if fn is None:
+            raise NotImplementedError("this scene has no dynamics queries (MirScene.dynamics / mir_dynamics)")
+        cols = self._jac_dofs()
+        run = bool(cols) and cols == list(range(cols[0], cols[0] + len(cols)))
+        win = dict(dof0=cols[0], n_dofs=len(cols)) if run else {}
+        flags = dict(mass=False, bias=False, gravity=False, tau=False, ctrl_force=False)
+        flags[name] = True
+        out = fn(env_idx=_env_index(self._mir, envs_idx), **win, **flags, **kw)[name]
+        if not run:
+            ix = torch.as_tensor(cols, dtype=torch.long, device=out.device)
+            out = out.index_select(1, ix)
+            if name == "mass":
+                out = out.index_select(2, ix)
+        if dofs_idx_local is not None:
+            out = out[:, [int(i) for i in np.asarray(dofs_idx_local).ravel()]]
+        return out.contiguous()
+
+    def get_mass_mat(self, envs_idx=None, decompose: bool = False) -> torch.Tensor:
+        """``entity.get_mass_mat()`` (a Genesis name) -> (B, n, n): the joint-space mass matrix of this entity's dofs in its dof order,
+        by the composite-rigid-body algorithm, with the dofs' armature on the diagonal and without the integrator's dt (damping + kv)."""
+        if decompose:
+            raise NotImplementedError("decompose")
+        return self._dynamics(envs_idx, None, "mass")
+
+    def get_dofs_control_force(self, dofs_idx_local=None, envs_idx=None) -> torch.Tensor:
+        """``entity.get_dofs_control_force()`` (a Genesis name) -> (B, n): clamp(kp (target - q) - kv qvel, force range) of the
+        position-controlled dofs, 0 for the others: the PD torque the next step applies if the targets stay as they are."""
+        return self._dynamics(envs_idx, dofs_idx_local, "ctrl_force")
+
+    def get_dofs_bias_force(self, dofs_idx_local=None, envs_idx=None) -> torch.Tensor:
+        """(B, n): Coriolis, centrifugal and gravity forces c(q, qvel) of M qacc + c = applied torque.  This package's own name:
+        parity with Genesis is unpinned."""
+        return self._dynamics(envs_idx, dofs_idx_local, "bias")
+
+    def get_dofs_gravity_force(self, dofs_idx_local=None, envs_idx=None) -> torch.Tensor:
+        """(B, n): the bias force at qvel = 0, the torque that holds the pose at rest (gravity compensation).  This package's own name:
+        parity with Genesis is unpinned."""
+        return self._dynamics(envs_idx, dofs_idx_local, "gravity")
+
+    def inverse_dynamics(self, qacc, qpos=None, qvel=None, dofs_idx_local=None, envs_idx=None) -> torch.Tensor:
+        """(B, n): tau = M qacc + c(q, qvel) for the acceleration `qacc` (B, n) of this entity's dofs, at `qpos` / `qvel` (B, n) over
+        this entity's dofs when given (the way inverse_kinematics takes init_qpos), else at the current state.  The dofs of other
+        entities are at zero acceleration and in their current state; passive damping and PD torques are not included.  `qpos` is
+        taken for entities with scalar joints only (the robot): for an entity without them (a free cube, whose qpos row is seven wide
+        where it has six dofs) it raises NotImplementedError; `qvel` and `qacc` work for every entity.  This package's own name: parity
+        with Genesis is unpinned."""
+        mir, cols = self._mir, self._jac_dofs()
+        idx = _env_index(mir, envs_idx)
+        R = mir.num_envs if idx is None else int(idx.numel())
+        ct = torch.as_tensor(cols, dtype=torch.long, device=mir.device)
+
+        def entity_rows(t, name):
+            t = torch.as_tensor(t, device=mir.device).to(torch.float32).reshape(R, -1)
+            if t.shape[1] != len(cols):
+                raise ValueError(f"{name} must be ({R}, {len(cols)}) over this entity's dofs, got {tuple(t.shape)}")
+            return t
+
+        full_acc = torch.zeros((R, mir.nv), dtype=torch.float32, device=mir.device)
+        full_acc[:, ct] = entity_rows(qacc, "qacc")
+        kw = dict(qacc=full_acc)
+        if qpos is not None or qvel is not None:
+            state = mir.get_state()
+            if qpos is not None:
+                if not self.dof_idx:
+                    raise NotImplementedError("inverse_dynamics: qpos override of an entity without scalar joints")
+                assert len(self._qcols) == len(cols), "an entity with named dofs has one qpos column per dof"
+                full = _rows(state[0], idx).clone()
+                full[:, torch.as_tensor(self._qcols, dtype=torch.long, device=mir.device)] = entity_rows(qpos, "qpos")
+                kw["qpos"] = full
+            if qvel is not None:
+                full = _rows(state[1], idx).clone()
+                full[:, ct] = entity_rows(qvel, "qvel")
+                kw["qvel"] = full
+        return self._dynamics(idx, dofs_idx_local, "tau", **kw)
+
     def get_link(self, name: str) -> LinkView:
         return LinkView(self._mir, self._b.body_index(name), name)
 

@@ -481,6 +481,49 @@ int mir_link_kinematics(MirHandle h, const MirKinQuery* q, const int64_t* env_id
                         float* pos /* (R, L, 3) */, float* quat /* (R, L, 4) wxyz */, float* vel /* (R, L, 6) lin, ang */,
                         float* jac /* (R, L, 6, n_dofs) */, void* stream);
 
+/* ---- rigid-body dynamics queries: mass matrix, bias forces, inverse dynamics --------------------------------
+ * entity.get_mass_mat() / entity.get_dofs_control_force() of Genesis (RigidEntity), and with them gravity compensation and the
+ * feed-forward torque tau = M qacc + c along a planned trajectory: beside the Jacobian of mir_link_kinematics, the objects that
+ * operational-space and impedance controllers are written on.  ONE launch of a kernel of its own for a WINDOW of scene dofs of a LIST of
+ * envs: it reads qpos / qvel / the PD targets and the compiled model and writes only its outputs (mir_forward, the other way to M and
+ * qfrc_bias, runs the step kernel with collision, constraint rows and the Newton solve over every env and returns all nv x nv).
+ *   R = n_rows, or num_envs when env_idx is NULL; row k belongs to env env_idx[k] (int64, device; repeats and any order allowed; an
+ *   index outside the batch is clamped as in mir_link_kinematics).  n = q->n_dofs; the window is the scene dofs [dof0, dof0 + n).
+ * State overrides: qpos (R, nq) and / or qvel (R, nv), in the public layout of mir_get_state; row k replaces the current state of env
+ * env_idx[k] for this evaluation only (a free joint's quaternion is normalised as the forward kinematics does).  What is not
+ * overridden comes from the current state of env env_idx[k]; the PD targets always do.
+ * Definitions (the oracle's conventions: oracle/orc_rigid.c orc_crb, orc_rne, orc_smooth; MIR_JNT_FREE above for the free joint --
+ * qvel = world linear velocity of the body origin, then world angular velocity; generalized forces are dual to that qvel):
+ *   M          (R, n, n) row-major: the window block of the joint-space inertia by the composite-rigid-body algorithm, WITH the dofs'
+ *              armature on the diagonal and WITHOUT the dt (damping + kv) the implicit integrator adds for its own solve.  Symmetric,
+ *              both triangles written; entries that couple different kinematic trees are exact zeros (written, not left as they were).
+ *   bias       (R, n): recursive Newton-Euler at qacc = 0 with gravity: Coriolis, centrifugal and gravity forces, on the LEFT of
+ *              M qacc + bias = tau_applied.
+ *   gravity    (R, n): bias evaluated at qvel = 0: the torque that holds the pose at rest.
+ *   tau        (R, n): the window of M_full qacc + bias for the full-length qacc (R, nv): inverse dynamics.  Passive damping and the
+ *              PD torques are not in it.
+ *   ctrl_force (R, n): clamp(kp (target - q) - kv qvel, force range) for MIR_CTRL_POSITION dofs, 0 for the others: the PD torque the
+ *              next step applies if the targets stay as they are.
+ * Every output is nullable and written only when asked for; all five NULL, or R == 0, or n == 0: MIR_OK without a launch.
+ * A read changes nothing: state, targets, warm start, state version, pose cache, diagnostics, counters and the scratch row of a split
+ * step stay as they are, and the steps around it are bit for bit those of a run without it.
+ * MIR_E_INVALID: a NULL handle or query, struct_size != sizeof(MirDynQuery), a window outside [0, nv], an unknown flag bit, tau without
+ * qacc, a free joint that is not the root of its tree, a call while a mir_step_begin is open (the rule of mir_contact_forces).
+ * MIR_E_CAPACITY: R x n x n does not fit 2^31 - 1; a
+ * kinematic tree of more than 16 bodies or 15 dofs, or more than 20 trees with dofs (neither compiler produces such a scene today).
+ * None of them launches anything.  (An added struct and entry point: MIR_VERSION and every other struct stay as they are.) */
+typedef struct MirDynQuery {
+  int32_t struct_size;   /* = sizeof(MirDynQuery) */
+  int32_t dof0, n_dofs;  /* window of scene dofs [dof0, dof0 + n_dofs) */
+  uint32_t flags;        /* 0; unknown bits are MIR_E_INVALID */
+} MirDynQuery;
+int mir_dyn_query_sizeof(void);
+int mir_dynamics(MirHandle h, const MirDynQuery* q, const int64_t* env_idx /* device, nullable */, int32_t n_rows,
+                 const float* qpos /* (R, nq) device, nullable: evaluate here instead of at the current state */,
+                 const float* qvel /* (R, nv) nullable, likewise */, const float* qacc /* (R, nv) nullable; needed for tau only */,
+                 float* M /* (R, n_dofs, n_dofs) */, float* bias /* (R, n_dofs) */, float* gravity /* (R, n_dofs) */,
+                 float* tau /* (R, n_dofs) */, float* ctrl_force /* (R, n_dofs) */, void* stream);
+
 /* ---- range sensing: batched ray casts ------------------------------------------------------------------
  * scene.add_sensor(gs.sensors.Lidar / Raycaster / DepthCamera(...)) + sensor.read() -> points, distances of Genesis (parity with
  * Genesis unpinned: the reference's tasks cast no rays and the package is not in the reference tree; the names follow its sensor API
