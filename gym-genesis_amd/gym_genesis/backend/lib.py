@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirVisualSpec, make_dyn_query, make_kin_query, make_ray_query  # noqa: F401
+from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirAccQuery, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirVisualSpec, make_acc_query, make_dyn_query, make_kin_query, make_ray_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -128,6 +128,9 @@ def load_library() -> C.CDLL:
     lib.mir_kin_query_sizeof.restype = C.c_int
     lib.mir_link_kinematics.argtypes = [vp, C.POINTER(MirKinQuery), vp, i32, vp, vp, vp, vp, vp]
     lib.mir_link_kinematics.restype = C.c_int
+    lib.mir_acc_query_sizeof.restype = C.c_int
+    lib.mir_link_accelerations.argtypes = [vp, C.POINTER(MirAccQuery), vp, i32, vp, vp, vp, vp, vp]
+    lib.mir_link_accelerations.restype = C.c_int
     lib.mir_dyn_query_sizeof.restype = C.c_int
     lib.mir_dynamics.argtypes = [vp, C.POINTER(MirDynQuery), vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_dynamics.restype = C.c_int
@@ -142,6 +145,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec (rebuild the library)")
     if lib.mir_kin_query_sizeof() != C.sizeof(MirKinQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirKinQuery (rebuild the library)")
+    if lib.mir_acc_query_sizeof() != C.sizeof(MirAccQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirAccQuery (rebuild the library)")
     if lib.mir_dyn_query_sizeof() != C.sizeof(MirDynQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirDynQuery (rebuild the library)")
     if lib.mir_ray_query_sizeof() != C.sizeof(MirRayQuery):
@@ -687,6 +692,43 @@ class MirScene(StepHelpers):
         self._check(self.lib.mir_link_kinematics(self.h, C.byref(q), _ptr(idx), R, _ptr(out.get("pos")), _ptr(out.get("quat")), _ptr(out.get("vel")),
                                                  _ptr(out.get("jac")), self._stream()))
         self.link_kinematics_launches = self.__dict__.get("link_kinematics_launches", 0) + 1
+        return out
+
+    def link_accelerations(self, links, local_points=None, quat_offsets=None, env_idx=None, qacc=None, acc: bool = True,
+                           bias_acc: bool = False, imu: bool = False) -> dict:
+        """mir_link_accelerations: world accelerations of the links `links` (body indices of the spec, repeats allowed) in ONE launch of a
+        kernel of its own, for the envs `env_idx` (int64 device tensor, any order, repeats allowed; None: all envs).  With p = the link's
+        origin + R_link local_point (local_points (3,) or (n_links, 3); None: the origins), R rows and L links:
+        acc (R,L,6) = classical world linear acceleration of the material point p, then the link's world angular acceleration
+        (J qacc + Jdot qvel with the J of link_kinematics); bias_acc (R,L,6) = the same at qacc = 0 (Jdot qvel); imu (R,L,6) = what an
+        accelerometer and a gyro at p with the axes R_link R(quat_offsets) read: R_s^T (acc - gravity), R_s^T w (quat_offsets wxyz, (4,) or
+        (n_links, 4); None: the link's axes).  `qacc` (R,nv), in the dof order of get_state(), is used as given; None: the acceleration
+        the next step applies if the targets stay as they are (forward(), gathered to the rows; the convention of contact_forces) -- taken
+        only when acc or imu is asked for.  Only the outputs asked for are computed and returned: fresh device tensors on the current
+        stream.  The read changes nothing (with qacc=None: nothing that a bare forward() does not)."""
+        q = make_acc_query(links, local_points, quat_offsets)
+        idx = None
+        if env_idx is not None:
+            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        R, L = (self.num_envs if idx is None else int(idx.numel())), q.n_links
+        if acc or imu:
+            if qacc is None:
+                qacc = self.forward()[3]
+                if idx is not None:
+                    qacc = qacc.index_select(0, idx.clamp(0, self.num_envs - 1))   # (the kernel clamps the same way)
+            qacc = torch.as_tensor(qacc, device=self.device).to(torch.float32).contiguous()
+            if tuple(qacc.shape) != (R, self.nv):
+                raise ValueError(f"qacc must be ({R}, {self.nv}), got {tuple(qacc.shape)}")
+        else:
+            qacc = None
+        out = {}
+        for name, want in (("acc", acc), ("bias_acc", bias_acc), ("imu", imu)):
+            if want:
+                out[name] = torch.empty((R, L, 6), dtype=torch.float32, device=self.device)
+        self._check(self.lib.mir_link_accelerations(self.h, C.byref(q), _ptr(idx), R, _ptr(qacc), _ptr(out.get("acc")), _ptr(out.get("bias_acc")),
+                                                    _ptr(out.get("imu")), self._stream()))
+        if out and R > 0:
+            self.link_accelerations_launches = self.__dict__.get("link_accelerations_launches", 0) + 1
         return out
 
     def dynamics(self, env_idx=None, dof0: int = 0, n_dofs: Optional[int] = None, qpos=None, qvel=None, qacc=None, mass: bool = True,

@@ -232,6 +232,52 @@ def make_kin_query(links: Sequence[int], local_points=None, dof0: int = 0, n_dof
     return q
 
 
+class MirAccQuery(C.Structure):
+    """include/mirigid.h: MirAccQuery (mir_link_accelerations)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_links", C.c_int32),
+        ("link_body", C.c_int32 * MIR_MAX_BODY),
+        ("local_point", (C.c_float * 3) * MIR_MAX_BODY),
+        ("quat_offset", (C.c_float * 4) * MIR_MAX_BODY),
+        ("flags", C.c_uint32),
+    ]
+
+
+def _per_link(values, n_links: int, width: int, name: str) -> list:
+    """one row of `width` floats for every link, or one per link -> n_links rows"""
+    rows = values.tolist() if hasattr(values, "tolist") else list(values)
+    if rows and not isinstance(rows[0], (list, tuple)):
+        rows = [rows] * n_links
+    rows = [[float(v) for v in r] for r in rows]
+    if len(rows) != n_links or any(len(r) != width for r in rows):
+        raise ValueError(f"{name} must be ({width},) or (n_links, {width})")
+    return rows
+
+
+def make_acc_query(links: Sequence[int], local_points=None, quat_offsets=None, flags: int = 0) -> MirAccQuery:
+    """links: body indices of the spec; local_points: one point (3,) for every link, or one per link (n_links, 3); None = the origins;
+    quat_offsets: the sensors' axes in their links' frames, wxyz, (4,) or (n_links, 4); None (all-zero in the struct) = the links' axes.
+    No flag bit is defined yet."""
+    q = MirAccQuery()
+    q.struct_size = C.sizeof(MirAccQuery)
+    links = [int(b) for b in links]
+    if not 1 <= len(links) <= MIR_MAX_BODY:
+        raise ValueError(f"link_accelerations takes 1 .. {MIR_MAX_BODY} links, got {len(links)}")
+    if int(flags) != 0:
+        raise ValueError(f"unknown MirAccQuery flag bits {int(flags):#x}")
+    q.n_links = len(links)
+    q.link_body[:len(links)] = links
+    if local_points is not None:
+        for i, p in enumerate(_per_link(local_points, len(links), 3, "local_points")):
+            q.local_point[i][:] = p
+    if quat_offsets is not None:
+        for i, p in enumerate(_per_link(quat_offsets, len(links), 4, "quat_offsets")):
+            q.quat_offset[i][:] = p
+    q.flags = 0
+    return q
+
+
 class MirDynQuery(C.Structure):
     """include/mirigid.h: MirDynQuery (mir_dynamics)"""
     _fields_ = [

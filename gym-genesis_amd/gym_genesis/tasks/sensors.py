@@ -13,6 +13,10 @@ Patterns (each has ``.shape`` and ``.directions()`` -> float32 ``(prod(shape), 3
     parallel rays from a grid of origins; mir_raycast carries one origin per sensor).
   * ``DepthCameraPattern(res=(W, H), fov_vertical=60)``: shape (H, W); the pinhole camera of include/mirigid.h -- pixel centres, row 0
     at the top, d = F + x R + y U before normalising -- with F = +x, R = -y, U = +z of the sensor frame.
+
+Inertial sensors: ``scene.add_sensor(IMU(entity=robot, link="hand"))`` + ``sensor.read()`` -> ``lin_acc``, ``ang_vel`` (Genesis:
+``gs.sensors.IMU``): what an accelerometer and a gyro on the link read, in the sensor's frame; a read is ONE launch of
+``mir_link_accelerations`` for the envs asked for.
 """
 from __future__ import annotations
 
@@ -170,22 +174,11 @@ class RaySensor:
     """What SceneView.add_sensor returns.  The pattern's directions are uploaded once."""
 
     def __init__(self, mir, options):
-        from .views import LinkView
-
         self._mir, self.options, self.pattern = mir, options, options.pattern
         self.shape = tuple(int(s) for s in self.pattern.shape)
         spec = mir.spec
-        link, entity = options.link, options.entity
-        if isinstance(link, LinkView):
-            body = link.idx
-        elif isinstance(link, str):
-            if entity is None:
-                raise ValueError("a link name needs the entity it belongs to")
-            body = entity.get_link(link).idx
-        elif link is None:
-            body = 0 if entity is None else int(entity.root)
-        else:
-            body = int(link)
+        entity = options.entity
+        body = _link_body(options)
         if not 0 <= body < spec.nbody:
             raise ValueError(f"link body {body} outside the scene's {spec.nbody} bodies")
         self.link_body = body
@@ -240,7 +233,67 @@ class RaySensor:
         return (dist * self._dirs[:, 0][None, :]).reshape(dist.shape[0], *self.shape)
 
 
-def make_sensor(mir, options) -> RaySensor:
+@dataclass
+class IMU:
+    """Options of an inertial measurement unit (Genesis: ``gs.sensors.IMU``; parity with Genesis unpinned): an accelerometer and a gyro on
+    a link.  `link`: a LinkView, or a link name together with `entity`, or None -- then the sensor rides on the entity's root link (it
+    needs a link: there is nothing to measure in the world's frame).  `pos_offset` / `euler_offset` (degrees, xyz; or `quat_offset`
+    wxyz, which wins): the sensor frame in the link's frame.  No noise, bias or delay model: that is torch on the caller's side."""
+    entity: Any = None
+    link: Any = None
+    pos_offset: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    euler_offset: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    quat_offset: Optional[Tuple[float, float, float, float]] = None
+
+
+ImuData = namedtuple("ImuData", ("lin_acc", "ang_vel"))
+
+
+def _link_body(options) -> int:
+    """the body a sensor's options put it on (0: the world), resolved as for Raycaster"""
+    from .views import LinkView
+
+    link, entity = options.link, options.entity
+    if isinstance(link, LinkView):
+        return link.idx
+    if isinstance(link, str):
+        if entity is None:
+            raise ValueError("a link name needs the entity it belongs to")
+        return entity.get_link(link).idx
+    if link is None:
+        return 0 if entity is None else int(entity.root)
+    return int(link)
+
+
+class ImuSensor:
+    """What SceneView.add_sensor returns for IMU options."""
+
+    def __init__(self, mir, options):
+        self._mir, self.options = mir, options
+        body = _link_body(options)
+        if not 1 <= body < mir.spec.nbody:
+            raise ValueError(f"an IMU rides on a link: body {body} outside 1 .. {mir.spec.nbody - 1}")
+        self.link_body = body
+        self.quat_offset = tuple(float(v) for v in options.quat_offset) if options.quat_offset is not None else euler_to_quat(options.euler_offset)
+        self.pos_offset = tuple(float(v) for v in options.pos_offset)
+
+    def read(self, envs_idx=None, qacc=None) -> ImuData:
+        """-> named tuple (lin_acc (R, 3), ang_vel (R, 3)) in the sensor's frame: the classical acceleration of the sensor's point minus
+        gravity (at rest: +9.81 along the world's up axis) and the link's angular velocity.  `qacc` (R, nv): the joint accelerations
+        to read at; None: those the next step applies if the targets stay as they are (one forward evaluation)."""
+        from .views import _env_index
+
+        fn = getattr(self._mir, "link_accelerations", None)
+        if fn is None:
+            raise NotImplementedError("this scene has no link accelerations (MirScene.link_accelerations / mir_link_accelerations)")
+        r = fn([self.link_body], local_points=self.pos_offset, quat_offsets=self.quat_offset, env_idx=_env_index(self._mir, envs_idx), qacc=qacc,
+               acc=False, imu=True)["imu"]
+        return ImuData(r[:, 0, 0:3].contiguous(), r[:, 0, 3:6].contiguous())
+
+
+def make_sensor(mir, options):
+    if isinstance(options, IMU):
+        return ImuSensor(mir, options)
     if not isinstance(options, Raycaster):
         raise TypeError(f"add_sensor takes Raycaster / Lidar / DepthCamera options, got {type(options).__name__}")
     return RaySensor(mir, options)

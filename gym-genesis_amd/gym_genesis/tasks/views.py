@@ -64,9 +64,27 @@ def _kinematics(mir, **kw) -> dict:
     return fn(**kw)
 
 
+def _accelerations(mir, **kw) -> dict:
+    fn = getattr(mir, "link_accelerations", None)
+    if fn is None:
+        raise NotImplementedError("this scene has no link accelerations (MirScene.link_accelerations / mir_link_accelerations)")
+    return fn(**kw)
+
+
 class LinkView:
     def __init__(self, mir, body_index: int, name: str):
         self._mir, self.idx, self.name = mir, body_index, name
+
+    def get_acc(self, envs_idx=None) -> torch.Tensor:
+        """(B, 3): classical world linear acceleration of the link's origin, for the acceleration the next step applies if the targets
+        stay as they are (EntityView.get_links_acc for one link)."""
+        k = _accelerations(self._mir, links=[self.idx], env_idx=_env_index(self._mir, envs_idx))
+        return k["acc"][:, 0, 0:3].contiguous()
+
+    def get_ang_acc(self, envs_idx=None) -> torch.Tensor:
+        """(B, 3): world angular acceleration of the link.  This package's own name: parity with Genesis is unpinned."""
+        k = _accelerations(self._mir, links=[self.idx], env_idx=_env_index(self._mir, envs_idx))
+        return k["acc"][:, 0, 3:6].contiguous()
 
     def get_vel(self, envs_idx=None) -> torch.Tensor:
         """(B, 3): world linear velocity of the link's origin (Genesis: RigidLink.get_vel)."""
@@ -228,6 +246,31 @@ class EntityView:
     def get_links_ang(self, links_idx_local=None, envs_idx=None) -> torch.Tensor:
         """(B, n_links, 3): world angular velocity of each link"""
         return self.links_kinematics(links_idx_local, envs_idx, pos=False, quat=False)["ang"]
+
+    # ---- link accelerations (MirScene.link_accelerations / mir_link_accelerations): one launch per call, for the links and envs asked for
+    # only.  The acceleration is the one the next scene.step() applies if the targets stay as they are (one forward evaluation, the
+    # convention of the contact forces) -- Genesis reports that of the step just taken; parity with Genesis is unpinned.
+    def links_accelerations(self, links_idx_local=None, envs_idx=None) -> dict:
+        """acc (B,n,3), ang_acc (B,n,3) of this entity's links (all, or the local indices given) from ONE launch."""
+        k = _accelerations(self._mir, links=self._link_bodies(links_idx_local), env_idx=_env_index(self._mir, envs_idx))
+        return {"acc": k["acc"][:, :, 0:3].contiguous(), "ang_acc": k["acc"][:, :, 3:6].contiguous()}
+
+    def get_links_acc(self, links_idx_local=None, envs_idx=None) -> torch.Tensor:
+        """``entity.get_links_acc()`` (a Genesis name) -> (B, n_links, 3): classical world linear acceleration of each link's origin.
+        Gravity is not added: a link at rest reads 0 (an IMU sensor reads +9.81 up: tasks/sensors.py)."""
+        return self.links_accelerations(links_idx_local, envs_idx)["acc"]
+
+    def get_links_ang_acc(self, links_idx_local=None, envs_idx=None) -> torch.Tensor:
+        """(B, n_links, 3): world angular acceleration of each link.  This package's own name: parity with Genesis is unpinned."""
+        return self.links_accelerations(links_idx_local, envs_idx)["ang_acc"]
+
+    def get_jacobian_dot_qvel(self, link, local_point=None, envs_idx=None) -> torch.Tensor:
+        """(B, 6): Jdot qvel of the link's origin (of `local_point`, given in the link's frame) -- the acceleration of the point and the
+        angular acceleration of the link at qacc = 0, the term of a = J qacc + Jdot qvel beside get_jacobian's J.  It needs no forward
+        evaluation.  This package's own name: parity with Genesis is unpinned."""
+        k = _accelerations(self._mir, links=[self._link_body(link)], local_points=None if local_point is None else [float(v) for v in np.asarray(local_point).reshape(3)],
+                           env_idx=_env_index(self._mir, envs_idx), acc=False, bias_acc=True)
+        return k["bias_acc"][:, 0].contiguous()
 
     # ---- rigid-body dynamics queries (MirScene.dynamics / mir_dynamics): one launch per call, for this entity's dofs and the envs asked
     # for only.  get_mass_mat and get_dofs_control_force are Genesis names (RigidEntity); get_dofs_bias_force, get_dofs_gravity_force and
@@ -642,7 +685,9 @@ class SceneView:
 
     def add_sensor(self, options):
         """``scene.add_sensor(gs.sensors.Lidar(...))``: a ray-cast range sensor (tasks/sensors.py: Raycaster / Lidar / DepthCamera options)
-        on a link or fixed in the world; ``sensor.read()`` -> (points, distances) in one launch (mir_raycast)."""
+        on a link or fixed in the world; ``sensor.read()`` -> (points, distances) in one launch (mir_raycast).
+        ``scene.add_sensor(gs.sensors.IMU(...))``: an accelerometer and gyro on a link; ``sensor.read()`` -> (lin_acc, ang_vel) in one
+        launch (mir_link_accelerations)."""
         from .sensors import make_sensor
 
         return make_sensor(self._mir, options)

@@ -524,6 +524,44 @@ int mir_dynamics(MirHandle h, const MirDynQuery* q, const int64_t* env_idx /* de
                  float* M /* (R, n_dofs, n_dofs) */, float* bias /* (R, n_dofs) */, float* gravity /* (R, n_dofs) */,
                  float* tau /* (R, n_dofs) */, float* ctrl_force /* (R, n_dofs) */, void* stream);
 
+/* ---- link accelerations and IMU readings -------------------------------------------------------------
+ * entity.get_links_acc() and gs.sensors.IMU of Genesis (RigidEntity; parity with Genesis unpinned: the reference's tasks read neither),
+ * and the term Jdot qvel of operational-space control, a = J qacc + Jdot qvel with J the Jacobian of mir_link_kinematics.
+ * ONE launch of a kernel of its own for a LIST of links of a LIST of envs: it reads qpos / qvel, the caller's qacc and the compiled
+ * model and writes only its outputs.
+ *   R = n_rows, or num_envs when env_idx is NULL; row k belongs to env env_idx[k] (int64, device; repeats and any order allowed; an
+ *   index outside the batch is clamped as in mir_link_kinematics).  L = q->n_links.  qacc (R, nv) is in the public dof order of
+ *   mir_get_state, row k for row k of the outputs; the state is the current one.
+ * Definitions (the conventions of mir_link_kinematics: a free joint's qvel is the world linear velocity of the body origin, then the
+ * world angular velocity, qacc its time derivative).  With o, R, w the world pose and angular velocity of the link,
+ * p = o + R local_point the material point of the link that is there now:
+ *   acc      (R, L, 6): rows 0-2 the classical world linear acceleration d^2 p / dt^2, rows 3-5 the link's world angular acceleration:
+ *            J qacc + Jdot qvel over all scene dofs.  Gravity is not added: it is in qacc already.
+ *   bias_acc (R, L, 6): the same at qacc = 0, Jdot qvel.  It needs no qacc and does not depend on it, to the bit.
+ *   imu      (R, L, 6): rows 0-2 R_s^T (d^2 p / dt^2 - g), rows 3-5 R_s^T w, with R_s = R R(quat_offset[l]) the sensor's axes and g the
+ *            gravity vector of the scene spec (opt.gravity): a sensor at rest reads +9.81 along the world's up axis, in its own frame.
+ * Every output is nullable and written only when asked for; all three NULL, or R == 0: MIR_OK without a launch.
+ * A read changes nothing: state, targets, warm start, state version, pose cache, diagnostics, counters and the scratch row of a split
+ * step stay as they are, and the steps around it are bit for bit those of a run without it.
+ * MIR_E_INVALID: a NULL handle or query, struct_size != sizeof(MirAccQuery), n_links outside 1 .. MIR_MAX_BODY, a link outside
+ * 1 .. nbody - 1, a local_point or quat_offset that is not finite, an unknown flag bit, acc or imu without qacc (the rule of tau in
+ * mir_dynamics), a free joint below another body (its qvel would mix two conventions: the rule of mir_dynamics), a call while a
+ * mir_step_begin is open.  MIR_E_CAPACITY: a path world -> link of more than 16 bodies.  None of them launches anything.
+ * (An added struct and entry point: MIR_VERSION and every other struct stay as they are.) */
+typedef struct MirAccQuery {
+  int32_t struct_size;                  /* = sizeof(MirAccQuery) */
+  int32_t n_links;                      /* 1 .. MIR_MAX_BODY */
+  int32_t link_body[MIR_MAX_BODY];      /* body indices of the spec, 1 .. nbody-1, repeats allowed */
+  float local_point[MIR_MAX_BODY][3];   /* per queried link: point in the link's frame (0 = link origin) */
+  float quat_offset[MIR_MAX_BODY][4];   /* per queried link: sensor axes in the link's frame, wxyz, normalised by the library; all-zero = identity */
+  uint32_t flags;                       /* 0; unknown bits are MIR_E_INVALID */
+} MirAccQuery;
+int mir_acc_query_sizeof(void);
+int mir_link_accelerations(MirHandle h, const MirAccQuery* q, const int64_t* env_idx /* device, nullable */, int32_t n_rows,
+                           const float* qacc /* (R, nv) device, public layout, nullable: needed for acc and imu */,
+                           float* acc /* (R, L, 6) lin, ang */, float* bias_acc /* (R, L, 6) */, float* imu /* (R, L, 6) lin, gyro */,
+                           void* stream);
+
 /* ---- range sensing: batched ray casts ------------------------------------------------------------------
  * scene.add_sensor(gs.sensors.Lidar / Raycaster / DepthCamera(...)) + sensor.read() -> points, distances of Genesis (parity with
  * Genesis unpinned: the reference's tasks cast no rays and the package is not in the reference tree; the names follow its sensor API
