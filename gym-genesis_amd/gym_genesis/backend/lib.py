@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirAccQuery, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirVisualSpec, make_acc_query, make_dyn_query, make_kin_query, make_ray_query  # noqa: F401
+from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirAccQuery, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirTaskQuery, MirVisualSpec, make_acc_query, make_dyn_query, make_kin_query, make_ray_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -134,6 +134,9 @@ def load_library() -> C.CDLL:
     lib.mir_dyn_query_sizeof.restype = C.c_int
     lib.mir_dynamics.argtypes = [vp, C.POINTER(MirDynQuery), vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_dynamics.restype = C.c_int
+    lib.mir_task_query_sizeof.restype = C.c_int
+    lib.mir_task_dynamics.argtypes = [vp, C.POINTER(MirTaskQuery), vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_task_dynamics.restype = C.c_int
     lib.mir_ray_query_sizeof.restype = C.c_int
     lib.mir_raycast.argtypes = [vp, C.POINTER(MirRayQuery), vp, vp, i32, vp, vp, vp, vp, vp]
     lib.mir_raycast.restype = C.c_int
@@ -149,6 +152,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirAccQuery (rebuild the library)")
     if lib.mir_dyn_query_sizeof() != C.sizeof(MirDynQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirDynQuery (rebuild the library)")
+    if lib.mir_task_query_sizeof() != C.sizeof(MirTaskQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirTaskQuery (rebuild the library)")
     if lib.mir_ray_query_sizeof() != C.sizeof(MirRayQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRayQuery (rebuild the library)")
     _lib = lib
@@ -771,6 +776,60 @@ class MirScene(StepHelpers):
                                           self._stream()))
         if out and R > 0 and n > 0:
             self.dynamics_launches = self.__dict__.get("dynamics_launches", 0) + 1
+        return out
+
+    def task_dynamics(self, links=(), local_points=None, env_idx=None, dof0: int = 0, n_dofs: Optional[int] = None, qpos=None, x=None,
+                      damping: float = 0.0, minv: bool = False, solve: bool = False, lambda_inv: Optional[bool] = None,
+                      lambda_: Optional[bool] = None, jbar: Optional[bool] = None) -> dict:
+        """mir_task_dynamics: operational-space dynamics of the links `links` (body indices of the spec, repeats allowed; none for minv /
+        solve alone) in ONE launch of a kernel of its own, for the envs `env_idx` (int64 device tensor, any order, repeats allowed; None:
+        all envs).  With M the mass matrix of dynamics(), J the Jacobian of link_kinematics() at `local_points` ((3,) or (n_links, 3);
+        None: the origins), R rows, L links and n the dofs [dof0, dof0 + n_dofs) (n_dofs None: up to nv):
+        minv (R,n,n) = the window of M^-1, solve (R,n) = the window of M^-1 x for the full-length `x` (R,nv), lambda_inv (R,L,6,6) =
+        J M^-1 J^T, lambda (R,L,6,6) = (J M^-1 J^T + damping^2 I)^-1, jbar (R,L,n,6) = the window rows of M^-1 J^T lambda.  The window
+        selects what is written, never what is inverted.  Where the 6 x 6 matrix is singular to float32 (a relative Cholesky pivot
+        <= 1e-5: a link with fewer than six dofs above it, an arm at a singularity) lambda and jbar of that row and link are NaN;
+        damping > 0 is the remedy.  `qpos` (R,nq), in the layout of get_state(), replaces the rows' current qpos for this evaluation
+        only.  Only the outputs asked for are computed and returned (lambda under the key "lambda"; lambda_inv / lambda_ / jbar None:
+        asked for when there are links): fresh device tensors on the current stream.  The read changes nothing."""
+        nd = self.nv - int(dof0) if n_dofs is None else int(n_dofs)
+        lambda_inv, lambda_, jbar = (bool(len(links)) if w is None else bool(w) for w in (lambda_inv, lambda_, jbar))
+        q = make_task_query(links, local_points, dof0, nd, damping)
+        idx = None
+        if env_idx is not None:
+            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        R, L = (self.num_envs if idx is None else int(idx.numel())), q.n_links
+
+        def rows(t, width, name):
+            if t is None:
+                return None
+            t = torch.as_tensor(t, device=self.device).to(torch.float32).contiguous()
+            if tuple(t.shape) != (R, width):
+                raise ValueError(f"{name} must be ({R}, {width}), got {tuple(t.shape)}")
+            return t
+
+        qpos, x = rows(qpos, self.nq, "qpos"), rows(x, self.nv, "x")
+        if solve and x is None:
+            raise ValueError("solve needs x")
+        if (lambda_inv or lambda_ or jbar) and L == 0:
+            raise ValueError("lambda_inv, lambda and jbar need a link")
+        n = max(nd, 0)
+        new = lambda *shape: torch.empty((R, *shape), dtype=torch.float32, device=self.device)  # noqa: E731
+        out = {}
+        if minv:
+            out["minv"] = new(n, n)
+        if solve:
+            out["solve"] = new(n)
+        if lambda_inv:
+            out["lambda_inv"] = new(L, 6, 6)
+        if lambda_:
+            out["lambda"] = new(L, 6, 6)
+        if jbar:
+            out["jbar"] = new(L, n, 6)
+        self._check(self.lib.mir_task_dynamics(self.h, C.byref(q), _ptr(idx), R, _ptr(qpos), _ptr(x), _ptr(out.get("minv")), _ptr(out.get("solve")),
+                                               _ptr(out.get("lambda_inv")), _ptr(out.get("lambda")), _ptr(out.get("jbar")), self._stream()))
+        if R > 0 and any(v.numel() for v in out.values()):
+            self.task_dynamics_launches = self.__dict__.get("task_dynamics_launches", 0) + 1
         return out
 
     def raycast(self, dirs, link: int = 0, pos_offset=(0.0, 0.0, 0.0), quat_offset=(1.0, 0.0, 0.0, 0.0), min_range: float = 0.0,

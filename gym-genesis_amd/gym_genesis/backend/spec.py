@@ -301,6 +301,50 @@ def make_dyn_query(dof0: int = 0, n_dofs: int = 0, flags: int = 0) -> MirDynQuer
     return q
 
 
+class MirTaskQuery(C.Structure):
+    """include/mirigid.h: MirTaskQuery (mir_task_dynamics)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_links", C.c_int32),
+        ("link_body", C.c_int32 * MIR_MAX_BODY),
+        ("local_point", (C.c_float * 3) * MIR_MAX_BODY),
+        ("dof0", C.c_int32),
+        ("n_dofs", C.c_int32),
+        ("damping", C.c_float),
+        ("flags", C.c_uint32),
+    ]
+
+
+def make_task_query(links: Sequence[int] = (), local_points=None, dof0: int = 0, n_dofs: int = 0, damping: float = 0.0, flags: int = 0) -> MirTaskQuery:
+    """links: body indices of the spec, none for a query of minv / solve alone; local_points: one task point (3,) for every link, or
+    one per link (n_links, 3), in the link's frame; None = the origins; [dof0, dof0 + n_dofs): the window of scene dofs of the
+    dof-indexed outputs; damping >= 0: damping^2 is added to the diagonal of lambda_inv before it is inverted.  No flag bit is defined
+    yet."""
+    links = [int(b) for b in links]
+    dof0, n_dofs, damping, flags = int(dof0), int(n_dofs), float(damping), int(flags)
+    if len(links) > MIR_MAX_BODY:
+        raise ValueError(f"task_dynamics takes 0 .. {MIR_MAX_BODY} links, got {len(links)}")
+    if any(b < 1 for b in links):
+        raise ValueError(f"task_dynamics links are body indices >= 1, got {links}")
+    if dof0 < 0 or n_dofs < 0 or dof0 + n_dofs > MIR_MAX_DOF:
+        raise ValueError(f"task_dynamics window [{dof0}, {dof0 + n_dofs}) outside [0, {MIR_MAX_DOF}]")
+    if not math.isfinite(damping) or damping < 0.0:
+        raise ValueError(f"damping must be finite and >= 0, got {damping}")
+    if flags != 0:
+        raise ValueError(f"unknown MirTaskQuery flag bits {flags:#x}")
+    q = MirTaskQuery()
+    q.struct_size = C.sizeof(MirTaskQuery)
+    q.n_links = len(links)
+    q.link_body[:len(links)] = links
+    if local_points is not None and links:
+        for i, p in enumerate(_per_link(local_points, len(links), 3, "local_points")):
+            if not all(math.isfinite(v) for v in p):
+                raise ValueError("local_points must be finite")
+            q.local_point[i][:] = p
+    q.dof0, q.n_dofs, q.damping, q.flags = dof0, n_dofs, damping, flags
+    return q
+
+
 MIR_RAY_POINTS_WORLD = 1  # MirRayQuery.flags: points / normal in world axes (include/mirigid.h)
 
 

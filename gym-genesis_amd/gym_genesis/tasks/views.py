@@ -352,6 +352,105 @@ class EntityView:
                 kw["qvel"] = full
         return self._dynamics(idx, dofs_idx_local, "tau", **kw)
 
+    # ---- operational-space dynamics (MirScene.task_dynamics / mir_task_dynamics): one launch per call, for this entity's dofs, the link
+    # and the envs asked for only.  Windows and columns are over the entity's own dofs; `envs_idx` and `qpos` are handled as in
+    # inverse_dynamics.  The names are this package's own: parity with Genesis is unpinned (the reference's tasks call none).
+    def _entity_rows(self, t, R: int, name: str) -> torch.Tensor:
+        n = len(self._jac_dofs())
+        t = torch.as_tensor(t, device=self._mir.device).to(torch.float32).reshape(R, -1)
+        if t.shape[1] != n:
+            raise ValueError(f"{name} must be ({R}, {n}) over this entity's dofs, got {tuple(t.shape)}")
+        return t
+
+    def _full_state_rows(self, idx, R: int, qpos=None, qvel=None, who: str = "task_dynamics") -> dict:
+        """the entity-wide `qpos` / `qvel` overrides as full rows of the scene state (the other entities in their current state)"""
+        mir, kw = self._mir, {}
+        if qpos is None and qvel is None:
+            return kw
+        state = mir.get_state()
+        if qpos is not None:
+            if not self.dof_idx:
+                raise NotImplementedError(f"{who}: qpos override of an entity without scalar joints")
+            full = _rows(state[0], idx).clone()
+            full[:, torch.as_tensor(self._qcols, dtype=torch.long, device=mir.device)] = self._entity_rows(qpos, R, "qpos")
+            kw["qpos"] = full
+        if qvel is not None:
+            full = _rows(state[1], idx).clone()
+            full[:, torch.as_tensor(self._jac_dofs(), dtype=torch.long, device=mir.device)] = self._entity_rows(qvel, R, "qvel")
+            kw["qvel"] = full
+        return kw
+
+    def _task_dynamics(self, idx, **kw) -> dict:
+        fn = getattr(self._mir, "task_dynamics", None)
+        if fn is None:
+            raise NotImplementedError("this scene has no operational-space dynamics (MirScene.task_dynamics / mir_task_dynamics)")
+        cols = self._jac_dofs()
+        run = bool(cols) and cols == list(range(cols[0], cols[0] + len(cols)))
+        win = dict(dof0=cols[0], n_dofs=len(cols)) if run else {}
+        out = fn(env_idx=idx, **win, **kw)
+        if not run:
+            ix = torch.as_tensor(cols, dtype=torch.long, device=self._mir.device)
+            if "minv" in out:
+                out["minv"] = out["minv"].index_select(1, ix).index_select(2, ix)
+            if "solve" in out:
+                out["solve"] = out["solve"].index_select(1, ix)
+            if "jbar" in out:
+                out["jbar"] = out["jbar"].index_select(2, ix)
+        return out
+
+    def get_mass_mat_inv(self, envs_idx=None) -> torch.Tensor:
+        """(B, n, n): the inverse of get_mass_mat() over this entity's dofs -- the block of M^-1 of its kinematic tree, by a Cholesky
+        factorisation on the GPU in the launch that builds M.  Bitwise symmetric."""
+        out = self._task_dynamics(_env_index(self._mir, envs_idx), minv=True, lambda_inv=False, lambda_=False, jbar=False)
+        return out["minv"].contiguous()
+
+    def mass_mat_solve(self, x, qpos=None, envs_idx=None) -> torch.Tensor:
+        """(B, n): M^-1 x for `x` (B, n) over this entity's dofs, at `qpos` (B, n) over this entity's dofs when given, else at the
+        current state."""
+        mir = self._mir
+        idx = _env_index(mir, envs_idx)
+        R = mir.num_envs if idx is None else int(idx.numel())
+        full = torch.zeros((R, mir.nv), dtype=torch.float32, device=mir.device)
+        full[:, torch.as_tensor(self._jac_dofs(), dtype=torch.long, device=mir.device)] = self._entity_rows(x, R, "x")
+        kw = self._full_state_rows(idx, R, qpos=qpos, who="mass_mat_solve")
+        out = self._task_dynamics(idx, x=full, solve=True, lambda_inv=False, lambda_=False, jbar=False, **kw)
+        return out["solve"].contiguous()
+
+    def forward_dynamics(self, tau, qpos=None, qvel=None, envs_idx=None) -> torch.Tensor:
+        """(B, n): qacc = M^-1 (tau - c(q, qvel)) for the applied torque `tau` (B, n) over this entity's dofs: the inverse of
+        inverse_dynamics.  TWO launches: mir_dynamics for the bias force c, then mir_task_dynamics for the solve.  At `qpos` / `qvel`
+        (B, n) over this entity's dofs when given, else at the current state; passive damping, PD torques and contact forces are not
+        included (they belong in tau)."""
+        mir = self._mir
+        idx = _env_index(mir, envs_idx)
+        R = mir.num_envs if idx is None else int(idx.numel())
+        kw = self._full_state_rows(idx, R, qpos=qpos, qvel=qvel, who="forward_dynamics")
+        bias = self._dynamics(idx, None, "bias", **kw)
+        x = self._entity_rows(tau, R, "tau") - bias
+        return self.mass_mat_solve(x, qpos=qpos, envs_idx=idx)
+
+    def operational_space(self, link, local_point=None, envs_idx=None, damping: float = 0.0, qpos=None) -> dict:
+        """Operational-space dynamics of `link` (a LinkView of this entity or a local link index) at `local_point` (in the link's frame;
+        None: its origin), from ONE launch: lambda_inv (B, 6, 6) = J M^-1 J^T, lambda (B, 6, 6) = (J M^-1 J^T + damping^2 I)^-1 and
+        jbar (B, n, 6) = M^-1 J^T lambda over this entity's dofs, with J = get_jacobian(link, local_point) (linear rows first, then
+        angular).  Where the task space is singular to float32 -- a link with fewer than six dofs above it, an arm at a singularity --
+        lambda and jbar of that env are NaN; damping > 0 is the remedy.  lambda_inv is always finite."""
+        mir = self._mir
+        idx = _env_index(mir, envs_idx)
+        R = mir.num_envs if idx is None else int(idx.numel())
+        kw = self._full_state_rows(idx, R, qpos=qpos, who="operational_space")
+        lp = None if local_point is None else [float(v) for v in np.asarray(local_point).reshape(3)]
+        out = self._task_dynamics(idx, links=[self._link_body(link)], local_points=lp, damping=float(damping), **kw)
+        return {"lambda_inv": out["lambda_inv"][:, 0].contiguous(), "lambda": out["lambda"][:, 0].contiguous(), "jbar": out["jbar"][:, 0].contiguous()}
+
+    def get_operational_inertia(self, link, local_point=None, envs_idx=None, damping: float = 0.0, qpos=None) -> torch.Tensor:
+        """(B, 6, 6): lambda of operational_space()."""
+        return self.operational_space(link, local_point, envs_idx, damping, qpos)["lambda"]
+
+    def get_jacobian_dyn_inverse(self, link, local_point=None, envs_idx=None, damping: float = 0.0, qpos=None) -> torch.Tensor:
+        """(B, n, 6): jbar of operational_space(), the dynamically consistent generalised inverse of get_jacobian(link)."""
+        return self.operational_space(link, local_point, envs_idx, damping, qpos)["jbar"]
+
     def get_link(self, name: str) -> LinkView:
         return LinkView(self._mir, self._b.body_index(name), name)
 

@@ -562,6 +562,60 @@ int mir_link_accelerations(MirHandle h, const MirAccQuery* q, const int64_t* env
                            float* acc /* (R, L, 6) lin, ang */, float* bias_acc /* (R, L, 6) */, float* imu /* (R, L, 6) lin, gyro */,
                            void* stream);
 
+/* ---- operational-space dynamics: M^-1, task-space inertia, J-bar ---------------------------------------------
+ * The step from M (mir_dynamics), J (mir_link_kinematics) and Jdot qvel (mir_link_accelerations) to an operational-space or impedance
+ * controller, and forward dynamics qacc = M^-1 (tau - bias) (parity with Genesis unpinned: the reference's tasks call none of it).
+ * ONE launch of a kernel of its own for a LIST of links of a LIST of envs: it reads qpos and the compiled model and writes only its
+ * outputs.  Everything here depends on qpos only.
+ *   R = n_rows, or num_envs when env_idx is NULL; row k belongs to env env_idx[k] (int64, device; repeats and any order allowed; an
+ *   index outside the batch is clamped as in mir_dynamics).  L = q->n_links; n = q->n_dofs, the window of scene dofs [dof0, dof0 + n).
+ *   The window selects which rows and columns are WRITTEN; it never changes the matrix that is inverted, which is always the whole
+ *   block of a kinematic tree.
+ * State override: qpos (R, nq) in the public layout of mir_get_state, the rule of mir_dynamics: row k replaces the current qpos of env
+ * env_idx[k] for this evaluation only.
+ * Definitions.  M is the full joint-space inertia of mir_dynamics (armature on the diagonal, no dt (damping + kv)).  J is the 6 x nv
+ * Jacobian of mir_link_kinematics at p = o_link + R_link local_point: linear rows first, then angular, with the free-joint convention
+ * of MIR_JNT_FREE.
+ *   minv       (R, n, n) row-major: the window of M^-1.  Symmetric, both triangles written, bitwise symmetric; entries between
+ *              different kinematic trees are exact zeros (written, not left as they were).
+ *   solve      (R, n): the window of M^-1 x for the full-length x (R, nv), public dof order.  Forward dynamics is x = tau - bias with
+ *              the bias of mir_dynamics.
+ *   lambda_inv (R, L, 6, 6): J M^-1 J^T, the task-space mobility.  Both triangles written by one owner: bitwise symmetric.  Always finite.
+ *   lambda     (R, L, 6, 6): (J M^-1 J^T + damping^2 I)^-1, the operational-space inertia.
+ *   jbar       (R, L, n, 6): the window rows of M^-1 J^T lambda, the dynamically consistent generalised inverse of J.  With
+ *              damping = 0, J jbar = I.
+ * Singular task spaces (a link with fewer than six dofs on its path; an arm at a singularity).  The 6 x 6 matrix
+ * A = J M^-1 J^T + damping^2 I is factored by Cholesky without pivoting.  If a pivot -- the remainder a_jj - sum_k c_jk^2 of which the
+ * square root would be taken -- is <= 1e-5 x the largest diagonal entry of A, lambda and jbar of that (row, link) are written as quiet
+ * NaNs; nothing else is affected and the call still returns MIR_OK.  A relative pivot of 1e-5 means a condition number beyond what
+ * float32 can invert meaningfully; damping > 0 is the remedy.
+ * Every output is nullable and written only when asked for; all five NULL, or R == 0, or an empty result (n == 0 with no lambda_inv /
+ * lambda asked for): MIR_OK without a launch.  Any 4-byte aligned address works; every element is written exactly once.
+ * A read changes nothing: state, targets, warm start, state version, pose cache, diagnostics, counters and the scratch row of a split
+ * step stay as they are, and the steps around it are bit for bit those of a run without it.
+ * MIR_E_INVALID: a NULL handle or query, struct_size != sizeof(MirTaskQuery), n_links outside 0 .. MIR_MAX_BODY, a link outside
+ * 1 .. nbody - 1, a link whose kinematic tree has no dofs, a local_point or damping that is not finite, damping < 0, a window outside
+ * [0, nv], an unknown flag bit, solve without x, lambda_inv / lambda / jbar with n_links == 0, a free joint that is not the root of its
+ * tree, a call while a mir_step_begin is open.  MIR_E_CAPACITY (the limits of mir_dynamics): a kinematic tree of more than 16 bodies
+ * or 15 dofs, more than 20 trees with dofs, an output asked for whose element count exceeds 2^31 - 1.  None of them launches anything.
+ * (An added struct and entry point: MIR_VERSION and every other struct stay as they are.) */
+typedef struct MirTaskQuery {
+  int32_t struct_size;                  /* = sizeof(MirTaskQuery) */
+  int32_t n_links;                      /* 0 .. MIR_MAX_BODY (0: only minv / solve) */
+  int32_t link_body[MIR_MAX_BODY];      /* body indices of the spec, 1 .. nbody-1, repeats allowed */
+  float local_point[MIR_MAX_BODY][3];   /* task point in the link frame (0 = link origin) */
+  int32_t dof0, n_dofs;                 /* window of scene dofs for the dof-indexed outputs */
+  float damping;                        /* >= 0, finite; damping^2 is added to the diagonal of lambda_inv before it is inverted */
+  uint32_t flags;                       /* 0; unknown bits are MIR_E_INVALID */
+} MirTaskQuery;
+int mir_task_query_sizeof(void);
+int mir_task_dynamics(MirHandle h, const MirTaskQuery* q, const int64_t* env_idx /* device, nullable */, int32_t n_rows,
+                      const float* qpos /* (R, nq) device, nullable: evaluate here instead of at the current qpos */,
+                      const float* x /* (R, nv) nullable; needed for solve only */,
+                      float* minv /* (R, n, n) */, float* solve /* (R, n) */,
+                      float* lambda_inv /* (R, L, 6, 6) */, float* lambda /* (R, L, 6, 6) */,
+                      float* jbar /* (R, L, n, 6) */, void* stream);
+
 /* ---- range sensing: batched ray casts ------------------------------------------------------------------
  * scene.add_sensor(gs.sensors.Lidar / Raycaster / DepthCamera(...)) + sensor.read() -> points, distances of Genesis (parity with
  * Genesis unpinned: the reference's tasks cast no rays and the package is not in the reference tree; the names follow its sensor API
