@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import IK_DEFAULTS, MIR_VERSION, MirCameraSpec, MirDims, MirIkOptions, MirIkRows, MirAccQuery, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirTaskQuery, MirVisualSpec, make_acc_query, make_dyn_query, make_kin_query, make_ray_query, make_task_query  # noqa: F401
+from .spec import IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirTaskQuery, MirVisualSpec, make_acc_query, make_dyn_query, make_ik_multi, make_kin_query, make_ray_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -125,6 +125,9 @@ def load_library() -> C.CDLL:
     lib.mir_inverse_kinematics.restype = C.c_int
     lib.mir_inverse_kinematics_rows.argtypes = [vp, i32, C.POINTER(MirIkRows), vp, vp, vp, C.POINTER(MirIkOptions), vp, vp, vp]
     lib.mir_inverse_kinematics_rows.restype = C.c_int
+    lib.mir_ik_multi_sizeof.restype = C.c_int
+    lib.mir_inverse_kinematics_multilink.argtypes = [vp, C.POINTER(MirIkMulti), vp, vp, vp, C.POINTER(MirIkOptions), vp, vp, vp, vp, vp]
+    lib.mir_inverse_kinematics_multilink.restype = C.c_int
     lib.mir_kin_query_sizeof.restype = C.c_int
     lib.mir_link_kinematics.argtypes = [vp, C.POINTER(MirKinQuery), vp, i32, vp, vp, vp, vp, vp]
     lib.mir_link_kinematics.restype = C.c_int
@@ -156,6 +159,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirTaskQuery (rebuild the library)")
     if lib.mir_ray_query_sizeof() != C.sizeof(MirRayQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRayQuery (rebuild the library)")
+    if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
     _lib = lib
     _bind_fast(lib)
     return lib
@@ -1016,3 +1021,44 @@ class MirScene(StepHelpers):
         self._check(self.lib.mir_inverse_kinematics_rows(self.h, int(link_body), C.byref(rows), _ptr(pos), _ptr(quat), _ptr(init_qpos), C.byref(o),
                                                          _ptr(out), _ptr(err), self._stream()))
         return (out, err) if return_error else out
+
+    def inverse_kinematics_multilink(self, links, poss, quats=None, init_qpos=None, env_idx=None, flags: int = 0, init_col0: int = 0,
+                                     init_ncols: int = 0, pos_mask=(True, True, True), rot_mask=(True, True, True), dof_mask=None,
+                                     max_samples: int = 1, seed: int = 0, return_error: bool = False, return_info: bool = False, **opts):
+        """mir_inverse_kinematics_multilink: damped-least-squares IK for up to four links at once (body indices `links`), with axis masks
+        shared by the links, a mask over the n_arm joint columns that may move (None: every joint on a chain) and `max_samples` restarts,
+        for the rows `env_idx` (int64 device tensor, or None: every env) in ONE launch of a kernel of its own.  poss (n or B, L, 3),
+        quats (n or B, L, 4 | L, 4 with IK_QUAT_ONE | None), init_qpos: float32 tensors addressed as `flags` say (spec.IK_*), made
+        contiguous here.  -> (n, n_arm)[, err (n, L, 2)][, info dict: iters (n) int32 summed over the samples, sample (n) int32].
+        The scene state is read and never written."""
+        q = make_ik_multi(links, pos_mask, rot_mask, dof_mask, max_samples, seed, self.n_arm)
+        L = q.n_links
+        idx = None if env_idx is None else torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        n = self.num_envs if idx is None else int(idx.numel())
+        q.rows = MirIkRows(None if idx is None else idx.data_ptr(), n, int(flags), int(init_col0), int(init_ncols))
+
+        def dev(t, width, name, by_env, one=False):
+            if t is None:
+                return None
+            t = torch.as_tensor(t, device=self.device).to(torch.float32).contiguous()
+            want = 1 if one else (self.num_envs if by_env else n)
+            if t.numel() != want * width:
+                raise ValueError(f"{name} must hold {want} x {width} values, got {tuple(t.shape)}")
+            return t
+
+        p = dev(poss, L * 3, "poss", flags & IK_POS_BY_ENV)
+        if p is None:
+            raise ValueError("inverse_kinematics_multilink needs target positions")
+        qq = dev(quats, L * 4, "quats", flags & IK_QUAT_BY_ENV, bool(flags & IK_QUAT_ONE))
+        iq = dev(init_qpos, init_ncols or self.n_arm, "init_qpos", flags & IK_INIT_BY_ENV)
+        o = MirIkOptions(**{**IK_DEFAULTS, **opts})
+        out = torch.empty((n, self.n_arm), dtype=torch.float32, device=self.device)
+        err = torch.empty((n, L, 2), dtype=torch.float32, device=self.device) if return_error else None
+        iters = torch.empty((n,), dtype=torch.int32, device=self.device) if return_info else None
+        sample = torch.empty((n,), dtype=torch.int32, device=self.device) if return_info else None
+        if n > 0:   # (no rows: nothing to launch, and an empty tensor has no address to pass)
+            self._check(self.lib.mir_inverse_kinematics_multilink(self.h, C.byref(q), _ptr(p), _ptr(qq), _ptr(iq), C.byref(o), _ptr(out), _ptr(err),
+                                                                  _ptr(iters), _ptr(sample), self._stream()))
+            self.ik_multilink_launches = self.__dict__.get("ik_multilink_launches", 0) + 1
+        res = (out,) + ((err,) if return_error else ()) + (({"iters": iters, "sample": sample},) if return_info else ())
+        return res if len(res) > 1 else out

@@ -197,6 +197,55 @@ class MirIkRows(C.Structure):
 
 IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, IK_INIT_BY_ENV = 1, 2, 4, 8
 
+IK_MAX_LINKS = 4
+
+
+class MirIkMulti(C.Structure):
+    """include/mirigid.h: MirIkMulti (mir_inverse_kinematics_multilink)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_links", C.c_int32),
+        ("link_body", C.c_int32 * IK_MAX_LINKS),
+        ("pos_mask", C.c_uint8 * 3),
+        ("rot_mask", C.c_uint8 * 3),
+        ("reserved", C.c_uint8 * 2),
+        ("dof_mask", C.c_void_p),
+        ("max_samples", C.c_int32),
+        ("seed", C.c_uint32),
+        ("rows", MirIkRows),
+    ]
+
+
+def make_ik_multi(links: Sequence[int], pos_mask=(True, True, True), rot_mask=(True, True, True), dof_mask=None, max_samples: int = 1,
+                  seed: int = 0, n_arm: int = 0) -> MirIkMulti:
+    """links: 1 .. 4 body indices of the spec; pos_mask / rot_mask: three booleans each, shared by the links (rot_mask: 0, 1 or 3 true);
+    dof_mask: n_arm booleans over the joint columns, None = every joint on a chain.  The mask's bytes are kept alive by the struct
+    (`_dof_mask_buf`); `rows` is left for the caller."""
+    q = MirIkMulti()
+    q.struct_size = C.sizeof(MirIkMulti)
+    links = [int(b) for b in links]
+    if not 1 <= len(links) <= IK_MAX_LINKS:
+        raise ValueError(f"inverse_kinematics_multilink takes 1 .. {IK_MAX_LINKS} links, got {len(links)}")
+    pm, rm = [bool(v) for v in pos_mask], [bool(v) for v in rot_mask]
+    if len(pm) != 3 or len(rm) != 3:
+        raise ValueError("pos_mask and rot_mask take three entries")
+    if sum(rm) == 2:
+        raise ValueError("You can only align 0, 1 axis or all 3 axes.")
+    if int(max_samples) < 1:
+        raise ValueError("max_samples must be at least 1")
+    q.n_links = len(links)
+    q.link_body[:len(links)] = links
+    q.pos_mask[:] = [int(v) for v in pm]
+    q.rot_mask[:] = [int(v) for v in rm]
+    if dof_mask is not None:
+        dm = [1 if v else 0 for v in dof_mask]
+        if len(dm) != int(n_arm):
+            raise ValueError(f"dof_mask must have one entry per joint column ({n_arm}), got {len(dm)}")
+        q._dof_mask_buf = (C.c_uint8 * len(dm))(*dm)
+        q.dof_mask = C.addressof(q._dof_mask_buf)
+    q.max_samples, q.seed = int(max_samples), int(seed) & 0xFFFFFFFF
+    return q
+
 
 class MirKinQuery(C.Structure):
     """include/mirigid.h: MirKinQuery (mir_link_kinematics)"""

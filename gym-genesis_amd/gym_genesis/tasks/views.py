@@ -487,7 +487,81 @@ class EntityView:
             ix = self._qcols_t = torch.as_tensor(qc, dtype=torch.long, device=t.device)
         return t.index_select(1, ix)
 
-    def inverse_kinematics(self, link, pos=None, quat=None, init_qpos=None, envs_idx=None, return_error=False, **opts):
+    def inverse_kinematics_multilink(self, links, poss, quats=None, init_qpos=None, envs_idx=None, pos_mask=(True, True, True),
+                                     rot_mask=(True, True, True), dofs_idx_local=None, max_samples=1, seed=0, return_error=False, **opts):
+        """``robot.inverse_kinematics_multilink(links=[left_finger, right_finger], poss=[...], quats=[...])`` -> (R, n_dofs): joint
+        positions that bring every link of `links` (LinkViews of this entity or local link indices, 1 .. 4) to its target at once, from
+        ONE launch (MirScene.inverse_kinematics_multilink / mir_inverse_kinematics_multilink, where the iteration is defined).
+        `poss` / `quats`: one (R, 3) / (R, 4) tensor per link, or one quaternion (4 numbers) per link or for all links; quats None:
+        positions only.  R is the batch when `envs_idx` is None (row k = env k), else len(envs_idx), and then every argument is
+        addressed by row.  `pos_mask` / `rot_mask` (world axes of the position error; 0, 1 or 3 axes of the link to align) are shared
+        by the links; `dofs_idx_local` are the dofs of this entity that may move (None: every joint on a chain), every other entry of
+        the result is the seed (`init_qpos` (R, n_dofs), else the current state); `max_samples` restarts from seeded random joint
+        positions, the first converged sample wins.  With `return_error` also (R, L, 2): |e_pos|, |e_rot| per link."""
+        if sum(bool(v) for v in rot_mask) == 2:
+            raise ValueError("You can only align 0, 1 axis or all 3 axes.")
+        mir = self._mir
+        fn = getattr(mir, "inverse_kinematics_multilink", None)
+        if fn is None:
+            raise NotImplementedError("this scene has no multi-link IK (MirScene.inverse_kinematics_multilink / mir_inverse_kinematics_multilink)")
+        bodies = [self._link_body(l) for l in links]
+        L = len(bodies)
+        idx = _env_index(mir, envs_idx)   # (None also for an arange(B) given on the host: row k = env k)
+        R = mir.num_envs if idx is None else int(idx.numel())
+
+        def per_link(ts, k, name):
+            if not isinstance(ts, (list, tuple)) or (len(ts) == k and not hasattr(ts[0], "__len__")):
+                ts = [ts] * L   # (one quaternion for every link)
+            if len(ts) != L:
+                raise ValueError(f"{name} must hold one entry per link ({L}), got {len(ts)}")
+            return [torch.as_tensor(t, dtype=torch.float32, device=mir.device) for t in ts]
+
+        def rows(ts, k, name):
+            out = []
+            for t in ts:
+                t = t.expand(R, k) if t.numel() == k else t.reshape(-1, k)
+                if t.shape[0] != R:
+                    raise ValueError(f"{name}: expected {R} rows of {k}, got {tuple(t.shape)}")
+                out.append(t)
+            return torch.stack(out, dim=1).contiguous()
+
+        p = rows(per_link(poss, 3, "poss"), 3, "poss")
+        q, flags = None, 0
+        if quats is not None:
+            qs = per_link(quats, 4, "quats")
+            if all(t.numel() == 4 for t in qs):
+                q, flags = torch.stack([t.reshape(4) for t in qs]).contiguous(), IK_QUAT_ONE
+            else:
+                q = rows(qs, 4, "quats")
+        qc = self._qcols
+        run = qc == list(range(qc[0], qc[0] + len(qc)))
+        iq, col0, ncols = None, 0, 0
+        if init_qpos is not None:
+            iq = torch.as_tensor(init_qpos, dtype=torch.float32, device=mir.device).reshape(-1, len(qc))
+            if iq.shape[0] != R:
+                raise ValueError(f"init_qpos: expected {R} rows of {len(qc)}, got {tuple(iq.shape)}")
+            if run:
+                iq, col0, ncols = iq.contiguous(), qc[0], len(qc)
+            else:
+                cur = _rows(mir.get_state()[0][:, :mir.n_arm], idx).clone()
+                cur[:, torch.as_tensor(qc, dtype=torch.long, device=mir.device)] = iq
+                iq = cur
+        dof_mask = None
+        if dofs_idx_local is not None:
+            dof_mask = [False] * mir.n_arm
+            for i in np.asarray(dofs_idx_local).ravel():
+                if not -self.n_dofs <= int(i) < self.n_dofs:
+                    raise IndexError(f"dofs_idx_local: {int(i)} outside the entity's {self.n_dofs} dofs")
+                dof_mask[qc[int(i)]] = True
+        res = fn(bodies, p, q, iq, env_idx=idx, flags=flags, init_col0=col0, init_ncols=ncols, pos_mask=tuple(bool(v) for v in pos_mask),
+                 rot_mask=tuple(bool(v) for v in rot_mask), dof_mask=dof_mask, max_samples=int(max_samples), seed=int(seed),
+                 return_error=return_error, **opts)
+        qout, err = (res if return_error else (res, None))
+        qout = self._cols(qout).contiguous()
+        return (qout, err) if return_error else qout
+
+    def inverse_kinematics(self, link, pos=None, quat=None, init_qpos=None, envs_idx=None, return_error=False, pos_mask=(True, True, True),
+                           rot_mask=(True, True, True), dofs_idx_local=None, max_samples=1, seed=0, **opts):
         """``robot.inverse_kinematics(link=eef, pos=(B,3), quat=(B,4), init_qpos=..., envs_idx=...)`` -> (B, n_dofs)
         (/root/reference/examples/franka/pick_cube_state.py:46-51).  One batched launch for all envs; `envs_idx` selects
         the rows returned (and addressed by pos / quat / init_qpos) as in Genesis.  `pos` is required (a quat-only target
@@ -495,6 +569,12 @@ class EntityView:
         their loops: that case costs the launch and one row gather -- no scatter, no clone, no index upload.)"""
         if pos is None:
             raise ValueError("inverse_kinematics needs a target position")
+        if not (all(bool(v) for v in pos_mask) and all(bool(v) for v in rot_mask) and dofs_idx_local is None and int(max_samples) == 1 and int(seed) == 0):
+            # Genesis's further arguments: the multi-link kernel with one link (every argument addressed by row, see there)
+            res = self.inverse_kinematics_multilink([link], [pos], None if quat is None else [quat], init_qpos=init_qpos, envs_idx=envs_idx,
+                                                    pos_mask=pos_mask, rot_mask=rot_mask, dofs_idx_local=dofs_idx_local, max_samples=max_samples,
+                                                    seed=seed, return_error=return_error, **opts)
+            return (res[0], res[1][:, 0].contiguous()) if return_error else res
         mir = self._mir
         B = mir.num_envs
         idx = None if envs_idx is None else torch.as_tensor(envs_idx, device=mir.device).long().reshape(-1)

@@ -805,6 +805,65 @@ typedef struct MirIkRows {
 int mir_inverse_kinematics_rows(MirHandle h, int32_t link_body, const MirIkRows* rows, const float* target_pos, const float* target_quat,
                                 const float* init_qpos, const MirIkOptions* opt, float* qpos_out, float* err_out, void* stream);
 
+/* ---- multi-link inverse kinematics: axis masks, dof subsets, restarts ------------------------------------------
+ * robot.inverse_kinematics(link, pos, quat, pos_mask=..., rot_mask=..., dofs_idx_local=..., max_samples=...) and
+ * robot.inverse_kinematics_multilink(links=[left_finger, right_finger], poss=..., quats=...) of Genesis (parity with Genesis itself is
+ * unpinned, the one-axis rule below included: the package is not in the reference tree; the argument names follow its API as far as it
+ * is remembered).  ONE launch of a kernel of its own (csrc/mir_ikm.hip; mir_inverse_kinematics and its kernel are untouched and keep
+ * their bits).  The scene state is read and never written.  Restated independently by tests/ikm_ref.py.
+ * It is the iteration of mir_inverse_kinematics with these generalisations, for the L = n_links links (1 .. 4) at once:
+ *   Task rows of link l.  ep_l = pos_mask o (p*_l - p_l) in world axes, the linear Jacobian rows masked alike.  Orientation:
+ *     rot_mask all true:  er_l = rotvec(q*_l q_l^-1) as in mir_inverse_kinematics, rows = the angular Jacobian J_w;
+ *     one true entry k:   align the link's own axis k with the target's: a = R_l e_k, a* = R*_l e_k,
+ *                         er_l = atan2(|a x a*|, a . a*) (a x a*) / |a x a*|, 0 when |a x a*| < 1e-9; rows = (I - a a^T) J_w, so the
+ *                         rotation about the axis is free;
+ *     no true entry, or target_quat == NULL: no orientation rows (whatever rot_mask says).
+ *     Two true entries: MIR_E_INVALID.  The masks are shared by all links.
+ *   Metric m = sum_l (|ep_l| / pos_tol + |er_l| / rot_tol).  A row is converged when every link has |ep_l| < pos_tol and |er_l| < rot_tol
+ *     at the accepted iterate.  The accept / reject / stall rules, the lambda^2 schedule, the max_step scaling, the clamp to the joint
+ *     ranges and max_iters are those of mir_inverse_kinematics, word for word.
+ *   Moving joints: the scalar joints on the chain of at least one link that are also in dof_mask.  Every other entry of the result is
+ *     the seed, bit for bit.
+ *   Limit rule (only with respect_joint_limit), evaluated when an iterate is accepted, with g = J^T e of that iterate: a limited moving
+ *     joint j with q_j == lo_j and g_j < 0, or q_j == hi_j and g_j > 0, has a zero Jacobian column until the next accepted iterate (the
+ *     equality is exact: the clamp produced the value).  Without it a joint on its limit keeps being asked to move past it and the
+ *     others creep.
+ *   Step dq = J^T (J J^T + lambda^2 I)^-1 e = (J^T J + lambda^2 I)^-1 J^T e (the kernel solves the second form; lambda^2 >= damping^2 / 256
+ *     keeps the matrix positive definite where the task rows are rank deficient: two rigidly related links, the one-axis projector).
+ *   Samples (max_samples >= 1).  Sample 0 starts from the seed.  Sample s >= 1 replaces every moving joint that has a range, of
+ *     column k, by lo + (hi - lo) u; joints without a range keep the seed value.  u = (x >> 8) 2^-24 with, in uint32 arithmetic,
+ *       x = seed 0x9E3779B1 + env 0x85EBCA77 + s 0xC2B2AE3D + k 0x27D4EB2F + 0x165667B1;
+ *       x ^= x >> 16; x *= 0x7FEB352D; x ^= x >> 15; x *= 0x846CA68B; x ^= x >> 16     (env: the env index, not the row).
+ *     The first converged sample is the result; if none converges, the sample with the smallest final m, the lower s on a tie.  The
+ *     same arguments give the same bits on every call.
+ * Rows are addressed as in mir_inverse_kinematics_rows (q->rows; env_idx NULL: n_rows = num_envs, row k = env k; an index outside the
+ * batch is clamped).  target_pos (rows or num_envs, L, 3); target_quat (rows or num_envs, L, 4) wxyz, or with MIR_IK_QUAT_ONE (L, 4)
+ * for every row, or NULL; init_qpos as in mir_inverse_kinematics_rows.  qpos_out (rows, n_arm); err_out (rows, L, 2) nullable = |ep_l|,
+ * |er_l| of the result; iters_out (rows) nullable = iterations summed over the samples the row ran; sample_out (rows) nullable = the
+ * sample that produced the result.  Each output element is written once.
+ * MIR_E_INVALID: a NULL handle, query, target_pos or qpos_out; struct_size != sizeof(MirIkMulti); n_links outside 1 .. 4; a link outside
+ * 1 .. nbody - 1 or hanging off a free body; two true entries in rot_mask; masks that select no task row at all; max_samples < 1; bad
+ * options; a bad row description or init columns outside the joint row.  MIR_E_CAPACITY: the union of the chains, with the fixed
+ * elements that are no target folded into their children, has more than 16 elements.  n_rows == 0: MIR_OK without a launch.
+ * (An added struct and entry point: MIR_VERSION and every other struct stay as they are.) */
+typedef struct MirIkMulti {
+  int32_t struct_size;      /* = sizeof(MirIkMulti) */
+  int32_t n_links;          /* 1 .. 4 */
+  int32_t link_body[4];     /* body indices of the spec, 1 .. nbody-1 */
+  uint8_t pos_mask[3];      /* world axes x y z of the position error */
+  uint8_t rot_mask[3];      /* 0, 1 or 3 true entries */
+  uint8_t reserved[2];
+  const uint8_t* dof_mask;  /* HOST, n_arm bytes: joint column k may move; NULL: every joint on a chain */
+  int32_t max_samples;      /* >= 1 */
+  uint32_t seed;
+  MirIkRows rows;
+} MirIkMulti;
+int mir_ik_multi_sizeof(void);
+int mir_inverse_kinematics_multilink(MirHandle h, const MirIkMulti* q, const float* target_pos, const float* target_quat /* nullable */,
+                                     const float* init_qpos /* nullable */, const MirIkOptions* opt /* nullable */,
+                                     float* qpos_out, float* err_out /* nullable */, int32_t* iters_out /* nullable */,
+                                     int32_t* sample_out /* nullable */, void* stream);
+
 /* ---- multi-GPU observation gather on the copy path (no reference counterpart: README.md:41-48 is single-device) ----
  * One process per GPU; every rank owns a receive buffer that the other ranks have mapped through HIP IPC (the host side does the
  * handle exchange: gym_genesis/sharding.py: CopyPathGather).  mir_p2p_push enqueues, on `stream` of the CURRENT device, one
