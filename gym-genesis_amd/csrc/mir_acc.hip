@@ -33,116 +33,72 @@
 #define G 16
 #include "mir_dev.h"
 
+#include "mir_query.h"
+
 namespace {
 
-constexpr int ACC_NO_DOF = 0xff;
-
 struct AccArgs {
-  // element j of link l's path: body | jtype << 8 | first dof of the body << 16 (ACC_NO_DOF: none)
-  uint32_t elem[MIR_MAX_BODY][G];
-  uint8_t n[MIR_MAX_BODY];          // bodies on the path of link l
+  LinkPaths paths;
   float local_point[MIR_MAX_BODY][3];
   float quat_offset[MIR_MAX_BODY][4];  // unit
-  int n_links, n_max;               // n_max: the longest path (how many scan steps the wave takes)
+  int n_links;
   int n_rows, B, qst, vst, nv;
   float gx, gy, gz;
   const long long* env_idx;
   const float *qpos, *qvel;         // the scene's state (storage layout)
   const float* qacc;                // the caller's rows (public layout), nullable: zeros
-  // per-body constants of the device model (DevModel or DevModel64: same shapes)
-  const float *b_pos, *b_quat, *b_axis;  // [.][3], [.][4], [.][3]
-  const int32_t* b_qadr;
-  const int32_t* d_lane;            // PlumbTab::d_lane: dof -> column of the qvel row
+  JointPtrs m;
   float *acc, *bias, *imu;
 };
 static_assert(sizeof(AccArgs) <= 4096, "kernel arguments");
 
-__device__ __forceinline__ V3 shr1(V3 v) { return v3(row_shr<1>(v.x), row_shr<1>(v.y), row_shr<1>(v.z)); }
-__device__ __forceinline__ V3 gather3(int src4, V3 v) { return v3(lane_gather(src4, v.x), lane_gather(src4, v.y), lane_gather(src4, v.z)); }
-__device__ __forceinline__ V3 gsum3(V3 v) { return v3(gsum(v.x), gsum(v.y), gsum(v.z)); }
 __device__ __forceinline__ float pick6(int lane, V3 lin, V3 ang) {
   return lane == 0 ? lin.x : (lane == 1 ? lin.y : (lane == 2 ? lin.z : (lane == 3 ? ang.x : (lane == 4 ? ang.y : ang.z))));
 }
 
+// inclusive prefix sum of a vector over the row (row_shr shifts zeros in: no lane test); n_max is uniform over the launch
+template <int D>
+__device__ __forceinline__ V3 psum_step(V3 v) { return v + v3(row_shr<D>(v.x), row_shr<D>(v.y), row_shr<D>(v.z)); }
+__device__ __forceinline__ V3 psum3(V3 v, int n_max) {
+  if (n_max > 1) v = psum_step<1>(v);
+  if (n_max > 2) v = psum_step<2>(v);
+  if (n_max > 4) v = psum_step<4>(v);
+  if (n_max > 8) v = psum_step<8>(v);
+  return v;
+}
+
 __global__ __launch_bounds__(64) void mir_acc_kernel(AccArgs a) {
-  const int tid = threadIdx.x, lane = tid & 15, grp = tid >> 4;
-  const int n_pairs = a.n_rows * a.n_links;
-  const int pair_raw = blockIdx.x * 4 + grp;
-  const bool valid = pair_raw < n_pairs;
-  const int pair = valid ? pair_raw : n_pairs - 1;
-  const int row = pair / a.n_links, li = pair - row * a.n_links;
-  int env = a.env_idx ? (int)a.env_idx[row] : row;
-  env = env < 0 ? 0 : (env >= a.B ? a.B - 1 : env);  // (an index outside the batch is clamped, not followed)
-  const int n = a.n[li];
-  const int last4 = ((tid & ~15) + n - 1) << 2;  // (lane_gather address of the path's last element in this pair's row)
-  const bool onpath = lane < n;
-  const uint32_t el = onpath ? a.elem[li][lane] : (uint32_t)(MIR_JNT_FIXED << 8 | ACC_NO_DOF << 16);
-  const int body = el & 0xff, jt = (el >> 8) & 0xff, dof = (el >> 16) & 0xff;
-  const float* const qrow = a.qpos + (size_t)env * a.qst;
-  const float* const vrow = a.qvel + (size_t)env * a.vst;
+  const PairLane t = pair_decode(a, a.n_links);
+  const int lane = t.lane, pair = t.pair, row = t.row, li = t.item;
+  const bool valid = t.valid;
+  const PathLane e = path_lane(a.paths, li, lane);
+  const int last4 = e.last4, jt = e.jt, dof = e.dof;
+  const bool onpath = e.onpath;
+  const float* const qrow = a.qpos + (size_t)t.env * a.qst;
+  const float* const vrow = a.qvel + (size_t)t.env * a.vst;
   const float* const arow = a.qacc ? a.qacc + (size_t)row * a.nv : nullptr;
-  // ---- local transform of my path element (identity off the path), as mir_kin.hip
-  V3 P = v3(0, 0, 0), baxis = v3(0, 0, 0);
-  Q4 Qx = Q4{1, 0, 0, 0};
-  if (onpath) {
-    const int qa = a.b_qadr[body];
-    if (jt == MIR_JNT_FREE) {
-      P = ld3(qrow + qa);
-      Qx = qnormalize(ld4(qrow + qa + 3));
-    } else {
-      const Q4 bquat = ld4(a.b_quat + body * 4);
-      P = ld3(a.b_pos + body * 3);
-      Qx = bquat;
-      baxis = ld3(a.b_axis + body * 3);
-      if (jt == MIR_JNT_REVOLUTE) {
-        float sn, cs;
-        sincos_pi2(0.5f * qrow[qa], &sn, &cs);
-        Qx = qmul(bquat, Q4{cs, baxis.x * sn, baxis.y * sn, baxis.z * sn});
-      } else if (jt == MIR_JNT_PRISMATIC) {
-        P = P + qrot(bquat, qrow[qa] * baxis);
-      }
-    }
-  }
-  // ---- my prefix of the path by a log-step scan over the DPP row ((P,Q) o (p,q) = (P + Q p, Q q) is associative)
-#define ACC_SCAN_STEP(D)                                                                                       \
-  {                                                                                                            \
-    const V3 pp = v3(row_shr<D>(P.x), row_shr<D>(P.y), row_shr<D>(P.z));                                       \
-    const Q4 pq = Q4{row_shr<D>(Qx.w), row_shr<D>(Qx.x), row_shr<D>(Qx.y), row_shr<D>(Qx.z)};                  \
-    if (lane >= D) {                                                                                           \
-      P = pp + qrot(pq, P);                                                                                    \
-      Qx = qmul(pq, Qx);                                                                                       \
-    }                                                                                                          \
-  }
-  if (a.n_max > 1) ACC_SCAN_STEP(1)
-  if (a.n_max > 2) ACC_SCAN_STEP(2)
-  if (a.n_max > 4) ACC_SCAN_STEP(4)
-  if (a.n_max > 8) ACC_SCAN_STEP(8)
-#undef ACC_SCAN_STEP
-  // inclusive prefix sum of a vector over the row (row_shr shifts zeros in: no lane test)
-#define ACC_PSUM_STEP(D, V) V = V + v3(row_shr<D>(V.x), row_shr<D>(V.y), row_shr<D>(V.z));
-#define ACC_PSUM(V)                      \
-  {                                      \
-    if (a.n_max > 1) ACC_PSUM_STEP(1, V) \
-    if (a.n_max > 2) ACC_PSUM_STEP(2, V) \
-    if (a.n_max > 4) ACC_PSUM_STEP(4, V) \
-    if (a.n_max > 8) ACC_PSUM_STEP(8, V) \
-  }
+  // ---- local transform of my path element (identity off the path), my prefix of the path
+  const JointLocal jl0 = joint_local(onpath, e.body, jt, qrow, a.m);
+  const V3 baxis = jl0.baxis;
+  const Pose me = path_scan(Pose{jl0.P, jl0.Qx}, lane, a.paths.n_max);
+  const V3 P = me.P;
+  const Q4 Qx = me.Qx;
   // ---- the link's rotation in every lane of the row, the queried point relative to the link's origin
-  const Q4 ql = qnormalize(Q4{lane_gather(last4, Qx.w), lane_gather(last4, Qx.x), lane_gather(last4, Qx.y), lane_gather(last4, Qx.z)});
+  const Q4 ql = qnormalize(gather4(last4, Qx));
   const V3 r = qrot(ql, ld3(a.local_point[li]));
   // ---- my element's joint: world axis, qd, qdd (a free root: its four vectors)
-  const bool hasdof = onpath && dof != ACC_NO_DOF;
+  const bool hasdof = onpath && dof != NO_DOF;
   const bool rev = hasdof && jt == MIR_JNT_REVOLUTE, pri = hasdof && jt == MIR_JNT_PRISMATIC, free6 = hasdof && jt == MIR_JNT_FREE;
   V3 axw = v3(0, 0, 0), s = v3(0, 0, 0), fvd = v3(0, 0, 0), fwd = v3(0, 0, 0);
   float qd = 0.0f, qdd = 0.0f;
   if (rev || pri) {
     axw = qrot(Qx, baxis);
-    qd = vrow[a.d_lane[dof]];
+    qd = vrow[a.m.d_lane[dof]];
     qdd = arow ? arow[dof] : 0.0f;
     if (rev) s = qd * axw;
   }
   if (free6) {
-    s = v3(vrow[a.d_lane[dof + 3]], vrow[a.d_lane[dof + 4]], vrow[a.d_lane[dof + 5]]);
+    s = v3(vrow[a.m.d_lane[dof + 3]], vrow[a.m.d_lane[dof + 4]], vrow[a.m.d_lane[dof + 5]]);
     if (arow) {
       fvd = ld3(arow + dof);
       fwd = ld3(arow + dof + 3);
@@ -150,7 +106,7 @@ __global__ __launch_bounds__(64) void mir_acc_kernel(AccArgs a) {
   }
   // ---- angular velocities: w_j inclusive, w_{j-1} exclusive
   V3 wi = s;
-  ACC_PSUM(wi)
+  wi = psum3(wi, a.paths.n_max);
   const V3 wp = shr1(wi);
   // ---- angular accelerations, the part without qacc (b) and the part linear in it (a)
   const V3 wxa = cross(wp, axw);
@@ -159,11 +115,9 @@ __global__ __launch_bounds__(64) void mir_acc_kernel(AccArgs a) {
     ab = qd * wxa;
     aa = qdd * axw;
   }
-  ACC_PSUM(ab)
-  ACC_PSUM(aa)
+  ab = psum3(ab, a.paths.n_max);
+  aa = psum3(aa, a.paths.n_max);
   const V3 abp = shr1(ab), aap = shr1(aa);
-#undef ACC_PSUM
-#undef ACC_PSUM_STEP
   // ---- my element's step of the origin's acceleration
   const V3 d = P - shr1(P);  // (lane 0: from the world's origin, which does not move)
   V3 tb = v3(0, 0, 0), ta = fvd;
@@ -213,26 +167,9 @@ extern "C" int mir_link_accelerations(MirHandle h, const MirAccQuery* q, const i
   if (env_idx && n_rows < 0) return mir_set_error(MIR_E_INVALID, "mir_link_accelerations: negative n_rows");
   AccArgs a;
   memset(&a, 0, sizeof a);
-  const bool k16 = h->kernel == 16;
-  auto parent = [&](int b) { return k16 ? h->hm.b_parent[b] : h->hm64.b_parent[b]; };
-  auto jtype = [&](int b) { return k16 ? h->hm.b_jtype[b] : h->hm64.b_jtype[b]; };
-  // first dof of a body in the scene's dof order (the wave kernel's model addresses dofs by lane: d_dof maps back)
-  auto dofadr = [&](int b) { return k16 ? h->hm.b_dofadr[b] : h->hm64.d_dof[h->hm64.b_dofadr[b]]; };
+  // (only here: a free body's qvel is a world velocity whatever is above it, so a free joint below another body is refused)
+  if (int rc = build_link_paths(h, q->link_body, q->n_links, "mir_link_accelerations", true, a.paths)) return rc;
   for (int l = 0; l < q->n_links; l++) {
-    int path[G], n = 0;
-    for (int b = q->link_body[l]; b > 0; b = parent(b)) {
-      if (n >= G) return mir_set_error(MIR_E_CAPACITY, "mir_link_accelerations: path longer than 16 bodies");
-      // (a free body's qvel is a world velocity whatever is above it: below another body the path would mix two conventions)
-      if (jtype(b) == MIR_JNT_FREE && parent(b) != 0) return mir_set_error(MIR_E_INVALID, "mir_link_accelerations: a free joint below another body");
-      path[n++] = b;
-    }
-    for (int i = 0; i < n; i++) {
-      const int b = path[n - 1 - i], jt = jtype(b);
-      const int d = jt == MIR_JNT_FIXED ? ACC_NO_DOF : dofadr(b);
-      a.elem[l][i] = (uint32_t)b | (uint32_t)jt << 8 | (uint32_t)d << 16;
-    }
-    a.n[l] = (uint8_t)n;
-    if (n > a.n_max) a.n_max = n;
     for (int k = 0; k < 3; k++) a.local_point[l][k] = q->local_point[l][k];
     double n2 = 0.0;
     for (int k = 0; k < 4; k++) n2 += (double)q->quat_offset[l][k] * q->quat_offset[l][k];
@@ -243,24 +180,13 @@ extern "C" int mir_link_accelerations(MirHandle h, const MirAccQuery* q, const i
   if (R == 0 || (!acc && !bias_acc && !imu)) return MIR_OK;  // (nothing asked for)
   a.n_links = q->n_links;
   a.n_rows = R; a.B = h->B; a.qst = h->pt.qst; a.vst = h->pt.vst; a.nv = h->nv;
-  a.gx = k16 ? h->hm.gx : h->hm64.gx; a.gy = k16 ? h->hm.gy : h->hm64.gy; a.gz = k16 ? h->hm.gz : h->hm64.gz;
+  const ModelView mv(h);
+  mv.gravity(a.gx, a.gy, a.gz);
   a.env_idx = reinterpret_cast<const long long*>(env_idx);
   a.qpos = h->qpos; a.qvel = h->qvel; a.qacc = qacc;
-  const char* const dm = k16 ? reinterpret_cast<const char*>(h->dm) : reinterpret_cast<const char*>(h->dm64);
-  a.b_pos = reinterpret_cast<const float*>(dm + (k16 ? offsetof(DevModel, b_pos) : offsetof(DevModel64, b_pos)));
-  a.b_quat = reinterpret_cast<const float*>(dm + (k16 ? offsetof(DevModel, b_quat) : offsetof(DevModel64, b_quat)));
-  a.b_axis = reinterpret_cast<const float*>(dm + (k16 ? offsetof(DevModel, b_axis) : offsetof(DevModel64, b_axis)));
-  a.b_qadr = reinterpret_cast<const int32_t*>(dm + (k16 ? offsetof(DevModel, b_qadr) : offsetof(DevModel64, b_qadr)));
-  a.d_lane = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(h->dpt) + offsetof(PlumbTab, d_lane));
+  a.m = mv.joint_pointers();
   a.acc = acc; a.bias = bias_acc; a.imu = imu;
   const long long n_pairs = (long long)R * q->n_links;
   if (n_pairs > 0x7fffffffLL - 4) return mir_set_error(MIR_E_CAPACITY, "mir_link_accelerations: rows x links reaches 2^31");
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != h->device) (void)hipSetDevice(h->device);
-  hipLaunchKernelGGL(mir_acc_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(64), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  if (prev != h->device && prev >= 0) (void)hipSetDevice(prev);
-  if (e != hipSuccess) return mir_set_error(MIR_E_HIP, hipGetErrorString(e));
-  return MIR_OK;
+  return launch_rows(h, mir_acc_kernel, (n_pairs + 3) / 4, stream, a);
 }

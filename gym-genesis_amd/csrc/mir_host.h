@@ -1,8 +1,10 @@
 // mir_host.h — what the host code of the step path shares between mir_api.hip (the C ABI, begin / go / end) and mir_exact.hip (the
-// launches and waits of exact contacts): error plumbing, the device guard, the launch arguments and the poller.
+// launches and waits of exact contacts): error plumbing, the launch arguments and the poller.  The device guard they and the query
+// files take is in mir_guard.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "mir_guard.h"
 #include "mir_scene.h"
 #include "mir_step.h"
 
@@ -17,16 +19,7 @@ int hip_fail(hipError_t e, const char* what);
     if (_e != hipSuccess) return hip_fail(_e, #call);  \
   } while (0)
 
-struct DeviceGuard {
-  int prev = -1;
-  bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-  }
-  ~DeviceGuard() {
-    if (switched) (void)hipSetDevice(prev);
-  }
-};
+using ::DeviceGuard;  // (mir_guard.h)
 
 inline int check(MirHandle h) {
   if (!h) return set_err(MIR_E_INVALID, "null MirHandle");

@@ -21,6 +21,8 @@
 #define G 16
 #include "mir_dev.h"
 
+#include "mir_query.h"
+
 namespace {
 
 struct IkChain {
@@ -243,8 +245,8 @@ extern "C" int mir_inverse_kinematics_rows(MirHandle h, int32_t link_body, const
   memset(&a, 0, sizeof a);
   // chain world -> link from whichever model serves the scene
   int chain[MIR_MAX_BODY], n = 0;
-  auto parent = [&](int b) { return h->kernel == 16 ? h->hm.b_parent[b] : h->hm64.b_parent[b]; };
-  for (int b = link_body; b > 0; b = parent(b)) {
+  const ModelView mv(h);
+  for (int b = link_body; b > 0; b = mv.parent(b)) {
     if (n >= G) return mir_set_error(MIR_E_CAPACITY, "mir_inverse_kinematics: chain longer than 16 bodies");
     chain[n++] = b;
   }
@@ -253,25 +255,19 @@ extern "C" int mir_inverse_kinematics_rows(MirHandle h, int32_t link_body, const
   int col_of_body[MIR_MAX_BODY];
   int narm = 0;
   for (int b = 1; b < h->nbody; b++) {
-    const int jt = h->kernel == 16 ? h->hm.b_jtype[b] : h->hm64.b_jtype[b];
+    const int jt = mv.jtype(b);
     col_of_body[b] = (jt == MIR_JNT_REVOLUTE || jt == MIR_JNT_PRISMATIC) ? narm++ : -1;
-    if (col_of_body[b] >= 0) a.arm_qadr[col_of_body[b]] = h->kernel == 16 ? h->hm.b_qadr[b] : h->hm64.b_qadr[b];
+    if (col_of_body[b] >= 0) a.arm_qadr[col_of_body[b]] = mv.qadr(b);
   }
   for (int i = 0; i < n; i++) {
     const int b = chain[n - 1 - i];
-    int jt;
-    if (h->kernel == 16) {
-      const DevModel& m = h->hm;
-      jt = m.b_jtype[b];
-      for (int k = 0; k < 3; k++) { a.ch.pos[i][k] = m.b_pos[b][k]; a.ch.axis[i][k] = m.b_axis[b][k]; }
-      for (int k = 0; k < 4; k++) a.ch.quat[i][k] = m.b_quat[b][k];
-      if (col_of_body[b] >= 0) { const int d = m.b_dofadr[b]; a.ch.lo[i] = m.d_lo[d]; a.ch.hi[i] = m.d_hi[d]; a.ch.limited[i] = m.d_limited[d]; }
-    } else {
-      const DevModel64& m = h->hm64;
-      jt = m.b_jtype[b];
-      for (int k = 0; k < 3; k++) { a.ch.pos[i][k] = m.b_pos[b][k]; a.ch.axis[i][k] = m.b_axis[b][k]; }
-      for (int k = 0; k < 4; k++) a.ch.quat[i][k] = m.b_quat[b][k];
-      if (col_of_body[b] >= 0) { const int d = m.b_dofadr[b]; a.ch.lo[i] = m.d_lo[d]; a.ch.hi[i] = m.d_hi[d]; a.ch.limited[i] = m.d_limited[d]; }
+    const int jt = mv.jtype(b);
+    for (int k = 0; k < 3; k++) { a.ch.pos[i][k] = mv.body_pos(b)[k]; a.ch.axis[i][k] = mv.body_axis(b)[k]; }
+    for (int k = 0; k < 4; k++) a.ch.quat[i][k] = mv.body_quat(b)[k];
+    if (col_of_body[b] >= 0) {
+      double lo, hi;
+      mv.limits(b, lo, hi, a.ch.limited[i]);
+      a.ch.lo[i] = (float)lo; a.ch.hi[i] = (float)hi;
     }
     if (jt == MIR_JNT_FREE) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics: the link hangs off a free body");
     a.ch.jtype[i] = jt;
@@ -335,14 +331,7 @@ extern "C" int mir_inverse_kinematics_rows(MirHandle h, int32_t link_body, const
   a.iters_out = h->dbg_ik_iters;
   a.max_iters = o.max_iters; a.respect_limits = o.respect_joint_limit;
   a.damping2 = (float)(o.damping * o.damping); a.pos_tol = (float)o.pos_tol; a.rot_tol = (float)o.rot_tol; a.inv_pos_tol = (float)(1.0 / o.pos_tol); a.inv_rot_tol = (float)(1.0 / o.rot_tol); a.max_step = (float)o.max_step;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != h->device) (void)hipSetDevice(h->device);
-  hipLaunchKernelGGL(mir_ik_kernel, dim3((a.n_rows + 3) / 4), dim3(64), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  if (prev != h->device && prev >= 0) (void)hipSetDevice(prev);
-  if (e != hipSuccess) return mir_set_error(MIR_E_HIP, hipGetErrorString(e));
-  return MIR_OK;
+  return launch_rows(h, mir_ik_kernel, (a.n_rows + 3) / 4, stream, a);
 }
 
 extern "C" int mir_inverse_kinematics(MirHandle h, int32_t link_body, const float* target_pos, const float* target_quat, const float* init_qpos,
@@ -370,11 +359,9 @@ __global__ __launch_bounds__(64) void k_debug_row_sum(const float* __restrict__ 
 }  // namespace
 extern "C" int mir_debug_row_sum(const float* in, float* out, int32_t n_rows, int device_id, void* stream) {
   if (!in || !out || n_rows <= 0) return mir_set_error(MIR_E_INVALID, "mir_debug_row_sum: bad argument");
-  int prev = -1;
-  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != device_id && hipSetDevice(device_id) == hipSuccess;
+  DeviceGuard guard(device_id);
   hipLaunchKernelGGL(k_debug_row_sum, dim3((n_rows * 16 + 63) / 64), dim3(64), 0, (hipStream_t)stream, in, out, n_rows);
   const hipError_t e = hipGetLastError();
-  if (sw) (void)hipSetDevice(prev);
   return e == hipSuccess ? MIR_OK : mir_set_error(MIR_E_HIP, hipGetErrorString(e));
 }
 

@@ -30,6 +30,8 @@
 #define G 16
 #include "mir_dev.h"
 
+#include "mir_query.h"
+
 namespace {
 
 constexpr int IKM_L = 4;  // links per call
@@ -362,8 +364,7 @@ extern "C" int mir_inverse_kinematics_multilink(MirHandle h, const MirIkMulti* m
       return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics_multilink: bad options");
   }
   const int nbody = h->nbody;
-  auto parent = [&](int b) { return h->kernel == 16 ? h->hm.b_parent[b] : h->hm64.b_parent[b]; };
-  auto jtype = [&](int b) { return h->kernel == 16 ? h->hm.b_jtype[b] : h->hm64.b_jtype[b]; };
+  const ModelView mv(h);
   // the union of the chains world -> link_l, with each body's depth
   int depth[MIR_MAX_BODY];
   bool inu[MIR_MAX_BODY], target[MIR_MAX_BODY];
@@ -373,22 +374,22 @@ extern "C" int mir_inverse_kinematics_multilink(MirHandle h, const MirIkMulti* m
     if (lb <= 0 || lb >= nbody) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics_multilink: link out of range");
     target[lb] = true;
     int steps = 0;
-    for (int b = lb; b > 0; b = parent(b)) {
-      if (jtype(b) == MIR_JNT_FREE) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics_multilink: the link hangs off a free body");
+    for (int b = lb; b > 0; b = mv.parent(b)) {
+      if (mv.jtype(b) == MIR_JNT_FREE) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics_multilink: the link hangs off a free body");
       if (++steps > MIR_MAX_BODY) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics_multilink: parent cycle");
       inu[b] = true;
     }
   }
   for (int b = 1; b < nbody; b++)
-    if (inu[b]) { int d = 0; for (int c = b; c > 0; c = parent(c)) d++; depth[b] = d; }
+    if (inu[b]) { int d = 0; for (int c = b; c > 0; c = mv.parent(c)) d++; depth[b] = d; }
   // columns of the scalar joints in the (rows, n_arm) arrays = their rank in body order
   IkmArgs a;
   memset(&a, 0, sizeof a);
   int col_of_body[MIR_MAX_BODY], narm = 0;
   for (int b = 1; b < nbody; b++) {
-    const int jt = jtype(b);
+    const int jt = mv.jtype(b);
     col_of_body[b] = (jt == MIR_JNT_REVOLUTE || jt == MIR_JNT_PRISMATIC) ? narm++ : -1;
-    if (col_of_body[b] >= 0) a.arm_qadr[col_of_body[b]] = h->kernel == 16 ? h->hm.b_qadr[b] : h->hm64.b_qadr[b];
+    if (col_of_body[b] >= 0) a.arm_qadr[col_of_body[b]] = mv.qadr(b);
   }
   if (rows->init_ncols > 0 && (rows->init_col0 < 0 || rows->init_col0 + rows->init_ncols > narm))
     return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics_multilink: init columns outside the joint row");
@@ -405,18 +406,10 @@ extern "C" int mir_inverse_kinematics_multilink(MirHandle h, const MirIkMulti* m
       if (!inu[b] || depth[b] != d) continue;
       double p[3], q[4], ax[3], lo = 0, hi = 0;
       int limited = 0;
-      if (h->kernel == 16) {
-        const DevModel& m = h->hm;
-        for (int k = 0; k < 3; k++) { p[k] = m.b_pos[b][k]; ax[k] = m.b_axis[b][k]; }
-        for (int k = 0; k < 4; k++) q[k] = m.b_quat[b][k];
-        if (col_of_body[b] >= 0) { const int dd = m.b_dofadr[b]; lo = m.d_lo[dd]; hi = m.d_hi[dd]; limited = m.d_limited[dd]; }
-      } else {
-        const DevModel64& m = h->hm64;
-        for (int k = 0; k < 3; k++) { p[k] = m.b_pos[b][k]; ax[k] = m.b_axis[b][k]; }
-        for (int k = 0; k < 4; k++) q[k] = m.b_quat[b][k];
-        if (col_of_body[b] >= 0) { const int dd = m.b_dofadr[b]; lo = m.d_lo[dd]; hi = m.d_hi[dd]; limited = m.d_limited[dd]; }
-      }
-      const int pb = parent(b);
+      for (int k = 0; k < 3; k++) { p[k] = mv.body_pos(b)[k]; ax[k] = mv.body_axis(b)[k]; }
+      for (int k = 0; k < 4; k++) q[k] = mv.body_quat(b)[k];
+      if (col_of_body[b] >= 0) mv.limits(b, lo, hi, limited);
+      const int pb = mv.parent(b);
       int pe = -1;
       if (pb > 0 && folded[pb]) {  // my base transform behind the folded parent's
         const double v[4] = {0, p[0], p[1], p[2]}, *cq = fq[pb];
@@ -429,7 +422,7 @@ extern "C" int mir_inverse_kinematics_multilink(MirHandle h, const MirIkMulti* m
       } else if (pb > 0) {
         pe = el_of[pb];
       }
-      if (jtype(b) == MIR_JNT_FIXED && !target[b]) {
+      if (mv.jtype(b) == MIR_JNT_FIXED && !target[b]) {
         folded[b] = true; fold_par[b] = pe;
         for (int k = 0; k < 3; k++) fp[b][k] = p[k];
         for (int k = 0; k < 4; k++) fq[b][k] = q[k];
@@ -438,7 +431,7 @@ extern "C" int mir_inverse_kinematics_multilink(MirHandle h, const MirIkMulti* m
       if (nel >= G) return mir_set_error(MIR_E_CAPACITY, "mir_inverse_kinematics_multilink: the union of the chains has more than 16 elements");
       const int i = nel++;
       el_of[b] = i; par_el[i] = pe;
-      a.tr.jtype[i] = jtype(b); a.tr.qcol[i] = col_of_body[b];
+      a.tr.jtype[i] = mv.jtype(b); a.tr.qcol[i] = col_of_body[b];
       for (int k = 0; k < 3; k++) { a.tr.pos[i][k] = (float)p[k]; a.tr.axis[i][k] = (float)ax[k]; }
       for (int k = 0; k < 4; k++) a.tr.quat[i][k] = (float)q[k];
       a.tr.lo[i] = (float)lo; a.tr.hi[i] = (float)hi; a.tr.limited[i] = limited;
@@ -485,12 +478,5 @@ extern "C" int mir_inverse_kinematics_multilink(MirHandle h, const MirIkMulti* m
   a.max_iters = o.max_iters; a.respect_limits = o.respect_joint_limit;
   a.damping2 = (float)(o.damping * o.damping); a.pos_tol = (float)o.pos_tol; a.rot_tol = (float)o.rot_tol;
   a.inv_pos_tol = (float)(1.0 / o.pos_tol); a.inv_rot_tol = (float)(1.0 / o.rot_tol); a.max_step = (float)o.max_step;
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != h->device) (void)hipSetDevice(h->device);
-  hipLaunchKernelGGL(mir_ikm_kernel, dim3((a.n_rows + 3) / 4), dim3(64), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  if (prev != h->device && prev >= 0) (void)hipSetDevice(prev);
-  if (e != hipSuccess) return mir_set_error(MIR_E_HIP, hipGetErrorString(e));
-  return MIR_OK;
+  return launch_rows(h, mir_ikm_kernel, (a.n_rows + 3) / 4, stream, a);
 }

@@ -30,104 +30,63 @@
 #define G 16
 #include "mir_dev.h"
 
+#include "mir_query.h"
+
 namespace {
 
-constexpr int KIN_NO_DOF = 0xff;
-
 struct KinArgs {
-  // element j of link l's path: body | jtype << 8 | first dof of the body << 16 (KIN_NO_DOF: none)
-  uint32_t elem[MIR_MAX_BODY][G];
-  uint8_t n[MIR_MAX_BODY];          // bodies on the path of link l
+  LinkPaths paths;
   float local_point[MIR_MAX_BODY][3];
-  int n_links, n_max;               // n_max: the longest path (how many scan steps the wave takes)
+  int n_links;
   int dof0, n_dofs;
   int n_rows, B, qst, vst;
   int vec4;                         // jac is 16-byte aligned: the span goes out as float4
   const long long* env_idx;
   const float *qpos, *qvel;
-  // per-body constants of the device model (DevModel or DevModel64: same shapes)
-  const float *b_pos, *b_quat, *b_axis;  // [.][3], [.][4], [.][3]
-  const int32_t* b_qadr;
-  const int32_t* d_lane;            // PlumbTab::d_lane: dof -> column of the qvel row
+  JointPtrs m;
   float *pos, *quat, *vel, *jac;
 };
+static_assert(sizeof(KinArgs) <= 4096, "kernel arguments");
 
 __global__ __launch_bounds__(64) void mir_kin_kernel(KinArgs a) {
   __shared__ float4 jl4[4 * 6 * MIR_MAX_DOF / 4];
   float* const jl = reinterpret_cast<float*>(jl4);
-  const int tid = threadIdx.x, lane = tid & 15, grp = tid >> 4;
+  const PairLane t = pair_decode(a, a.n_links);
+  const int tid = threadIdx.x, lane = t.lane, grp = t.grp, pair = t.pair, li = t.item;
+  const bool valid = t.valid;
   const int n_pairs = a.n_rows * a.n_links;
-  const int pair_raw = blockIdx.x * 4 + grp;
-  const bool valid = pair_raw < n_pairs;
-  const int pair = valid ? pair_raw : n_pairs - 1;
-  const int row = pair / a.n_links, li = pair - row * a.n_links;
-  int env = a.env_idx ? (int)a.env_idx[row] : row;
-  env = env < 0 ? 0 : (env >= a.B ? a.B - 1 : env);  // (an index outside the batch is clamped, not followed: the caller's side checks it)
-  const int n = a.n[li];
-  const int last4 = ((tid & ~15) + n - 1) << 2;  // (lane_gather address of the path's last element in this pair's row)
-  const bool onpath = lane < n;
-  const uint32_t el = onpath ? a.elem[li][lane] : (uint32_t)(MIR_JNT_FIXED << 8 | KIN_NO_DOF << 16);
-  const int body = el & 0xff, jt = (el >> 8) & 0xff, dof = (el >> 16) & 0xff;
-  const float* const qrow = a.qpos + (size_t)env * a.qst;
-  const float* const vrow = a.qvel + (size_t)env * a.vst;
-  // ---- local transform of my path element (identity off the path)
-  V3 P = v3(0, 0, 0), baxis = v3(0, 0, 0);
-  Q4 Qx = Q4{1, 0, 0, 0};
-  if (onpath) {
-    const int qa = a.b_qadr[body];
-    if (jt == MIR_JNT_FREE) {
-      P = ld3(qrow + qa);
-      Qx = qnormalize(ld4(qrow + qa + 3));
-    } else {
-      const Q4 bquat = ld4(a.b_quat + body * 4);
-      P = ld3(a.b_pos + body * 3);
-      Qx = bquat;
-      baxis = ld3(a.b_axis + body * 3);
-      if (jt == MIR_JNT_REVOLUTE) {
-        float sn, cs;
-        sincos_pi2(0.5f * qrow[qa], &sn, &cs);
-        Qx = qmul(bquat, Q4{cs, baxis.x * sn, baxis.y * sn, baxis.z * sn});
-      } else if (jt == MIR_JNT_PRISMATIC) {
-        P = P + qrot(bquat, qrow[qa] * baxis);
-      }
-    }
-  }
-  // ---- my prefix of the path by a log-step scan over the DPP row ((P,Q) o (p,q) = (P + Q p, Q q) is associative)
-#define KIN_SCAN_STEP(D)                                                                                       \
-  {                                                                                                            \
-    const V3 pp = v3(row_shr<D>(P.x), row_shr<D>(P.y), row_shr<D>(P.z));                                       \
-    const Q4 pq = Q4{row_shr<D>(Qx.w), row_shr<D>(Qx.x), row_shr<D>(Qx.y), row_shr<D>(Qx.z)};                  \
-    if (lane >= D) {                                                                                           \
-      P = pp + qrot(pq, P);                                                                                    \
-      Qx = qmul(pq, Qx);                                                                                       \
-    }                                                                                                          \
-  }
-  if (a.n_max > 1) KIN_SCAN_STEP(1)
-  if (a.n_max > 2) KIN_SCAN_STEP(2)
-  if (a.n_max > 4) KIN_SCAN_STEP(4)
-  if (a.n_max > 8) KIN_SCAN_STEP(8)
-#undef KIN_SCAN_STEP
+  const PathLane e = path_lane(a.paths, li, lane);
+  const int last4 = e.last4, jt = e.jt, dof = e.dof;
+  const bool onpath = e.onpath;
+  const float* const qrow = a.qpos + (size_t)t.env * a.qst;
+  const float* const vrow = a.qvel + (size_t)t.env * a.vst;
+  // ---- local transform of my path element (identity off the path), my prefix of the path
+  const JointLocal jl0 = joint_local(onpath, e.body, jt, qrow, a.m);
+  const V3 baxis = jl0.baxis;
+  const Pose me = path_scan(Pose{jl0.P, jl0.Qx}, lane, a.paths.n_max);
+  const V3 P = me.P;
+  const Q4 Qx = me.Qx;
   // ---- the link's pose in every lane of the row (seven lane gathers), the queried point
-  const V3 ol = v3(lane_gather(last4, P.x), lane_gather(last4, P.y), lane_gather(last4, P.z));
-  const Q4 ql = qnormalize(Q4{lane_gather(last4, Qx.w), lane_gather(last4, Qx.x), lane_gather(last4, Qx.y), lane_gather(last4, Qx.z)});
+  const V3 ol = gather3(last4, P);
+  const Q4 ql = qnormalize(gather4(last4, Qx));
   const V3 p = ol + qrot(ql, ld3(a.local_point[li]));
   // ---- my column(s) and my share of J qvel
   const V3 r = p - P;
   float c0[6] = {0, 0, 0, 0, 0, 0}, pv[6] = {0, 0, 0, 0, 0, 0};
-  const bool scalar = onpath && dof != KIN_NO_DOF && (jt == MIR_JNT_REVOLUTE || jt == MIR_JNT_PRISMATIC);
-  const bool free6 = onpath && dof != KIN_NO_DOF && jt == MIR_JNT_FREE;
+  const bool scalar = onpath && dof != NO_DOF && (jt == MIR_JNT_REVOLUTE || jt == MIR_JNT_PRISMATIC);
+  const bool free6 = onpath && dof != NO_DOF && jt == MIR_JNT_FREE;
   if (scalar) {
     const V3 axw = qrot(Qx, baxis);
     V3 jv = axw, jw = v3(0, 0, 0);
     if (jt == MIR_JNT_REVOLUTE) { jw = axw; jv = cross(axw, r); }
     c0[0] = jv.x; c0[1] = jv.y; c0[2] = jv.z; c0[3] = jw.x; c0[4] = jw.y; c0[5] = jw.z;
-    const float qd = vrow[a.d_lane[dof]];
+    const float qd = vrow[a.m.d_lane[dof]];
 #pragma unroll
     for (int k = 0; k < 6; k++) pv[k] = c0[k] * qd;
   }
   if (free6) {
-    const V3 v = v3(vrow[a.d_lane[dof]], vrow[a.d_lane[dof + 1]], vrow[a.d_lane[dof + 2]]);
-    const V3 w = v3(vrow[a.d_lane[dof + 3]], vrow[a.d_lane[dof + 4]], vrow[a.d_lane[dof + 5]]);
+    const V3 v = v3(vrow[a.m.d_lane[dof]], vrow[a.m.d_lane[dof + 1]], vrow[a.m.d_lane[dof + 2]]);
+    const V3 w = v3(vrow[a.m.d_lane[dof + 3]], vrow[a.m.d_lane[dof + 4]], vrow[a.m.d_lane[dof + 5]]);
     const V3 u = v + cross(w, r);
     pv[0] = u.x; pv[1] = u.y; pv[2] = u.z; pv[3] = w.x; pv[4] = w.y; pv[5] = w.z;
   }
@@ -204,26 +163,9 @@ extern "C" int mir_link_kinematics(MirHandle h, const MirKinQuery* q, const int6
   if (env_idx && n_rows < 0) return mir_set_error(MIR_E_INVALID, "mir_link_kinematics: negative n_rows");
   KinArgs a;
   memset(&a, 0, sizeof a);
-  const bool k16 = h->kernel == 16;
-  auto parent = [&](int b) { return k16 ? h->hm.b_parent[b] : h->hm64.b_parent[b]; };
-  auto jtype = [&](int b) { return k16 ? h->hm.b_jtype[b] : h->hm64.b_jtype[b]; };
-  // first dof of a body in the scene's dof order (the wave kernel's model addresses dofs by lane: d_dof maps back)
-  auto dofadr = [&](int b) { return k16 ? h->hm.b_dofadr[b] : h->hm64.d_dof[h->hm64.b_dofadr[b]]; };
-  for (int l = 0; l < q->n_links; l++) {
-    int path[G], n = 0;
-    for (int b = q->link_body[l]; b > 0; b = parent(b)) {
-      if (n >= G) return mir_set_error(MIR_E_CAPACITY, "mir_link_kinematics: path longer than 16 bodies");
-      path[n++] = b;
-    }
-    for (int i = 0; i < n; i++) {
-      const int b = path[n - 1 - i], jt = jtype(b);
-      const int d = jt == MIR_JNT_FIXED ? KIN_NO_DOF : dofadr(b);
-      a.elem[l][i] = (uint32_t)b | (uint32_t)jt << 8 | (uint32_t)d << 16;
-    }
-    a.n[l] = (uint8_t)n;
-    if (n > a.n_max) a.n_max = n;
+  if (int rc = build_link_paths(h, q->link_body, q->n_links, "mir_link_kinematics", false, a.paths)) return rc;
+  for (int l = 0; l < q->n_links; l++)
     for (int k = 0; k < 3; k++) a.local_point[l][k] = q->local_point[l][k];
-  }
   const int R = env_idx ? n_rows : h->B;
   if (q->n_dofs == 0) jac = nullptr;  // (an empty block)
   if (R == 0 || (!pos && !quat && !vel && !jac)) return MIR_OK;  // (nothing asked for)
@@ -232,21 +174,9 @@ extern "C" int mir_link_kinematics(MirHandle h, const MirKinQuery* q, const int6
   a.vec4 = ((uintptr_t)jac & 15) == 0;
   a.env_idx = reinterpret_cast<const long long*>(env_idx);
   a.qpos = h->qpos; a.qvel = h->qvel;
-  const char* const dm = k16 ? reinterpret_cast<const char*>(h->dm) : reinterpret_cast<const char*>(h->dm64);
-  a.b_pos = reinterpret_cast<const float*>(dm + (k16 ? offsetof(DevModel, b_pos) : offsetof(DevModel64, b_pos)));
-  a.b_quat = reinterpret_cast<const float*>(dm + (k16 ? offsetof(DevModel, b_quat) : offsetof(DevModel64, b_quat)));
-  a.b_axis = reinterpret_cast<const float*>(dm + (k16 ? offsetof(DevModel, b_axis) : offsetof(DevModel64, b_axis)));
-  a.b_qadr = reinterpret_cast<const int32_t*>(dm + (k16 ? offsetof(DevModel, b_qadr) : offsetof(DevModel64, b_qadr)));
-  a.d_lane = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(h->dpt) + offsetof(PlumbTab, d_lane));
+  a.m = ModelView(h).joint_pointers();
   a.pos = pos; a.quat = quat; a.vel = vel; a.jac = jac;
   const long long n_pairs = (long long)R * q->n_links;
   if (n_pairs > 0x7fffffffLL - 4) return mir_set_error(MIR_E_CAPACITY, "mir_link_kinematics: rows x links reaches 2^31");
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != h->device) (void)hipSetDevice(h->device);
-  hipLaunchKernelGGL(mir_kin_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(64), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  if (prev != h->device && prev >= 0) (void)hipSetDevice(prev);
-  if (e != hipSuccess) return mir_set_error(MIR_E_HIP, hipGetErrorString(e));
-  return MIR_OK;
+  return launch_rows(h, mir_kin_kernel, (n_pairs + 3) / 4, stream, a);
 }

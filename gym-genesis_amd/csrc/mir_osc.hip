@@ -6,8 +6,8 @@
 // controller, and forward dynamics qacc = M^-1 (tau - bias).  It reads qpos and the compiled model and writes only its own outputs.
 //
 // Mapping (the one of mir_dyn.hip): 16 lanes = one DPP row serve one (row, kinematic tree) PAIR, four pairs per wave64.
-//   1. poses, spatial inertias, motion subspaces and the composite-rigid-body M block of the tree in LDS: mir_dyn_body.h, the
-//      arithmetic of mir_dyn.hip in the same order.  No Newton-Euler pass.
+//   1. poses, spatial inertias, motion subspaces and the composite-rigid-body M block of the tree in LDS: mir_dyn_phases.inc, the
+//      fragment mir_dyn.hip includes too.  No Newton-Euler pass.
 //   2. Cholesky M = L L^T in place (lower triangle), left-looking: lane i is ROW i; column j is a dot product of row i with row j
 //      (the latter a broadcast read), the diagonal leaves through LDS as 1 / L[j][j].  M is SPD by the armature.
 //   3. per queried link of THIS tree (the links of other trees are skipped: every (row, link) has one owner, no atomics): the
@@ -41,6 +41,8 @@
 #define G 16
 #include "mir_dev.h"
 
+#include "mir_query.h"
+
 #include "mir_dyn_body.h"
 
 namespace {
@@ -58,9 +60,8 @@ struct OscArgs {
   float damping2;
   const long long* env_idx;
   const float *qpos, *qpos_o, *x;
-  // per-body / per-dof constants of the device model (mir_dyn_body.h: dyn_model_pointers)
-  const float *b_pos, *b_quat, *b_axis, *b_ipos, *b_inertia, *b_mass, *d_armature;
-  const int32_t *b_qadr, *d_lane;
+  JointPtrs m;
+  InertiaPtrs mi;
   float *minv, *solve, *lambda_inv, *lambda, *jbar;
 };
 static_assert(sizeof(OscArgs) <= 4096, "kernel arguments");
@@ -123,19 +124,10 @@ __device__ __forceinline__ void chol_solve(const OscLds& L, int n, float (&v)[OS
 __global__ __launch_bounds__(64) void mir_osc_kernel(OscArgs a) {
   __shared__ __attribute__((aligned(16))) OscLds lds[4];
   OscLds& L = lds[threadIdx.x >> 4];
-  const DynLane t = dyn_lane(a);
-  const int lane = t.lane, row = t.row, ti = t.ti, nd = t.nd, sdof = t.sdof;
-  const bool valid = t.valid, isdof = t.isdof;
-  const float* const qrow = a.qpos_o ? a.qpos_o + (size_t)row * a.nq : a.qpos + (size_t)t.env * a.qst;
+  L.dinv[threadIdx.x & 15] = 0.0f;
+  const bool want_mass = true;
   // ---- 1. poses, inertias, motion subspaces, the M block
-  V3 P, baxis;
-  Q4 Qx;
-  L.dinv[lane] = 0.0f;
-  dyn_poses(a, L, t, qrow, P, Qx, baxis);
-  dyn_inertia(a, L, t, P, Qx, baxis);
-  const Sp S = isdof ? lds6(L.cd[lane]) : Sp{v3(0, 0, 0), v3(0, 0, 0)};
-  const int sub = a.tree[ti].sub[isdof ? t.dbody : 0];
-  dyn_mass(a, L, t, S, sub);
+#include "mir_dyn_phases.inc"
   WSYNC();  // (the M block is complete)
   // ---- 2. Cholesky in place: lane i is row i
   const int nmax = a.nd_max;
@@ -154,8 +146,8 @@ __global__ __launch_bounds__(64) void mir_osc_kernel(OscArgs a) {
   const int nw = a.n_dofs, col = sdof - a.dof0;
   const bool mine = valid && isdof && col >= 0 && col < nw;
   // ---- 3. the queried links of my tree
-  const V3 obody = ld3(L.xp[isdof ? t.dbody : 0]);
-  const int jtd = (a.tree[ti].body[isdof ? t.dbody : 0] >> 8) & 3, comp = isdof ? (int)((a.tree[ti].dof[lane] >> 16) & 7) : 0;
+  const V3 obody = ld3(L.xp[isdof ? dbody : 0]);
+  const int jtd = (a.tree[ti].body[isdof ? dbody : 0] >> 8) & 3, comp = isdof ? (int)((a.tree[ti].dof[lane] >> 16) & 7) : 0;
   const bool slides = jtd == MIR_JNT_PRISMATIC || (jtd == MIR_JNT_FREE && comp < 3);  // (a dof that translates: its column is [v; 0])
   const bool want_lambda = a.lambda || a.jbar;
   for (int l = 0; l < a.n_links; l++) {
@@ -328,21 +320,21 @@ extern "C" int mir_task_query_sizeof(void) { return (int)sizeof(MirTaskQuery); }
 extern "C" int mir_task_dynamics(MirHandle h, const MirTaskQuery* q, const int64_t* env_idx, int32_t n_rows, const float* qpos, const float* x,
                                  float* minv, float* solve, float* lambda_inv, float* lambda, float* jbar, void* stream) {
   const char* const who = "mir_task_dynamics";
-  if (!h || !q) return dyn_error(MIR_E_INVALID, who, "null argument");
-  if (q->struct_size != (int32_t)sizeof(MirTaskQuery)) return dyn_error(MIR_E_INVALID, who, "struct_size is not sizeof(MirTaskQuery)");
-  if (q->flags != 0) return dyn_error(MIR_E_INVALID, who, "unknown flag bit");
-  if (q->n_links < 0 || q->n_links > MIR_MAX_BODY) return dyn_error(MIR_E_INVALID, who, "n_links outside 0 .. MIR_MAX_BODY");
+  if (!h || !q) return query_error(MIR_E_INVALID, who, "null argument");
+  if (q->struct_size != (int32_t)sizeof(MirTaskQuery)) return query_error(MIR_E_INVALID, who, "struct_size is not sizeof(MirTaskQuery)");
+  if (q->flags != 0) return query_error(MIR_E_INVALID, who, "unknown flag bit");
+  if (q->n_links < 0 || q->n_links > MIR_MAX_BODY) return query_error(MIR_E_INVALID, who, "n_links outside 0 .. MIR_MAX_BODY");
   for (int l = 0; l < q->n_links; l++) {
-    if (q->link_body[l] <= 0 || q->link_body[l] >= h->nbody) return dyn_error(MIR_E_INVALID, who, "link out of range");
+    if (q->link_body[l] <= 0 || q->link_body[l] >= h->nbody) return query_error(MIR_E_INVALID, who, "link out of range");
     for (int k = 0; k < 3; k++)
-      if (!std::isfinite(q->local_point[l][k])) return dyn_error(MIR_E_INVALID, who, "local_point is not finite");
+      if (!std::isfinite(q->local_point[l][k])) return query_error(MIR_E_INVALID, who, "local_point is not finite");
   }
-  if (!std::isfinite(q->damping) || q->damping < 0.0f) return dyn_error(MIR_E_INVALID, who, "damping is negative or not finite");
-  if (q->dof0 < 0 || q->n_dofs < 0 || q->dof0 > h->nv || q->n_dofs > h->nv - q->dof0) return dyn_error(MIR_E_INVALID, who, "dof window outside [0, nv]");
-  if (solve && !x) return dyn_error(MIR_E_INVALID, who, "solve needs x");
-  if ((lambda_inv || lambda || jbar) && q->n_links == 0) return dyn_error(MIR_E_INVALID, who, "lambda_inv, lambda and jbar need a link");
-  if (h->pending) return dyn_error(MIR_E_INVALID, who, "a step is pending (mir_step_end first)");
-  if (env_idx && n_rows < 0) return dyn_error(MIR_E_INVALID, who, "negative n_rows");
+  if (!std::isfinite(q->damping) || q->damping < 0.0f) return query_error(MIR_E_INVALID, who, "damping is negative or not finite");
+  if (q->dof0 < 0 || q->n_dofs < 0 || q->dof0 > h->nv || q->n_dofs > h->nv - q->dof0) return query_error(MIR_E_INVALID, who, "dof window outside [0, nv]");
+  if (solve && !x) return query_error(MIR_E_INVALID, who, "solve needs x");
+  if ((lambda_inv || lambda || jbar) && q->n_links == 0) return query_error(MIR_E_INVALID, who, "lambda_inv, lambda and jbar need a link");
+  if (h->pending) return query_error(MIR_E_INVALID, who, "a step is pending (mir_step_end first)");
+  if (env_idx && n_rows < 0) return query_error(MIR_E_INVALID, who, "negative n_rows");
   const long long R = env_idx ? n_rows : h->B, n = q->n_dofs, nl = q->n_links;
   OscArgs a;
   memset(&a, 0, sizeof a);
@@ -350,13 +342,13 @@ extern "C" int mir_task_dynamics(MirHandle h, const MirTaskQuery* q, const int64
   if (int rc = dyn_build_trees(h, a.tree, T, who)) return rc;
   for (int l = 0; l < q->n_links; l++) {
     const int b = q->link_body[l];
-    if (T.tree_of[b] < 0) return dyn_error(MIR_E_INVALID, who, "a link whose kinematic tree has no dofs");
+    if (T.tree_of[b] < 0) return query_error(MIR_E_INVALID, who, "a link whose kinematic tree has no dofs");
     a.link[l] = (uint16_t)(T.tree_of[b] | T.local[b] << 8);
     for (int k = 0; k < 3; k++) a.local_point[l][k] = q->local_point[l][k];
   }
   const long long lim = 0x7fffffffLL;
   if ((minv && R * n * n > lim) || (solve && R * n > lim) || ((lambda_inv || lambda) && R * nl * 36 > lim) || (jbar && R * nl * n * 6 > lim))
-    return dyn_error(MIR_E_CAPACITY, who, "an output of 2^31 elements or more");
+    return query_error(MIR_E_CAPACITY, who, "an output of 2^31 elements or more");
   // (what is asked for and empty is not computed)
   if (n == 0) minv = solve = jbar = nullptr;
   if (R == 0 || (!minv && !solve && !lambda_inv && !lambda && !jbar)) return MIR_OK;  // (nothing asked for)
@@ -367,16 +359,10 @@ extern "C" int mir_task_dynamics(MirHandle h, const MirTaskQuery* q, const int64
   a.damping2 = q->damping * q->damping;
   a.env_idx = reinterpret_cast<const long long*>(env_idx);
   a.qpos = h->qpos; a.qpos_o = qpos; a.x = x;
-  dyn_model_pointers(h, a);
+  const ModelView mv(h);
+  a.m = mv.joint_pointers(); a.mi = mv.inertia_pointers();
   a.minv = minv; a.solve = solve; a.lambda_inv = lambda_inv; a.lambda = lambda; a.jbar = jbar;
   const long long n_pairs = R * T.n_trees;
-  if (n_pairs > 0x7fffffffLL - 4) return dyn_error(MIR_E_CAPACITY, who, "rows x trees reaches 2^31");
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != h->device) (void)hipSetDevice(h->device);
-  hipLaunchKernelGGL(mir_osc_kernel, dim3((unsigned)((n_pairs + 3) / 4)), dim3(64), 0, (hipStream_t)stream, a);
-  hipError_t e = hipGetLastError();
-  if (prev != h->device && prev >= 0) (void)hipSetDevice(prev);
-  if (e != hipSuccess) return mir_set_error(MIR_E_HIP, hipGetErrorString(e));
-  return MIR_OK;
+  if (n_pairs > 0x7fffffffLL - 4) return query_error(MIR_E_CAPACITY, who, "rows x trees reaches 2^31");
+  return launch_rows(h, mir_osc_kernel, (n_pairs + 3) / 4, stream, a);
 }

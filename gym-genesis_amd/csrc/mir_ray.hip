@@ -28,7 +28,10 @@
 #include "mir_model64.h"
 #include "mir_scene.h"
 
+#define G 16
 #include "mir_dev.h"
+
+#include "mir_query.h"
 
 namespace {
 
@@ -394,9 +397,7 @@ extern "C" int mir_raycast(MirHandle h, const MirRayQuery* q, const float* dirs,
   const long long R = env_idx ? n_rows : h->B, N = q->n_rays;
   const long long nblk = (N + RAY_TPB - 1) / RAY_TPB;
   if (R * N > 0x7fffffffLL || R * nblk > 0x7fffffffLL) return mir_set_error(MIR_E_CAPACITY, "mir_raycast: rows x rays reaches 2^31");
-  int prev = -1;
-  (void)hipGetDevice(&prev);
-  if (prev != h->device) (void)hipSetDevice(h->device);
+  DeviceGuard guard(h->device);  // (the table's allocation and the pose refresh, too)
   int rc = MIR_OK;
   do {
     if (h->ray_state == 0) h->ray_state = (rc = build_tab(h)) == MIR_OK ? 1 : (rc == MIR_E_INVALID ? -1 : 0);
@@ -417,10 +418,7 @@ extern "C" int mir_raycast(MirHandle h, const MirRayQuery* q, const float* dirs,
     a.min_range = q->min_range; a.max_range = q->max_range; a.flags = q->flags; a.skip = q->skip_geoms;
     a.dirs = dirs; a.env_idx = reinterpret_cast<const long long*>(env_idx);
     a.distance = distance; a.points = points; a.geom = geom; a.normal = normal;
-    hipLaunchKernelGGL(mir_ray_kernel, dim3((unsigned)(R * nblk)), dim3(RAY_TPB), 0, (hipStream_t)stream, a);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) rc = mir_set_error(MIR_E_HIP, hipGetErrorString(e));
+    rc = launch_rows<RAY_TPB>(h, mir_ray_kernel, R * nblk, stream, a);
   } while (0);
-  if (prev != h->device && prev >= 0) (void)hipSetDevice(prev);
   return rc;
 }
