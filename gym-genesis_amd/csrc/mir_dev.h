@@ -73,6 +73,7 @@ __device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
   return {a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z, a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y,
           a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x, a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w};
 }
+__device__ __forceinline__ Q4 qconj(Q4 q) { return {q.w, -q.x, -q.y, -q.z}; }
 __device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
   V3 u = {q.x, q.y, q.z};
   V3 t = 2.0f * cross(u, v);

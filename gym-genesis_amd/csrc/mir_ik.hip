@@ -23,45 +23,23 @@
 
 #include "mir_query.h"
 
+#include "mir_ik_front.h"
+
 namespace {
 
-struct IkChain {
-  int n;                       // bodies on the chain (root first)
-  int jtype[G], qcol[G];       // joint type; column of the joint in the (B, n_arm) arrays, -1 for fixed links
-  float pos[G][3], quat[G][4], axis[G][3], lo[G], hi[G];
-  int limited[G];
-};
-
 struct IkArgs {
-  IkChain ch;
-  const float* target_pos;   // (B,3)
-  const float* target_quat;  // (B,4) or null
-  const float* init_qpos;    // (B,n_arm) or null
-  const float* scene_qpos;   // scene state row (B, qst) used when init_qpos is null
-  int qst, n_arm;
-  int arm_qadr[MIR_MAX_DOF]; // qpos address of scalar joint k in the scene row
-  float* qpos_out;           // (B,n_arm)
-  float* err_out;            // (B,2) or null
+  IkElems ch;                // the chain world -> link, root first (the tree of one link)
+  IkRowArgs r;
+  float* qpos_out;           // (rows, n_arm)
+  float* err_out;            // (rows, 2) or null
   int32_t* iters_out;        // (rows) or null: iterations the row took (debug: mir_debug_ik_iters)
-  // rows (mir_inverse_kinematics_rows): row k of the outputs belongs to env env_idx[k] (null: env k); the inputs are addressed by row,
-  // or by env (the *_by_env flags), the quaternion possibly ONE for all rows; init_qpos holds init_ncols columns from init_col0 on
-  const long long* env_idx;
-  int n_rows, pos_by_env, quat_by_env, quat_one, init_by_env, init_col0, init_ncols;
-  int B, max_iters, respect_limits;
-  float inv_pos_tol, inv_rot_tol;
-  float damping2, pos_tol, rot_tol, max_step;
 };
-
-__device__ __forceinline__ Q4 qconj(Q4 q) { return {q.w, -q.x, -q.y, -q.z}; }
 
 __global__ __launch_bounds__(64) void mir_ik_kernel(IkArgs a) {
-  const int tid = threadIdx.x, lane = tid & 15, grp = tid >> 4;
-  const int row_raw = blockIdx.x * 4 + grp;
-  const bool valid = row_raw < a.n_rows;
-  const int row = valid ? row_raw : a.n_rows - 1;
-  int env = a.env_idx ? (int)a.env_idx[row] : row;
-  env = env < 0 ? 0 : (env >= a.B ? a.B - 1 : env);  // (an index outside the batch is clamped, not followed: the caller's side checks it)
-  const int prow = a.pos_by_env ? env : row, qrow = a.quat_one ? 0 : (a.quat_by_env ? env : row), irow = a.init_by_env ? env : row;
+  const int tid = threadIdx.x, lane = tid & 15;
+  const IkRow t = ik_row_decode(a.r);
+  const int row = t.row;
+  const bool valid = t.valid;
   const int n = a.ch.n;
   const int eef4 = ((tid & ~15) + n - 1) << 2;  // (lane_gather address of the chain's last element in this env's row)
   const bool onchain = lane < n;
@@ -70,104 +48,55 @@ __global__ __launch_bounds__(64) void mir_ik_kernel(IkArgs a) {
   const Q4 bquat = ld4(a.ch.quat[lane]);
   const bool moving = onchain && qc >= 0 && (jt == MIR_JNT_REVOLUTE || jt == MIR_JNT_PRISMATIC);
   const float lo = a.ch.lo[lane], hi = a.ch.hi[lane];
-  const bool lim = moving && a.ch.limited[lane] && a.respect_limits;
+  const bool lim = moving && a.ch.limited[lane] && a.r.respect_limits;
   // seed: every scalar joint (the result keeps the seed outside the chain)
-  auto seed = [&](int k) -> float {
-    const bool from_init = a.init_qpos && k >= a.init_col0 && k < a.init_col0 + a.init_ncols;
-    return from_init ? a.init_qpos[(size_t)irow * a.init_ncols + (k - a.init_col0)] : a.scene_qpos[(size_t)env * a.qst + a.arm_qadr[k]];
-  };
-  for (int k = lane; k < a.n_arm; k += G) {
-    const float v = seed(k);
-    if (valid) a.qpos_out[(size_t)row * a.n_arm + k] = v;
+  for (int k = lane; k < a.r.n_arm; k += G) {
+    const float v = ik_seed(a.r, t.env, t.irow, k);
+    if (valid) a.qpos_out[(size_t)row * a.r.n_arm + k] = v;
   }
   float q = 0.0f;
-  if (moving) q = seed(qc);
-  const V3 tp = ld3(a.target_pos + (size_t)prow * 3);
-  const bool userot = a.target_quat != nullptr;
-  const Q4 tq = userot ? qnormalize(ld4(a.target_quat + (size_t)qrow * 4)) : Q4{1, 0, 0, 0};
+  if (moving) q = ik_seed(a.r, t.env, t.irow, qc);
+  const V3 tp = ld3(a.r.target_pos + (size_t)t.prow * 3);
+  const bool userot = a.r.target_quat != nullptr;
+  const Q4 tq = userot ? qnormalize(ld4(a.r.target_quat + (size_t)t.qrow * 4)) : Q4{1, 0, 0, 0};
   bool done = false;
-  int stall = 0, my_iters = 0;
+  int my_iters = 0;
   // the ACCEPTED iterate (Levenberg - Marquardt acceptance, include/mirigid.h): this lane's joint angle, Jacobian column; the env's
   // task-space error and scaled error (identical in all of its lanes: they are computed from the same gathered values)
-  float q_acc = q, lam2 = a.damping2, m_acc = 0.0f, epn = 0.0f, ern = 0.0f;
-  const float lam2_min = a.damping2 * (1.0f / 256.0f), lam2_max = a.damping2 * 64.0f;
+  float q_acc = q, epn = 0.0f, ern = 0.0f;
+  LmState lm = {a.r.damping2, 0, 0.0f};
   float J[6] = {0, 0, 0, 0, 0, 0}, e[6] = {0, 0, 0, 0, 0, 0};
-  for (int it = 0; it <= a.max_iters; it++) {
-    // ---- local transform of my chain element (identity off the chain) at the CANDIDATE q ...
-    V3 P = v3(0, 0, 0);
-    Q4 Qx = Q4{1, 0, 0, 0};
-    if (onchain) {
-      Qx = bquat;
-      P = bpos;
-      if (jt == MIR_JNT_REVOLUTE) {
-        float sn, cs;
-        sincos_pi2(0.5f * q, &sn, &cs);
-        Qx = qmul(bquat, Q4{cs, baxis.x * sn, baxis.y * sn, baxis.z * sn});
-      } else if (jt == MIR_JNT_PRISMATIC) {
-        P = bpos + qrot(bquat, q * baxis);
-      }
-    }
-    // ... then my own prefix of the chain by a log-step scan over the DPP row (composition (P,Q) o (p,q) = (P + Q p, Q q)
-    // is associative): 4 shifted exchanges instead of a walk of up to 15 links, no LDS round trips
-    {
-#define IK_SCAN_STEP(D)                                                                                          \
-      {                                                                                                          \
-        const V3 pp = v3(row_shr<D>(P.x), row_shr<D>(P.y), row_shr<D>(P.z));                                     \
-        const Q4 pq = Q4{row_shr<D>(Qx.w), row_shr<D>(Qx.x), row_shr<D>(Qx.y), row_shr<D>(Qx.z)};                \
-        if (lane >= D) {                                                                                         \
-          P = pp + qrot(pq, P);                                                                                  \
-          Qx = qmul(pq, Qx);                                                                                     \
-        }                                                                                                        \
-      }
-      IK_SCAN_STEP(1)
-      if (n > 2) IK_SCAN_STEP(2)
-      if (n > 4) IK_SCAN_STEP(4)
-      if (n > 8) IK_SCAN_STEP(8)  // (the Panda's chain to the hand is eight elements once its fixed base link is folded into joint 1: host side)
-#undef IK_SCAN_STEP
-    }
+  for (int it = 0; it <= a.r.max_iters; it++) {
+    // ---- local transform of my chain element (identity off the chain) at the CANDIDATE q, then my own prefix of the chain by a
+    // log-step scan over the DPP row: 4 shifted exchanges instead of a walk of up to 15 links, no LDS round trips (the Panda's chain to
+    // the hand is eight elements once its fixed base link is folded into joint 1: three steps)
+    const Pose x = path_scan(ik_elem_local(onchain, jt, bpos, bquat, baxis, q), lane, n);
+    const V3 P = x.P;
+    const Q4 Qx = x.Qx;
     // ---- task-space error of the candidate (every lane, redundantly): the pose of the chain's last element comes over the crossbar
     // (seven lane gathers, one trip; round 5 went through LDS: a store, a fence and a load per iteration of a chain that is all latency)
-    const V3 pe = v3(lane_gather(eef4, P.x), lane_gather(eef4, P.y), lane_gather(eef4, P.z));
-    const Q4 qe = Q4{lane_gather(eef4, Qx.w), lane_gather(eef4, Qx.x), lane_gather(eef4, Qx.y), lane_gather(eef4, Qx.z)};
+    const V3 pe = gather3(eef4, P);
+    const Q4 qe = gather4(eef4, Qx);
     const V3 ep = tp - pe;
     V3 er = v3(0, 0, 0);
-    if (userot) {
-      Q4 d = qmul(tq, qconj(qe));  // rotation taking the current frame to the target, world axes
-      if (d.w < 0.0f) d = Q4{-d.w, -d.x, -d.y, -d.z};
-      const float sn = sqrtf(d.x * d.x + d.y * d.y + d.z * d.z);
-      const float ang = 2.0f * atan2f(sn, d.w);
-      const float k = sn > 1e-9f ? ang / sn : 2.0f;
-      er = v3(k * d.x, k * d.y, k * d.z);
-    }
+    if (userot) er = ik_rot_error(tq, qe);
     const float epn_c = sqrtf(dot(ep, ep)), ern_c = sqrtf(dot(er, er));
-    const float metric = epn_c * a.inv_pos_tol + ern_c * a.inv_rot_tol;
+    const float metric = epn_c * a.r.inv_pos_tol + ern_c * a.r.inv_rot_tol;
     if (!done) {
-      if (it == 0 || metric < m_acc) {
-        // accepted: the damping relaxes; stagnation = an accepted step that gained less than 1 % (a target beyond the joint limits
-        // or the reach: without the rule the few unreachable targets of a batch set the time of the whole launch)
-        if (it > 0) {
-          stall = metric > 0.99f * m_acc ? stall + 1 : 0;
-          lam2 = fmaxf(lam2 * 0.25f, lam2_min);
-        }
-        m_acc = metric; epn = epn_c; ern = ern_c;
+      if (lm_accepts(lm, metric, it == 0)) {
+        lm = lm_accept(lm, metric, it == 0, a.r.damping2);
+        epn = epn_c; ern = ern_c;
         e[0] = ep.x; e[1] = ep.y; e[2] = ep.z; e[3] = er.x; e[4] = er.y; e[5] = er.z;
         q_acc = q;
-        // my Jacobian column at the accepted iterate (joint frame = my world pose)
-        V3 jv = v3(0, 0, 0), jw = v3(0, 0, 0);
-        if (moving) {
-          const V3 axw = qrot(Qx, baxis);
-          if (jt == MIR_JNT_REVOLUTE) { jw = axw; jv = cross(axw, pe - P); }
-          else jv = axw;
-        }
-        J[0] = jv.x; J[1] = jv.y; J[2] = jv.z; J[3] = userot ? jw.x : 0.0f; J[4] = userot ? jw.y : 0.0f; J[5] = userot ? jw.z : 0.0f;
+        // my Jacobian column at the accepted iterate
+        const JacColumn c = ik_jac_column(moving, jt, Qx, P, baxis, pe);
+        J[0] = c.jv.x; J[1] = c.jv.y; J[2] = c.jv.z; J[3] = userot ? c.jw.x : 0.0f; J[4] = userot ? c.jw.y : 0.0f; J[5] = userot ? c.jw.z : 0.0f;
       } else {
-        // rejected (the scaled error did not fall): back to the accepted iterate with eight times the damping; a stalled iteration
-        stall++;
-        lam2 = fminf(lam2 * 8.0f, lam2_max);
+        lm = lm_reject(lm, a.r.damping2);
       }
-      if ((epn < a.pos_tol && ern < a.rot_tol) || stall >= 3) done = true;
+      if ((epn < a.r.pos_tol && ern < a.r.rot_tol) || lm_stalled(lm)) done = true;
     }
-    if (it == a.max_iters) break;
+    if (it == a.r.max_iters) break;
     if (!__any(!done)) break;
     // ---- A = J J^T + lambda^2 I in every lane (J, e: the accepted iterate's)
     float A[6][6];
@@ -175,7 +104,7 @@ __global__ __launch_bounds__(64) void mir_ik_kernel(IkArgs a) {
     for (int r = 0; r < 6; r++)
 #pragma unroll
       for (int c = 0; c <= r; c++) {
-        const float v = gsum(J[r] * J[c]) + (r == c ? lam2 : 0.0f);
+        const float v = gsum(J[r] * J[c]) + (r == c ? lm.lam2 : 0.0f);
         A[r][c] = v;
         A[c][r] = v;
       }
@@ -214,8 +143,7 @@ __global__ __launch_bounds__(64) void mir_ik_kernel(IkArgs a) {
     float dq = 0.0f;
 #pragma unroll
     for (int r = 0; r < 6; r++) dq += J[r] * y[r];
-    const float big = gmaxf(fabsf(dq));
-    const float sc = big > a.max_step ? a.max_step / big : 1.0f;
+    const float sc = ik_step_scale(dq, a.r.max_step);
     if (!done) my_iters = it + 1;
     q = q_acc;
     if (moving && !done) {
@@ -224,7 +152,7 @@ __global__ __launch_bounds__(64) void mir_ik_kernel(IkArgs a) {
     }
   }
   q = q_acc;
-  if (valid && moving) a.qpos_out[(size_t)row * a.n_arm + qc] = q;
+  if (valid && moving) a.qpos_out[(size_t)row * a.r.n_arm + qc] = q;
   if (valid && a.iters_out && lane == 0) a.iters_out[row] = my_iters;
   if (valid && a.err_out && lane == 0) {
     a.err_out[(size_t)row * 2] = epn;
@@ -236,102 +164,22 @@ __global__ __launch_bounds__(64) void mir_ik_kernel(IkArgs a) {
 
 extern "C" int mir_inverse_kinematics_rows(MirHandle h, int32_t link_body, const MirIkRows* rows, const float* target_pos, const float* target_quat,
                                            const float* init_qpos, const MirIkOptions* opt, float* qpos_out, float* err_out, void* stream) {
-  if (!h || !target_pos || !qpos_out) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics: null argument");
-  if (rows && (rows->n_rows < 0 || (rows->flags & ~(uint32_t)(MIR_IK_POS_BY_ENV | MIR_IK_QUAT_BY_ENV | MIR_IK_QUAT_ONE | MIR_IK_INIT_BY_ENV))))
-    return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics_rows: bad row description");
+  const char* who = "mir_inverse_kinematics";
+  if (!h || !target_pos || !qpos_out) return query_error(MIR_E_INVALID, who, "null argument");
+  if (int rc = ik_check_rows(rows, "mir_inverse_kinematics_rows")) return rc;
   if (rows && rows->n_rows == 0) return MIR_OK;
-  if (link_body <= 0 || link_body >= h->nbody) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics: link out of range");
+  // the chain world -> link from whichever model serves the scene: the tree of one link
+  IkTree t;
+  const char* what;
+  if (int rc = build_ik_tree(ModelView(h), h->nbody, &link_body, 1, nullptr, "chain longer than 16 bodies", t, &what)) return query_error(rc, who, what);
+  MirIkOptions o;
+  if (int rc = ik_options(opt, false, who, o)) return rc;
   IkArgs a;
   memset(&a, 0, sizeof a);
-  // chain world -> link from whichever model serves the scene
-  int chain[MIR_MAX_BODY], n = 0;
-  const ModelView mv(h);
-  for (int b = link_body; b > 0; b = mv.parent(b)) {
-    if (n >= G) return mir_set_error(MIR_E_CAPACITY, "mir_inverse_kinematics: chain longer than 16 bodies");
-    chain[n++] = b;
-  }
-  a.ch.n = n;
-  // column of each scalar joint in the (B, n_arm) arrays = its rank among the scalar joints in body order
-  int col_of_body[MIR_MAX_BODY];
-  int narm = 0;
-  for (int b = 1; b < h->nbody; b++) {
-    const int jt = mv.jtype(b);
-    col_of_body[b] = (jt == MIR_JNT_REVOLUTE || jt == MIR_JNT_PRISMATIC) ? narm++ : -1;
-    if (col_of_body[b] >= 0) a.arm_qadr[col_of_body[b]] = mv.qadr(b);
-  }
-  for (int i = 0; i < n; i++) {
-    const int b = chain[n - 1 - i];
-    const int jt = mv.jtype(b);
-    for (int k = 0; k < 3; k++) { a.ch.pos[i][k] = mv.body_pos(b)[k]; a.ch.axis[i][k] = mv.body_axis(b)[k]; }
-    for (int k = 0; k < 4; k++) a.ch.quat[i][k] = mv.body_quat(b)[k];
-    if (col_of_body[b] >= 0) {
-      double lo, hi;
-      mv.limits(b, lo, hi, a.ch.limited[i]);
-      a.ch.lo[i] = (float)lo; a.ch.hi[i] = (float)hi;
-    }
-    if (jt == MIR_JNT_FREE) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics: the link hangs off a free body");
-    a.ch.jtype[i] = jt;
-    a.ch.qcol[i] = col_of_body[b];
-  }
-  // A FIXED element in front of another one is a constant: folded into that element's base transform (pos' = p_f + R_f pos, quat' = q_f quat)
-  // the chain is one element shorter -- for the Panda's hand nine become eight, and the kernel's prefix scan three steps instead of four.
-  {
-    auto qmul_h = [](const double* p, const double* q, double* r) {
-      r[0] = p[0] * q[0] - p[1] * q[1] - p[2] * q[2] - p[3] * q[3]; r[1] = p[0] * q[1] + p[1] * q[0] + p[2] * q[3] - p[3] * q[2];
-      r[2] = p[0] * q[2] - p[1] * q[3] + p[2] * q[0] + p[3] * q[1]; r[3] = p[0] * q[3] + p[1] * q[2] - p[2] * q[1] + p[3] * q[0];
-    };
-    int m_ = 0;
-    bool carry = false;
-    double cp[3] = {0, 0, 0}, cq[4] = {1, 0, 0, 0};  // the fixed elements folded so far, waiting for the next element
-    for (int i = 0; i < n; i++) {
-      double p[3] = {a.ch.pos[i][0], a.ch.pos[i][1], a.ch.pos[i][2]}, q[4] = {a.ch.quat[i][0], a.ch.quat[i][1], a.ch.quat[i][2], a.ch.quat[i][3]};
-      if (carry) {  // this element's base transform behind the carried one
-        const double v[4] = {0, p[0], p[1], p[2]};
-        double t[4], cqc[4] = {cq[0], -cq[1], -cq[2], -cq[3]}, rv[4], nq[4];
-        qmul_h(cq, v, t); qmul_h(t, cqc, rv);
-        p[0] = cp[0] + rv[1]; p[1] = cp[1] + rv[2]; p[2] = cp[2] + rv[3];
-        qmul_h(cq, q, nq);
-        for (int k = 0; k < 4; k++) q[k] = nq[k];
-        carry = false;
-      }
-      const bool fixed_inner = a.ch.jtype[i] == MIR_JNT_FIXED && i < n - 1;
-      if (fixed_inner) {
-        for (int k = 0; k < 3; k++) cp[k] = p[k];
-        for (int k = 0; k < 4; k++) cq[k] = q[k];
-        carry = true;
-        continue;
-      }
-      a.ch.jtype[m_] = a.ch.jtype[i]; a.ch.qcol[m_] = a.ch.qcol[i];
-      a.ch.lo[m_] = a.ch.lo[i]; a.ch.hi[m_] = a.ch.hi[i]; a.ch.limited[m_] = a.ch.limited[i];
-      for (int k = 0; k < 3; k++) { a.ch.pos[m_][k] = (float)p[k]; a.ch.axis[m_][k] = a.ch.axis[i][k]; }
-      for (int k = 0; k < 4; k++) a.ch.quat[m_][k] = (float)q[k];
-      m_++;
-    }
-    for (int i = m_; i < n; i++) { a.ch.jtype[i] = MIR_JNT_FIXED; a.ch.qcol[i] = -1; a.ch.limited[i] = 0; }
-    a.ch.n = m_;
-  }
-  MirIkOptions o = {20, 1, 0.05, 5e-4, 5e-3, 0.5};
-  if (opt) {
-    o = *opt;
-    if (o.max_iters <= 0 || !(o.damping > 0.0) || !(o.max_step > 0.0)) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics: bad options");
-  }
-  a.target_pos = target_pos; a.target_quat = target_quat; a.init_qpos = init_qpos; a.scene_qpos = h->qpos;
-  a.qst = h->pt.qst; a.n_arm = narm; a.qpos_out = qpos_out; a.err_out = err_out; a.B = h->B;
-  a.n_rows = h->B; a.init_col0 = 0; a.init_ncols = narm;
-  if (rows) {
-    a.env_idx = reinterpret_cast<const long long*>(rows->env_idx);
-    a.n_rows = rows->env_idx ? rows->n_rows : h->B;
-    a.pos_by_env = (rows->flags & MIR_IK_POS_BY_ENV) ? 1 : 0; a.quat_by_env = (rows->flags & MIR_IK_QUAT_BY_ENV) ? 1 : 0;
-    a.quat_one = (rows->flags & MIR_IK_QUAT_ONE) ? 1 : 0; a.init_by_env = (rows->flags & MIR_IK_INIT_BY_ENV) ? 1 : 0;
-    if (rows->init_ncols > 0) {
-      if (rows->init_col0 < 0 || rows->init_col0 + rows->init_ncols > narm) return mir_set_error(MIR_E_INVALID, "mir_inverse_kinematics_rows: init columns outside the joint row");
-      a.init_col0 = rows->init_col0; a.init_ncols = rows->init_ncols;
-    }
-  }
-  a.iters_out = h->dbg_ik_iters;
-  a.max_iters = o.max_iters; a.respect_limits = o.respect_joint_limit;
-  a.damping2 = (float)(o.damping * o.damping); a.pos_tol = (float)o.pos_tol; a.rot_tol = (float)o.rot_tol; a.inv_pos_tol = (float)(1.0 / o.pos_tol); a.inv_rot_tol = (float)(1.0 / o.rot_tol); a.max_step = (float)o.max_step;
-  return launch_rows(h, mir_ik_kernel, (a.n_rows + 3) / 4, stream, a);
+  a.ch = t.el;
+  if (int rc = fill_ik_rows(h, rows, o, t, false, "mir_inverse_kinematics_rows", target_pos, target_quat, init_qpos, a.r)) return rc;
+  a.qpos_out = qpos_out; a.err_out = err_out; a.iters_out = h->dbg_ik_iters;
+  return launch_rows(h, mir_ik_kernel, (a.r.n_rows + 3) / 4, stream, a);
 }
 
 extern "C" int mir_inverse_kinematics(MirHandle h, int32_t link_body, const float* target_pos, const float* target_quat, const float* init_qpos,

@@ -1,5 +1,5 @@
-// mir_query.h — the front end the batched query kernels share (mir_kin.hip, mir_acc.hip, mir_dyn.hip and mir_osc.hip on the device side;
-// those and mir_ik.hip, mir_ikm.hip, mir_ray.hip on the host side).
+// mir_query.h — the front end the batched query kernels share (mir_kin.hip, mir_acc.hip, mir_dyn.hip and mir_osc.hip on the device side,
+// mir_ik.hip and mir_ikm.hip for the pose scan and the gathers; those and mir_ray.hip on the host side).
 //   device: the (row, item) pair a 16-lane DPP row serves, the local joint transform of one body from a qpos row, the log-step pose scan
 //           along a world -> link path, and the path element of a lane;
 //   host:   a view of whichever compiled model serves the scene (DevModel or DevModel64), the addresses of its per-body / per-dof arrays

@@ -993,13 +993,27 @@ class MirScene(StepHelpers):
                                                 C.byref(o), self._stream()))
         return r, d, sg, n
 
+    def _ik_options(self, opts):
+        """MirIkOptions of a call: the defaults with `opts` over them (the object for no opts is made once and kept)"""
+        o = self.__dict__.get("_ik_default")
+        if opts or o is None:
+            o = MirIkOptions(**{**IK_DEFAULTS, **opts})
+            if not opts:
+                self._ik_default = o
+        return o
+
+    @staticmethod
+    def _ik_rows(env_idx, n, flags, col0, ncols):
+        """MirIkRows: n rows for the envs `env_idx` (an int64 device tensor, or None: row k = env k)"""
+        return MirIkRows(None if env_idx is None else env_idx.data_ptr(), n, int(flags), int(col0), int(ncols))
+
     def inverse_kinematics(self, link_body: int, pos, quat=None, init_qpos=None, return_error: bool = False, **opts):
         """Batched damped-least-squares IK (mir_inverse_kinematics): (B, n_arm) joint positions that bring body
         `link_body` to pos (B,3) / quat (B,4 wxyz, optional).  Seed = init_qpos or the scene's current joint positions."""
         p = self._f32(pos, 3)
         q = None if quat is None else self._f32(quat, 4)
         init = None if init_qpos is None else self._f32(init_qpos, self.n_arm)
-        o = MirIkOptions(**{**IK_DEFAULTS, **opts})
+        o = self._ik_options(opts)
         out, err = self.empty(self.n_arm), self.empty(2)
         self._check(self.lib.mir_inverse_kinematics(self.h, int(link_body), _ptr(p), _ptr(q), _ptr(init), C.byref(o), _ptr(out), _ptr(err),
                                                     self._stream()))
@@ -1010,12 +1024,8 @@ class MirScene(StepHelpers):
         """mir_inverse_kinematics_rows: the solver for the rows `env_idx` (int64 device tensor, or None: every env) in ONE launch.
         pos / quat / init_qpos: contiguous float32 device tensors addressed as `flags` say (spec.IK_*); -> (n_rows, n_arm)[, (n_rows, 2)]."""
         n = self.num_envs if env_idx is None else int(env_idx.numel())
-        o = self.__dict__.get("_ik_default")
-        if opts or o is None:
-            o = MirIkOptions(**{**IK_DEFAULTS, **opts})
-            if not opts:
-                self._ik_default = o
-        rows = MirIkRows(None if env_idx is None else env_idx.data_ptr(), n, int(flags), int(init_col0), int(init_ncols))
+        o = self._ik_options(opts)
+        rows = self._ik_rows(env_idx, n, flags, init_col0, init_ncols)
         out = torch.empty((n, self.n_arm), dtype=torch.float32, device=self.device)
         err = torch.empty((n, 2), dtype=torch.float32, device=self.device) if return_error else None
         self._check(self.lib.mir_inverse_kinematics_rows(self.h, int(link_body), C.byref(rows), _ptr(pos), _ptr(quat), _ptr(init_qpos), C.byref(o),
@@ -1035,7 +1045,7 @@ class MirScene(StepHelpers):
         L = q.n_links
         idx = None if env_idx is None else torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
         n = self.num_envs if idx is None else int(idx.numel())
-        q.rows = MirIkRows(None if idx is None else idx.data_ptr(), n, int(flags), int(init_col0), int(init_ncols))
+        q.rows = self._ik_rows(idx, n, flags, init_col0, init_ncols)
 
         def dev(t, width, name, by_env, one=False):
             if t is None:
@@ -1051,7 +1061,7 @@ class MirScene(StepHelpers):
             raise ValueError("inverse_kinematics_multilink needs target positions")
         qq = dev(quats, L * 4, "quats", flags & IK_QUAT_BY_ENV, bool(flags & IK_QUAT_ONE))
         iq = dev(init_qpos, init_ncols or self.n_arm, "init_qpos", flags & IK_INIT_BY_ENV)
-        o = MirIkOptions(**{**IK_DEFAULTS, **opts})
+        o = self._ik_options(opts)
         out = torch.empty((n, self.n_arm), dtype=torch.float32, device=self.device)
         err = torch.empty((n, L, 2), dtype=torch.float32, device=self.device) if return_error else None
         iters = torch.empty((n,), dtype=torch.int32, device=self.device) if return_info else None

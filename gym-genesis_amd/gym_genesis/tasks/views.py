@@ -113,6 +113,8 @@ class EntityView:
         self.dof_idx = [builder.dof_index(n) for n in dof_names]
         # qpos column of each scalar dof (scalar joints come first in every scene built here)
         self._qcols = list(self.dof_idx)
+        qc = self._qcols
+        self._qcols_run = bool(qc) and qc == list(range(qc[0], qc[0] + len(qc)))   # (a run of columns: a slice serves them)
         ctrl = [i for i, d in enumerate(builder.dofs) if d["ctrl_mode"] == 1]
         self._ucols = [ctrl.index(i) for i in self.dof_idx if i in ctrl]
         # the links of this entity: its root and everything below it, in body order
@@ -480,7 +482,7 @@ class EntityView:
         """Columns `_qcols` of a (B, n) tensor: a slice when they are a run (every scene built here), else through an index tensor kept on
         the device (a Python list as index is uploaded by every call: a synchronous copy in front of the launch)."""
         qc = self._qcols
-        if qc == list(range(qc[0], qc[0] + len(qc))):
+        if self._qcols_run:
             return t[:, qc[0]:qc[0] + len(qc)]
         ix = self.__dict__.get("_qcols_t")
         if ix is None or ix.device != t.device:
@@ -534,7 +536,7 @@ class EntityView:
             else:
                 q = rows(qs, 4, "quats")
         qc = self._qcols
-        run = qc == list(range(qc[0], qc[0] + len(qc)))
+        run = self._qcols_run
         iq, col0, ncols = None, 0, 0
         if init_qpos is not None:
             iq = torch.as_tensor(init_qpos, dtype=torch.float32, device=mir.device).reshape(-1, len(qc))
@@ -579,7 +581,7 @@ class EntityView:
         B = mir.num_envs
         idx = None if envs_idx is None else torch.as_tensor(envs_idx, device=mir.device).long().reshape(-1)
         qc = self._qcols
-        if IK_ROWS and hasattr(mir, "inverse_kinematics_rows") and qc == list(range(qc[0], qc[0] + len(qc))):
+        if IK_ROWS and hasattr(mir, "inverse_kinematics_rows") and self._qcols_run:
             # ONE launch (mir_inverse_kinematics_rows): the kernel addresses targets and seeds by row or by env itself and writes row k for
             # env envs_idx[k] -- what the scatter / clone / gather around the full-batch launch below did with five torch kernels
             n = B if idx is None else int(idx.numel())
@@ -624,12 +626,11 @@ class EntityView:
             q[:, 0] += (q.abs().sum(1) == 0).float()  # unaddressed rows: identity, so normalisation stays finite
         init = None
         if init_qpos is not None:
-            qc = self._qcols
             iq = torch.as_tensor(init_qpos, dtype=torch.float32, device=mir.device).reshape(-1, len(qc))
             cur = mir.get_state()[0][:, :mir.n_arm].clone()
             if idx is not None and iq.shape[0] != B:
                 cur[idx[:, None], torch.as_tensor(qc, device=mir.device)[None, :]] = iq
-            elif qc == list(range(qc[0], qc[0] + len(qc))):
+            elif self._qcols_run:
                 cur[:, qc[0]:qc[0] + len(qc)] = iq
             else:
                 cur[:, qc] = iq

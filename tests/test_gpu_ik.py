@@ -145,3 +145,54 @@ def test_ik_rows_one_launch_equals_the_full_batch_launch_bit_for_bit():
         assert torch.equal(e1, e0), f"case {i}: errors differ"
     with pytest.raises(ValueError):
         robot.inverse_kinematics(link=eef, pos=pos_full[:5], quat=one, envs_idx=sub)
+
+
+def test_short_chains_and_rows_match_oracle_and_the_full_batch_launch():
+    """The chains at which the scan and the tree builder the two IK kernels share can go wrong, at B = 5: the first arm link (ONE element
+    once the fixed base is folded into it: no scan step at all), link4 (four elements: two scan steps) and the hand (eight: three).
+    Targets are the float64 forward kinematics at home +- 0.3 rad, so they are reachable; the seed is the home pose.  Each link is solved
+    for the full batch and for seven rows with repeats (one full wave and a ragged one); the bars are those of
+    test_ik_matches_oracle_and_forward_kinematics, and the rows launch equals the full-batch launch bit for bit on the envs they share."""
+    from gym_genesis.backend.lib import MirScene
+    from gym_genesis.backend.spec import IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV
+
+    sb = models.franka_cube_pick_scene()
+    spec = sb.build()
+    B = 5
+    sc = MirScene(spec, B)
+    o = orc.Oracle(spec, B)
+    rng = np.random.default_rng(7)
+    qt = np.tile(HOME, (B, 1)).astype(np.float64)
+    qt[:, :7] += rng.uniform(-0.3, 0.3, (B, 7))
+    xpos, xquat = np.zeros((B, sc.nbody, 3)), np.zeros((B, sc.nbody, 4))
+    for e in range(B):
+        q = o.read(orc.F_QPOS, e)
+        q[:9] = qt[e]
+        o.write(orc.F_QPOS, q, e)
+        o.fk(e)
+        xpos[e], xquat[e] = o.read(orc.F_XPOS, e).reshape(-1, 3), o.read(orc.F_XQUAT, e).reshape(-1, 4)
+    seed = np.tile(HOME, (B, 1))
+    idx = [3, 0, 4, 1, 3, 2, 0]
+    dev = sc.device
+    q16 = sc.get_state()[0].cpu().numpy().copy()
+    for name in ("link1", "link4", "hand"):
+        link = sb.body_index(name)
+        tp, tq = xpos[:, link].astype(np.float32), xquat[:, link].astype(np.float32)
+        q, err = sc.inverse_kinematics(link, tp, tq, seed, return_error=True, max_iters=100)
+        qo, erro = o.ik(link, tp, tq, seed, max_iters=100)
+        t = [torch.as_tensor(a, dtype=torch.float32, device=dev).contiguous() for a in (tp, tq, seed)]
+        qr, errr = sc.inverse_kinematics_rows(link, t[0], t[1], t[2], torch.as_tensor(idx, device=dev), IK_POS_BY_ENV | IK_QUAT_BY_ENV | IK_INIT_BY_ENV,
+                                              return_error=True, max_iters=100)
+        assert torch.equal(qr, q[idx]) and torch.equal(errr, err[idx]), f"{name}: the rows launch differs from the full-batch launch"
+        q, err = q.cpu().numpy(), err.cpu().numpy()
+        print(f"{name}: |e_pos| {err[:, 0].max():.2e} |e_rot| {err[:, 1].max():.2e} oracle |e_pos| {erro[:, 0].max():.2e} "
+              f"|q - q_oracle| max {np.abs(q - qo).max():.2e} median {np.median(np.abs(q - qo).max(1)):.2e}")
+        assert (err[:, 0] < 5e-4).all() and (err[:, 1] < 5e-3).all() and (erro[:, 0] < 5e-4).all(), name
+        assert np.abs(q - qo).max() < 5e-3, (name, np.abs(q - qo).max())
+        assert np.median(np.abs(q - qo).max(1)) < 1e-4, name
+        q16[:, :9] = q
+        sc.set_state(qpos=q16)
+        pos2 = sc.get_links()[0].cpu().numpy()
+        assert np.abs(pos2[:, link] - tp).max() < 6e-4, name
+        moved = {"link1": 1, "link4": 4, "hand": 7}[name]
+        assert np.array_equal(q[:, moved:], seed[:, moved:].astype(np.float32)), f"{name}: a joint off the chain moved"
