@@ -474,6 +474,7 @@ int mir_destroy(MirHandle h) {
   if (h->scratch_row) (void)hipFree(h->scratch_row);
   if (h->pre) (void)hipFree(h->pre);
   if (h->ray_tab) (void)hipFree(h->ray_tab);
+  if (h->dist_tab) (void)hipFree(h->dist_tab);
   if (h->pin_host) (void)hipHostFree(h->pin_host);
   exact_destroy(h);
   delete h;

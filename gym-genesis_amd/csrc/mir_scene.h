@@ -110,6 +110,10 @@ struct MirScene {
   // RANGE SENSING (mir_raycast, mir_ray.hip): the geometry table with the hulls' face planes, built by the first call
   void* ray_tab;            // device
   int ray_state;            // 0 not built yet, 1 built, -1 the scene has a hull without volume (every call fails)
+  // SIGNED DISTANCE (mir_signed_distance, mir_dist.hip): its geometry table with the hulls' face planes and triangle fans, built by the first call
+  void* dist_tab;           // device
+  int dist_state;           // as ray_state
+  int dist_nplane;          // planes in the table (the triangles follow them)
 };
 
 // library-internal helpers implemented in mir_api.hip

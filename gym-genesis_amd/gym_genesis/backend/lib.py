@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirTaskQuery, MirVisualSpec, make_acc_query, make_dyn_query, make_ik_multi, make_kin_query, make_ray_query, make_task_query  # noqa: F401
+from .spec import IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirTaskQuery, MirVisualSpec, make_acc_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_ray_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -143,6 +143,9 @@ def load_library() -> C.CDLL:
     lib.mir_ray_query_sizeof.restype = C.c_int
     lib.mir_raycast.argtypes = [vp, C.POINTER(MirRayQuery), vp, vp, i32, vp, vp, vp, vp, vp]
     lib.mir_raycast.restype = C.c_int
+    lib.mir_dist_query_sizeof.restype = C.c_int
+    lib.mir_signed_distance.argtypes = [vp, C.POINTER(MirDistQuery), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_signed_distance.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
@@ -159,6 +162,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirTaskQuery (rebuild the library)")
     if lib.mir_ray_query_sizeof() != C.sizeof(MirRayQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRayQuery (rebuild the library)")
+    if lib.mir_dist_query_sizeof() != C.sizeof(MirDistQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirDistQuery (rebuild the library)")
     if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
     _lib = lib
@@ -871,6 +876,55 @@ class MirScene(StepHelpers):
         self._check(self.lib.mir_raycast(self.h, C.byref(q), _ptr(d), _ptr(idx), R, _ptr(out.get("distance")), _ptr(out.get("points")),
                                          _ptr(out.get("geom")), _ptr(out.get("normal")), self._stream()))
         self.raycast_launches = self.__dict__.get("raycast_launches", 0) + 1
+        return out
+
+    def signed_distance(self, probes, links=None, env_idx=None, qpos=None, max_distance: float = 1.0, skip_geoms=0, geom: bool = False,
+                        closest: bool = False, normal: bool = False, row_min: bool = False) -> dict:
+        """mir_signed_distance: the signed distance from the N probe spheres `probes` ((N,4) float32: centre in the frame of the probe's
+        link, radius; a device tensor is used as it is) to the nearest geom, for the envs `env_idx` (int64, any order, repeats allowed;
+        None: all envs), in ONE launch of a kernel of its own.  `links` (N,) host integers: the body each probe rides on (0: the world;
+        None: all in the world).  Every geom not in `skip_geoms` (indices, or the bit mask) is tested, each as its exact shape.
+        `qpos` (R,nq), in the layout of get_state(), is evaluated instead of the rows' current state, for this call only.
+        distance (R,N) = distance to the surface minus the probe's radius, negative inside, max_distance on a miss; geom (R,N) int32,
+        -1 on a miss; closest (R,N,3) = the nearest surface point in world axes (the probe centre on a miss); normal (R,N,3) = the unit
+        outward gradient, 0 on a miss; row_min: adds row_min (R,) and row_argmin (R,) int32, the lowest distance of a row and its probe.
+        distance and what was asked for are returned: fresh device tensors on the current stream.  The call changes nothing a later
+        call can see."""
+        if not isinstance(probes, torch.Tensor):
+            probes = torch.as_tensor(np.ascontiguousarray(probes, dtype=np.float32))
+        p = probes.to(device=self.device, dtype=torch.float32).contiguous()
+        if p.dim() != 2 or p.shape[1] != 4 or p.shape[0] < 1:
+            raise ValueError(f"probes must be (N, 4) with N >= 1, got {tuple(p.shape)}")
+        N = int(p.shape[0])
+        lk = None
+        if links is not None:
+            lk = np.ascontiguousarray(links.cpu().numpy() if isinstance(links, torch.Tensor) else links, dtype=np.int32).reshape(-1)
+            if lk.shape[0] != N:
+                raise ValueError(f"links must be ({N},), got {lk.shape}")
+        q = make_dist_query(N, max_distance, skip_geoms)
+        idx = None
+        if env_idx is not None:
+            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        R = self.num_envs if idx is None else int(idx.numel())
+        if qpos is not None:
+            qpos = torch.as_tensor(qpos, device=self.device).to(torch.float32).contiguous()
+            if tuple(qpos.shape) != (R, self.nq):
+                raise ValueError(f"qpos must be ({R}, {self.nq}), got {tuple(qpos.shape)}")
+        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        out = {"distance": new(N)}
+        if geom:
+            out["geom"] = new(N, dtype=torch.int32)
+        if closest:
+            out["closest"] = new(N, 3)
+        if normal:
+            out["normal"] = new(N, 3)
+        if row_min:
+            out["row_min"], out["row_argmin"] = new(), new(dtype=torch.int32)
+        self._check(self.lib.mir_signed_distance(self.h, C.byref(q), _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p), _ptr(idx), R,
+                                                 _ptr(qpos), _ptr(out["distance"]), _ptr(out.get("geom")), _ptr(out.get("closest")),
+                                                 _ptr(out.get("normal")), _ptr(out.get("row_min")), _ptr(out.get("row_argmin")), self._stream()))
+        if R > 0:
+            self.distance_launches = self.__dict__.get("distance_launches", 0) + 1
         return out
 
     def render(self, cam: MirCameraSpec, vis: MirVisualSpec, mode: int = 0, env_offset: Optional[torch.Tensor] = None,

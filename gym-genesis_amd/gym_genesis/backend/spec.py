@@ -434,6 +434,41 @@ def make_ray_query(n_rays: int, link: int = 0, pos_offset=(0.0, 0.0, 0.0), quat_
     return q
 
 
+DIST_MAX_PROBES = 1024  # probes of one mir_signed_distance call (include/mirigid.h)
+
+
+class MirDistQuery(C.Structure):
+    """include/mirigid.h: MirDistQuery (mir_signed_distance)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_probes", C.c_int32),
+        ("max_distance", C.c_float),
+        ("flags", C.c_uint32),
+        ("skip_geoms", C.c_uint64),
+    ]
+
+
+def _geom_mask(skip_geoms) -> int:
+    """geom indices that are not tested, or the bit mask itself"""
+    if isinstance(skip_geoms, int):
+        return skip_geoms
+    mask = 0
+    for g in skip_geoms:
+        if not 0 <= int(g) < 64:
+            raise ValueError(f"skip_geoms: geom index {g} outside 0 .. 63")
+        mask |= 1 << int(g)
+    return mask
+
+
+def make_dist_query(n_probes: int, max_distance: float = 1.0, skip_geoms=()) -> MirDistQuery:
+    """skip_geoms: geom indices that are not tested, or the bit mask."""
+    q = MirDistQuery()
+    q.struct_size = C.sizeof(MirDistQuery)
+    q.n_probes, q.max_distance, q.flags = int(n_probes), float(max_distance), 0
+    q.skip_geoms = _geom_mask(skip_geoms)
+    return q
+
+
 IK_DEFAULTS = dict(max_iters=20, respect_joint_limit=1, damping=0.05, pos_tol=5e-4, rot_tol=5e-3, max_step=0.5)
 
 RENDER_PER_ENV, RENDER_GLOBAL = 0, 1

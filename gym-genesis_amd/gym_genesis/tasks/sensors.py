@@ -291,9 +291,68 @@ class ImuSensor:
         return ImuData(r[:, 0, 0:3].contiguous(), r[:, 0, 3:6].contiguous())
 
 
+@dataclass
+class Proximity:
+    """Options of a proximity sensor (this package's own: parity with Genesis unpinned): the signed distance from one probe sphere to
+    the nearest surface, whatever the direction -- negative inside a solid, which a ray never reports.  `link` / `entity` as for
+    Raycaster (None: fixed in the world); `pos_offset`: the probe's centre in the link's frame; `radius`: of the probe; `max_range`:
+    what is reported when nothing is that near; `skip_own_entity`: the geoms of the link's own entity are not tested."""
+    entity: Any = None
+    link: Any = None
+    pos_offset: Tuple[float, float, float] = (0.0, 0.0, 0.0)
+    radius: float = 0.0
+    max_range: float = 1.0
+    skip_own_entity: bool = True
+
+
+ProximityData = namedtuple("ProximityData", ("distance", "point", "normal"))
+
+
+class ProximitySensor:
+    """What SceneView.add_sensor returns for Proximity options.  The probe is uploaded once."""
+
+    def __init__(self, mir, options):
+        self._mir, self.options = mir, options
+        spec = mir.spec
+        body = _link_body(options)
+        if not 0 <= body < spec.nbody:
+            raise ValueError(f"link body {body} outside the scene's {spec.nbody} bodies")
+        if not (float(options.radius) >= 0.0 and float(options.max_range) > 0.0):
+            raise ValueError("a proximity sensor needs radius >= 0 and max_range > 0")
+        self.link_body = body
+        own = set()
+        if options.entity is not None:
+            own = set(int(b) for b in options.entity.link_idx)
+        elif body > 0:
+            top = lambda b: b if spec.body[b].parent == 0 else top(spec.body[b].parent)  # noqa: E731
+            own = {b for b in range(1, spec.nbody) if top(b) == top(body)}
+        self.skip_geoms = 0
+        if options.skip_own_entity:
+            for g in range(spec.ngeom):
+                if spec.geom[g].body in own:
+                    self.skip_geoms |= 1 << g
+        probe = np.array([[*(float(v) for v in options.pos_offset), float(options.radius)]], dtype=np.float32)
+        self._probe = torch.as_tensor(probe, device=mir.device)
+        self._links = np.array([body], dtype=np.int32)
+
+    def read(self, envs_idx=None) -> ProximityData:
+        """-> named tuple (distance (R,), point (R, 3) the nearest surface point in world axes, normal (R, 3) unit, from the surface
+        towards the probe); nothing within max_range: max_range, the probe's own centre, 0.  One launch."""
+        from .views import _env_index
+
+        fn = getattr(self._mir, "signed_distance", None)
+        if fn is None:
+            raise NotImplementedError("this scene has no signed distance (MirScene.signed_distance / mir_signed_distance)")
+        r = fn(self._probe, links=self._links, env_idx=_env_index(self._mir, envs_idx), max_distance=float(self.options.max_range),
+               skip_geoms=self.skip_geoms, closest=True, normal=True)
+        return ProximityData(r["distance"][:, 0], r["closest"][:, 0], r["normal"][:, 0])
+
+
 def make_sensor(mir, options):
     if isinstance(options, IMU):
         return ImuSensor(mir, options)
+    if isinstance(options, Proximity):
+        return ProximitySensor(mir, options)
     if not isinstance(options, Raycaster):
         raise TypeError(f"add_sensor takes Raycaster / Lidar / DepthCamera options, got {type(options).__name__}")
     return RaySensor(mir, options)

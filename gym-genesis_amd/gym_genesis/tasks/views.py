@@ -453,6 +453,163 @@ class EntityView:
         """(B, n, 6): jbar of operational_space(), the dynamically consistent generalised inverse of get_jacobian(link)."""
         return self.operational_space(link, local_point, envs_idx, damping, qpos)["jbar"]
 
+    # ---- clearance (MirScene.signed_distance / mir_signed_distance): the entity as a set of spheres that ride on its links (the
+    # sphere model of cuRobo-style planners), the rest of the scene as its exact primitives.  One launch per call.  The names are this
+    # package's own: parity with Genesis is unpinned.
+    def _covered_links(self) -> list:
+        """the links with at least one dof on their path to the world (a base bolted to the floor never moves: it is left out)"""
+        bodies, out = self._b.bodies, []
+        for b in self.link_idx:
+            k, moves = b, False
+            while k > 0:
+                moves = moves or bodies[k]["jtype"] != 0
+                k = bodies[k]["parent"]
+            if moves:
+                out.append(b)
+        return out
+
+    def collision_spheres(self, spacing=None):
+        """-> (probes (N, 4) float32: centre in the link's frame and radius, probe_link (N,) int32: body index of the scene), derived
+        on the host, deterministically, from the collision geoms of the links that have at least one dof on their path to the world (a
+        base bolted to the floor is left out), in geom order.  The spheres of a geom together CONTAIN it:
+          sphere:  itself.
+          capsule: centres along the axis from end point to end point, both included, at most `spacing` apart (default: half the
+                   radius); the radius is sqrt(r^2 + (gap / 2)^2), gap = the distance between neighbouring centres -- the capsule's own
+                   radius would leave the surface between two centres uncovered.
+          box:     a regular grid of n_x x n_y x n_z equal cells, n_i = ceil(2 h_i / min(2 min(h), spacing)), and one sphere about every
+                   cell: its circumscribed sphere, radius = |cell half extents|.
+          hull:    the same grid over the bounding box of its vertices in the geom frame; a grid of one cell takes the smaller of
+                   that sphere and the bounding sphere of the vertices about the box's centre.
+        No radius exceeds the geom's own bounding radius (but for float32 rounding, which every radius is padded for).
+        set_collision_spheres() replaces the model."""
+        custom = self.__dict__.get("_spheres")
+        if custom is not None and spacing is None:
+            return custom[0].copy(), custom[1].copy()
+        return self._derive_spheres(spacing)[:2]
+
+    def _derive_spheres(self, spacing=None):
+        """collision_spheres() from the geoms -> (probes, probe_link, the geom each sphere belongs to)"""
+        from ..backend import spec as S
+
+        covered, probes, links, geoms = set(self._covered_links()), [], [], []
+
+        def rot(q, v):
+            w, u = q[0], np.asarray(q[1:], float)
+            t = 2.0 * np.cross(u, v)
+            return v + w * t + np.cross(u, t)
+
+        def grid(centre, half, q, cap=np.inf):
+            half = np.asarray(half, float)
+            edge = 2.0 * half.min() if spacing is None else min(2.0 * half.min(), float(spacing))
+            n = np.maximum(1, np.ceil(2.0 * half / edge - 1e-9)).astype(int)
+            cell = half / n
+            r = float(np.linalg.norm(cell)) if n.max() > 1 else min(float(np.linalg.norm(cell)), cap)
+            for i in range(n[0]):
+                for j in range(n[1]):
+                    for k in range(n[2]):
+                        local = -half + cell * (2.0 * np.array([i, j, k]) + 1.0)
+                        yield np.append(np.asarray(centre, float) + rot(q, local), r)
+
+        for gi, g in enumerate(self._b.geoms):
+            if g["body"] not in covered:
+                continue
+            pos, q, size, t = np.asarray(g["pos"], float), g["quat"], g["size"], g["type"]
+            if t == S.GEOM_SPHERE:
+                rows = [np.append(pos, size[0])]
+            elif t == S.GEOM_CAPSULE:
+                r, hl = float(size[0]), float(size[1])
+                gap_max = 0.5 * r if spacing is None else float(spacing)
+                n = 1 if hl <= 0.0 else int(np.ceil(2.0 * hl / gap_max - 1e-9)) + 1
+                gap = 0.0 if n == 1 else 2.0 * hl / (n - 1)
+                rad = float(np.hypot(r, 0.5 * gap))
+                rows = [np.append(pos + rot(q, np.array([0.0, 0.0, -hl + gap * i])), rad) for i in range(n)]
+            elif t == S.GEOM_BOX:
+                rows = list(grid(pos, size, q))
+            elif t == S.GEOM_HULL:
+                v = np.asarray(self._b.verts[int(size[0]):int(size[0]) + int(size[1])], float)
+                lo, hi = v.min(0), v.max(0)
+                rows = list(grid(pos + rot(q, 0.5 * (lo + hi)), 0.5 * (hi - lo), q, cap=float(np.linalg.norm(v - 0.5 * (lo + hi), axis=1).max())))
+            else:
+                continue   # (a plane has no sphere model)
+            probes.extend(rows)
+            links.extend([g["body"]] * len(rows))
+            geoms.extend([gi] * len(rows))
+        out = np.asarray(probes, dtype=np.float64).reshape(-1, 4)
+        # (the model is float32: every radius grows by what rounding the centre and the radius can take away, 2^-22 relative)
+        out[:, 3] += 2.0 ** -22 * (np.abs(out[:, :3]).max(1) + out[:, 3])
+        return out.astype(np.float32), np.asarray(links, dtype=np.int32), np.asarray(geoms, dtype=np.int32)
+
+    def set_collision_spheres(self, probes, links) -> None:
+        """Replace the sphere model: probes (N, 4) centre in the link's frame and radius, links (N,) body indices of the scene (or
+        LinkViews of this entity)."""
+        p = np.ascontiguousarray(probes, dtype=np.float32).reshape(-1, 4)
+        lk = np.asarray([l.idx if isinstance(l, LinkView) else int(l) for l in links], dtype=np.int32)
+        if lk.shape[0] != p.shape[0] or p.shape[0] < 1:
+            raise ValueError(f"probes (N, 4) and links (N,) must have the same N >= 1, got {p.shape} and {lk.shape}")
+        if any(int(b) not in self.link_idx for b in lk):
+            raise ValueError("a sphere rides on a link that does not belong to this entity")
+        if not (np.isfinite(p).all() and (p[:, 3] >= 0).all()):
+            raise ValueError("sphere centres must be finite and radii >= 0")
+        self._spheres = (p, lk)
+        self.__dict__.pop("_sphere_model", None)
+
+    def _own_geoms(self) -> int:
+        """bit mask of the geoms on this entity's links (the way sensors.Lidar computes skip_geoms)"""
+        mask = 0
+        for g, geom in enumerate(self._b.geoms):
+            if geom["body"] in self.link_idx:
+                mask |= 1 << g
+        return mask
+
+    def get_clearance(self, qpos=None, envs_idx=None, links=None, with_entity=None, max_distance: float = 1.0, return_detail: bool = False):
+        """(R,): the lowest signed distance between this entity's sphere model (collision_spheres(), or what set_collision_spheres()
+        put in its place) and every geom that does not belong to the entity itself -- with `with_entity`, only that entity's geoms --
+        from ONE launch; negative = penetration depth, max_distance when nothing is that near.  `qpos` (R, n) in this entity's own dof
+        order, as inverse_kinematics returns it: the clearance AT that configuration, with the other entities where they are; None: at
+        the current state.  `links` (local link indices or LinkViews): only the spheres on those links.  return_detail=True: a dict
+        with clearance (R,), sphere (R,) index into the model, link (R,) body index, geom (R,) (-1: nothing within max_distance), closest
+        (R, 3) surface point and normal (R, 3) of the minimum.
+        Self-collision (the entity's spheres against its own geoms or each other) is out of scope, and so is what lies between two
+        configurations: a clear start and a clear goal say nothing about the path."""
+        mir = self._mir
+        fn = getattr(mir, "signed_distance", None)
+        if fn is None:
+            raise NotImplementedError("this scene has no signed distance (MirScene.signed_distance / mir_signed_distance)")
+        model = self.__dict__.get("_sphere_model")   # (derived once: the model on the host, its probes on the device)
+        if model is None or model[2].device != mir.device:
+            probes, lk = self.collision_spheres()
+            if len(lk) == 0:
+                raise ValueError("no collision sphere to test (an entity without moving links or without geoms on them)")
+            model = self._sphere_model = (probes, lk, torch.as_tensor(probes, device=mir.device), self._own_geoms())
+        probes, lk, dev_probes, own = model
+        sel = None
+        if links is not None:
+            want = set(self._link_bodies(links))
+            sel = np.array([i for i, b in enumerate(lk) if int(b) in want], dtype=np.int64)
+            if len(sel) == 0:
+                raise ValueError("no collision sphere rides on the links asked for")
+            dev_probes, lk = torch.as_tensor(probes[sel], device=mir.device), np.ascontiguousarray(lk[sel])
+        skip = own
+        if with_entity is not None:
+            skip |= ((1 << len(self._b.geoms)) - 1) & ~with_entity._own_geoms()
+        idx = _env_index(mir, envs_idx)
+        R = mir.num_envs if idx is None else int(idx.numel())
+        kw = self._full_state_rows(idx, R, qpos=qpos, who="get_clearance")
+        r = fn(dev_probes, links=lk, env_idx=idx, max_distance=float(max_distance), skip_geoms=skip, geom=return_detail, closest=return_detail,
+               normal=return_detail, row_min=True, **kw)
+        if not return_detail:
+            return r["row_min"]
+        arg = r["row_argmin"].long()
+        take = lambda t: t.gather(1, arg.view(R, 1, *([1] * (t.dim() - 2))).expand(R, 1, *t.shape[2:]))[:, 0]  # noqa: E731
+        sphere = arg if sel is None else torch.as_tensor(sel, device=mir.device)[arg]
+        return {"clearance": r["row_min"], "sphere": sphere, "link": torch.as_tensor(lk, device=mir.device).long()[arg],
+                "geom": take(r["geom"]), "closest": take(r["closest"]), "normal": take(r["normal"])}
+
+    def in_collision(self, qpos=None, envs_idx=None, margin: float = 0.0, links=None, with_entity=None) -> torch.Tensor:
+        """(R,) bool: get_clearance(...) < margin -- the sphere model touches or penetrates something (margin = 0), or comes nearer than
+        `margin`.  Self-collision is out of scope (see get_clearance)."""
+        return self.get_clearance(qpos=qpos, envs_idx=envs_idx, links=links, with_entity=with_entity, max_distance=max(1.0, 2.0 * float(margin))) < float(margin)
+
     def get_link(self, name: str) -> LinkView:
         return LinkView(self._mir, self._b.body_index(name), name)
 
@@ -867,7 +1024,24 @@ class SceneView:
         """``scene.add_sensor(gs.sensors.Lidar(...))``: a ray-cast range sensor (tasks/sensors.py: Raycaster / Lidar / DepthCamera options)
         on a link or fixed in the world; ``sensor.read()`` -> (points, distances) in one launch (mir_raycast).
         ``scene.add_sensor(gs.sensors.IMU(...))``: an accelerometer and gyro on a link; ``sensor.read()`` -> (lin_acc, ang_vel) in one
-        launch (mir_link_accelerations)."""
+        launch (mir_link_accelerations).
+        ``scene.add_sensor(sensors.Proximity(...))``: a proximity probe on a link or in the world; ``sensor.read()`` -> (distance, point,
+        normal) in one launch (mir_signed_distance)."""
         from .sensors import make_sensor
 
         return make_sensor(self._mir, options)
+
+    def signed_distance(self, points, radius=0.0, link=None, envs_idx=None, max_distance: float = 1.0, skip_geoms=0, geom: bool = False,
+                        closest: bool = False, normal: bool = False) -> dict:
+        """The plain point query (mir_signed_distance, one launch): the signed distance from `points` ((N, 3), or (3,); in the frame of
+        `link` -- a LinkView or body index -- or in the world) with `radius` (a number or (N,)) to the nearest geom, negative inside a
+        solid: a dict with distance (R, N) and, when asked for, geom (R, N), closest (R, N, 3), normal (R, N, 3)."""
+        fn = getattr(self._mir, "signed_distance", None)
+        if fn is None:
+            raise NotImplementedError("this scene has no signed distance (MirScene.signed_distance / mir_signed_distance)")
+        p = np.asarray(points.cpu() if isinstance(points, torch.Tensor) else points, dtype=np.float32).reshape(-1, 3)
+        probes = np.concatenate([p, np.broadcast_to(np.asarray(radius, dtype=np.float32).reshape(-1, 1), (p.shape[0], 1))], axis=1)
+        body = 0 if link is None else (link.idx if isinstance(link, LinkView) else int(link))
+        links = None if body == 0 else np.full(p.shape[0], body, dtype=np.int32)
+        return fn(probes, links=links, env_idx=_env_index(self._mir, envs_idx), max_distance=float(max_distance), skip_geoms=skip_geoms, geom=geom,
+                  closest=closest, normal=normal)

@@ -667,6 +667,64 @@ int mir_raycast(MirHandle h, const MirRayQuery* q, const float* dirs /* (N,3) de
                 float* distance /* (R,N) */, float* points /* (R,N,3) */, int32_t* geom /* (R,N) */, float* normal /* (R,N,3) */,
                 void* stream);
 
+/* ---- signed distance: batched point / sphere to scene queries ------------------------------------------
+ * "How far is this point, or this arm, from the nearest thing?"  Proximity sensors, clearance rewards, potential fields, and the
+ * clearance of a sphere model of an arm (spheres that ride on its links) at the current state or at candidate configurations, before
+ * they are commanded (EntityView.get_clearance / in_collision; parity with Genesis unpinned).  mir_raycast measures along a direction and
+ * does not see a solid that contains its origin; mir_contact_forces knows only pairs that already touch.
+ * ONE launch of a kernel of its own for N probes, shared by all rows, on R rows: it reads the link poses (or the qpos rows given) and
+ * the compiled model and writes only its outputs.
+ *   R = n_rows, or num_envs when env_idx is NULL; row k belongs to env env_idx[k] (int64, device; repeats and any order allowed; an
+ *   index outside the batch is clamped as in mir_link_kinematics).  N = q->n_probes <= 1024.
+ * Probes.  probes (N, 4), device: centre xyz in the frame of the probe's link, radius >= 0.  probe_link (N), HOST memory, nullable (all
+ *   probes stand in the world): 0 = the world, else body 1 .. nbody-1 the probe rides on.  It is a host array so that it is checked
+ *   without a read-back; the library copies it into the launch's arguments, one byte per probe, which is where the cap of 1024 probes
+ *   comes from.  Nothing of it is kept after the call returns.
+ * Per-geom signed distance d_g, with the probe centre p in the geom's frame: negative inside, `closest` the nearest surface point.
+ *   Plane: the solid is the half space z <= 0 (as in the step kernel): d = p.z, closest = (p.x, p.y, 0), normal +z.
+ *   Sphere: d = |p| - r.  Capsule: d = |p - c| - r with c the point of the axis segment nearest p.
+ *   Box: outside, the distance to clamp(p, -h, h); inside, max_i(|p_i| - h_i), closest on that face.
+ *   Hull: the exact convex polytope of its vertices (as mir_raycast treats it).  Inside (every face plane <= 0): max_f(n_f . p - d_f),
+ *   closest = the projection on that face.  Outside: the minimum over the hull's triangles of the closed-form point - triangle
+ *   distance; the triangles are a fan per face, built with the face planes once per handle on the host at the first call.
+ *   normal = the unit outward gradient of d_g in world axes.  Where it is not unique: +z of the geom frame at a sphere's centre and on
+ *   a capsule's axis; the face of the lower index for an interior point equidistant from two faces and for a point exactly on the
+ *   surface of a box or hull (box faces are indexed by axis x, y, z; hull faces in the order the table finds them, triples of vertex
+ *   indices ascending).
+ * Result per (row, probe).  s_g = d_g - radius over every geom whose bit in skip_geoms is clear; the lowest wins, ties go to the lower
+ *   geom index.  s <= max_distance: distance = s, geom = its index of the spec, closest = the surface point in world axes (the env's own
+ *   frame, no env offsets), normal as above.  Otherwise a miss: distance = max_distance, geom = -1, closest = the probe centre (world),
+ *   normal = 0.  row_min (R) / row_argmin (R) = the lowest distance of the row and its probe index, the lower index on a tie (a row of
+ *   misses: max_distance and 0).
+ * Poses.  qpos NULL: the rasteriser's pose cache, refreshed exactly as mir_raycast does (one forward-kinematics launch, only when the
+ *   state has moved since it was written).  qpos (R, nq), device: row k is the full configuration in the layout of mir_get_state, for
+ *   this evaluation only; free-joint quaternions are normalised; the kernel computes the world pose of every body itself from the
+ *   compiled model, parent before child (a free body's pose is its qpos pose; paths longer than 16 bodies: MIR_E_CAPACITY).  The pose
+ *   cache is neither read nor written on this path.
+ * Every output is nullable and written only when asked for; all six NULL, or R == 0: MIR_OK without a launch.
+ * A call changes nothing a later call can see: state, targets, warm start, state version, diagnostics, counters and the scratch row of
+ * a split step stay as they are, and the steps around it are bit for bit those of a run without it.
+ * MIR_E_INVALID: a NULL handle, query or probes; struct_size != sizeof(MirDistQuery); n_probes < 1; a max_distance that is not finite
+ * or not > 0; an unknown flag bit; a skip_geoms bit at or above ngeom; a probe_link outside 0 .. nbody - 1; a call while a
+ * mir_step_begin is open; a hull without volume.  MIR_E_CAPACITY: N > 1024; R x N beyond 2^31 - 1.  None of them launches anything.
+ * Not covered: self-collision of the sphere model, swept volumes, robot geoms other than through spheres.
+ * (An added struct and entry point: MIR_VERSION and every other struct stay as they are.) */
+typedef struct MirDistQuery {
+  int32_t  struct_size;   /* = sizeof(MirDistQuery) */
+  int32_t  n_probes;      /* N, 1 .. 1024 */
+  float    max_distance;  /* > 0, finite */
+  uint32_t flags;         /* 0; unknown bits are MIR_E_INVALID */
+  uint64_t skip_geoms;    /* bit g set: geom g is not tested */
+} MirDistQuery;
+int mir_dist_query_sizeof(void);
+int mir_signed_distance(MirHandle h, const MirDistQuery* q,
+                        const float* probes /* (N,4) device: centre xyz in the link's frame, radius >= 0 */,
+                        const int32_t* probe_link /* (N) HOST, nullable = all in the world; 0 = world, else body 1..nbody-1 */,
+                        const int64_t* env_idx /* device, nullable */, int32_t n_rows,
+                        const float* qpos /* (R,nq) device, nullable: evaluate at these configurations, not the current state */,
+                        float* distance /* (R,N) */, int32_t* geom /* (R,N) */, float* closest /* (R,N,3) */, float* normal /* (R,N,3) */,
+                        float* row_min /* (R) */, int32_t* row_argmin /* (R) */, void* stream);
+
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
