@@ -39,22 +39,9 @@
 
 #include "mir_hullfan.h"
 
+#include "mir_dist_body.h"
+
 namespace {
-
-constexpr int DIST_MAX_PROBES = 1024;
-constexpr int DIST_REC = 24;  // floats per LDS record
-
-// per-handle geometry table (device): the geoms as the spec has them, and the face planes and triangle fans of every hull
-struct DistGeom {
-  int32_t type, body, p0, np, t0, nt, _pad[2];  // p0, np / t0, nt: the hull's planes / triangles behind the table
-  float size[3], rad;                           // rad: radius of the bounding sphere about the geom frame's origin
-  float pos[3], quat[4], _pad2;
-};
-struct DistTab {
-  int32_t ngeom, nplane, ntri, _pad;
-  DistGeom g[MIR_MAX_GEOM];
-  // float4 planes[nplane], then float4 tris[3 * ntri] follow (geom frame)
-};
 
 struct DistArgs {
   const DistTab* tab;
@@ -73,25 +60,6 @@ struct DistArgs {
   uint8_t link[DIST_MAX_PROBES];   // all zero when every probe stands in the world
 };
 static_assert(sizeof(DistArgs) <= 4096, "kernel arguments");
-
-// closest point of the triangle (a, b, c) to p: the regions of the Voronoi diagram of its features, highest priority last;
-// `face`: the foot of p on the triangle's plane lies inside it and p is on the outer side (a, b, c counter-clockwise seen from outside)
-__device__ __forceinline__ V3 closest_on_triangle(V3 p, V3 a, V3 b, V3 c, bool& face) {
-  const V3 ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c;
-  const float d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
-  const float vc = d1 * d4 - d3 * d2, vb = d5 * d2 - d1 * d6, va = d3 * d6 - d5 * d4;
-  const float den = 1.0f / (va + vb + vc);
-  float v = vb * den, w = vc * den;  // the face
-  bool in = true;
-  if (va <= 0.0f && d4 - d3 >= 0.0f && d5 - d6 >= 0.0f) { w = (d4 - d3) / ((d4 - d3) + (d5 - d6)); v = 1.0f - w; in = false; }  // edge bc
-  if (vb <= 0.0f && d2 >= 0.0f && d6 <= 0.0f) { w = d2 / (d2 - d6); v = 0.0f; in = false; }                                     // edge ac
-  if (d6 >= 0.0f && d5 <= d6) { v = 0.0f; w = 1.0f; in = false; }                                                                // vertex c
-  if (vc <= 0.0f && d1 >= 0.0f && d3 <= 0.0f) { v = d1 / (d1 - d3); w = 0.0f; in = false; }                                     // edge ab
-  if (d3 >= 0.0f && d4 <= d3) { v = 1.0f; w = 0.0f; in = false; }                                                                // vertex b
-  if (d1 <= 0.0f && d2 <= 0.0f) { v = 0.0f; w = 0.0f; in = false; }                                                              // vertex a
-  face = in && dot(ap, cross(ab, ac)) > 0.0f;
-  return a + v * ab + w * ac;
-}
 
 __global__ __launch_bounds__(64) void mir_dist_kernel(DistArgs a) {
   __shared__ float xp[MIR_MAX_BODY][4], xq[MIR_MAX_BODY][4];
@@ -140,39 +108,8 @@ __global__ __launch_bounds__(64) void mir_dist_kernel(DistArgs a) {
     }
   }
 
-  // ---- geom records, lane = geom
-  int count;
-  {
-    const DistTab* __restrict__ t = a.tab;
-    const int ng = t->ngeom;
-    const bool isg = lane < ng;
-    const int g = isg ? lane : 0;
-    const int b = t->g[g].body;
-    const V3 bp = ld3(xp[b]);
-    const Q4 bq = ld4(xq[b]);
-    // geom frame in the world: c = xpos + R(xquat) g_pos, q = xquat (x) g_quat
-    const V3 c = bp + qrot(bq, ld3(t->g[g].pos));
-    const M3 Rg = q2m(qnormalize(qmul(bq, ld4(t->g[g].quat))));
-    const bool keep = isg && !((a.skip >> g) & 1ull);
-    const unsigned long long m = __ballot(keep);
-    if (keep) {
-      const int slot = __popcll(m & ((1ull << lane) - 1ull));
-      float* r = rec + slot * DIST_REC;
-      const int type = t->g[g].type;
-      const float hl = type == MIR_GEOM_CAPSULE ? t->g[g].size[1] : 0.0f;
-      r[0] = __int_as_float(type); r[1] = __int_as_float(g);
-      r[2] = t->g[g].size[0]; r[3] = type == MIR_GEOM_BOX ? t->g[g].size[1] : hl; r[4] = t->g[g].size[2];
-      r[5] = c.x; r[6] = c.y; r[7] = c.z;
-      r[8] = Rg.r0.x; r[9] = Rg.r0.y; r[10] = Rg.r0.z;  // rows of R_g: its columns are the geom's axes in the world
-      r[11] = Rg.r1.x; r[12] = Rg.r1.y; r[13] = Rg.r1.z;
-      r[14] = Rg.r2.x; r[15] = Rg.r2.y; r[16] = Rg.r2.z;
-      r[17] = __int_as_float(t->g[g].p0); r[18] = __int_as_float(t->g[g].np);
-      r[19] = __int_as_float(t->g[g].t0); r[20] = __int_as_float(t->g[g].nt);
-      r[21] = t->g[g].rad;
-    }
-    count = __popcll(m);
-    WSYNC();
-  }
+  // ---- geom records, lane = geom (mir_dist_body.h)
+  int count = dist_build_records(a.tab, a.skip, lane, xp, xq, rec);
   count = __builtin_amdgcn_readfirstlane(count);
 
   // ---- probes, 64 at a time
@@ -185,98 +122,10 @@ __global__ __launch_bounds__(64) void mir_dist_kernel(DistArgs a) {
     const float radius = pr[3];
     const int lk = a.link[probe];
     const V3 pw = ld3(xp[lk]) + qrot(ld4(xq[lk]), ld3(pr));  // probe centre, world
-    float best = INFINITY;
-    int bestk = -1;
-    V3 bc = v3(0, 0, 0), bn = v3(0, 0, 0);  // closest point and normal of the best geom, in its frame
-    for (int k = 0; k < count; k++) {
-      const float* r = rec + k * DIST_REC;
-      const int type = __builtin_amdgcn_readfirstlane(__float_as_int(r[0]));
-      const V3 rel = pw - v3(r[5], r[6], r[7]);
-      // p = R_g^T rel
-      const V3 p = v3(r[8] * rel.x + r[11] * rel.y + r[14] * rel.z, r[9] * rel.x + r[12] * rel.y + r[15] * rel.z, r[10] * rel.x + r[13] * rel.y + r[16] * rel.z);
-      float d;
-      V3 cp, n;
-      if (type == MIR_GEOM_PLANE) {
-        d = p.z;
-        cp = v3(p.x, p.y, 0.0f);
-        n = v3(0, 0, 1);
-      } else if (type == MIR_GEOM_BOX) {
-        const float h[3] = {r[2], r[3], r[4]}, pp[3] = {p.x, p.y, p.z};
-        float q[3], cl[3];
-#pragma unroll
-        for (int i = 0; i < 3; i++) {
-          q[i] = fabsf(pp[i]) - h[i];
-          cl[i] = fminf(fmaxf(pp[i], -h[i]), h[i]);
-        }
-        int im = 0;
-        float qm = q[0];
-        if (q[1] > qm) { qm = q[1]; im = 1; }
-        if (q[2] > qm) { qm = q[2]; im = 2; }
-        const V3 v = v3(pp[0] - cl[0], pp[1] - cl[1], pp[2] - cl[2]);
-        const float dv = sqrtf(dot(v, v));
-        if (qm > 0.0f && dv > 0.0f) {  // outside: the clamped point
-          d = dv;
-          n = (1.0f / dv) * v;
-          cp = v3(cl[0], cl[1], cl[2]);
-        } else {  // inside or on the surface: the nearest face, the lower axis on a tie
-          d = qm;
-          const float sg = pp[im] >= 0.0f ? 1.0f : -1.0f;
-          n = v3(im == 0 ? sg : 0.0f, im == 1 ? sg : 0.0f, im == 2 ? sg : 0.0f);
-          cp = v3(im == 0 ? sg * h[0] : pp[0], im == 1 ? sg * h[1] : pp[1], im == 2 ? sg * h[2] : pp[2]);
-        }
-      } else if (type == MIR_GEOM_HULL) {
-        const int p0 = __builtin_amdgcn_readfirstlane(__float_as_int(r[17])), np = __builtin_amdgcn_readfirstlane(__float_as_int(r[18]));
-        const int t0 = __builtin_amdgcn_readfirstlane(__float_as_int(r[19])), nt = __builtin_amdgcn_readfirstlane(__float_as_int(r[20]));
-        float sm = -INFINITY;
-        V3 nm = v3(0, 0, 1);
-        for (int f = 0; f < np; f++) {
-          const float* pl = a.planes + 4 * (p0 + f);
-          const float px = pl[0], py = pl[1], pz = pl[2], pd = pl[3];
-          const float s = px * p.x + py * p.y + pz * p.z - pd;
-          if (s > sm) { sm = s; nm = v3(px, py, pz); }  // (strict: the lower face index on a tie)
-        }
-        d = sm;
-        n = nm;
-        cp = p - sm * nm;
-        // outside: the triangles, unless no lane of the wave can improve on what it holds (|p| - rad bounds the distance from below)
-        const bool need = sm > 0.0f && sqrtf(dot(p, p)) - r[21] - radius <= fminf(best, a.max_distance);
-        if (__ballot(need) != 0ull) {
-          // A triangle that holds the foot of p with p on its outer side holds the nearest point of the whole hull (the hull lies
-          // behind that plane): it is taken outright.  Left to the comparison of squared distances, a point a little inside such a
-          // triangle and the point of its edge that a neighbour offers differ by the SQUARE of their distance, and float32 picks either.
-          float d2m = INFINITY;
-          V3 cm = cp;
-          bool done = false;
-          for (int ti = 0; ti < nt; ti++) {
-            const float* tr = a.tris + 12 * (t0 + ti);
-            bool face;
-            const V3 c = closest_on_triangle(p, v3(tr[0], tr[1], tr[2]), v3(tr[4], tr[5], tr[6]), v3(tr[8], tr[9], tr[10]), face);
-            const V3 v = p - c;
-            const float d2 = dot(v, v);
-            if (!done && (face || d2 < d2m)) { d2m = d2; cm = c; }  // (strict: the lower face index on a tie)
-            done = done || face;
-          }
-          if (sm > 0.0f) {
-            const float dd = sqrtf(d2m);
-            d = dd;
-            cp = cm;
-            if (dd > 0.0f) n = (1.0f / dd) * (p - cm);  // (dd == 0: on the surface to float32, the face's normal stays)
-          }
-        } else if (sm > 0.0f) {
-          d = INFINITY;  // (cannot win, cannot be within max_distance)
-        }
-      } else {  // capsule about |z| <= hl (sphere: hl = 0)
-        const float rad = r[2], hl = r[3];
-        const float cz = fminf(fmaxf(p.z, -hl), hl);
-        const V3 v = v3(p.x, p.y, p.z - cz);
-        const float len = sqrtf(dot(v, v));
-        d = len - rad;
-        n = len > 0.0f ? (1.0f / len) * v : v3(0, 0, 1);  // (the centre, the axis: +z of the geom frame)
-        cp = v3(rad * n.x, rad * n.y, cz + rad * n.z);
-      }
-      const float s = d - radius;
-      if (s < best) { best = s; bestk = k; bc = cp; bn = n; }  // (strict: a tie stays with the lower geom index)
-    }
+    const DistBest w = dist_probe_min(rec, count, a.planes, a.tris, pw, radius, a.max_distance);
+    const float best = w.best;
+    const int bestk = w.bestk;
+    const V3 bc = w.bc, bn = w.bn;  // closest point and normal of the best geom, in its frame
     const bool hit = bestk >= 0 && best <= a.max_distance;
     const float dist = hit ? best : a.max_distance;
     const size_t cell = (size_t)row * a.N + probe;
@@ -313,7 +162,7 @@ __global__ __launch_bounds__(64) void mir_dist_kernel(DistArgs a) {
 }
 
 // ---- the geometry table, once per handle: geoms as the compiled model holds them (float32), hull faces by mir_hullfan.h
-int build_tab(MirScene* h) {
+int build_tab(MirScene* h, const char* who) {
   DistTab tab;
   memset(&tab, 0, sizeof tab);
   HullFan fan;
@@ -328,12 +177,12 @@ int build_tab(MirScene* h) {
       r.pos[k] = k16 ? h->hm.g_pos[g][k] : h->hm64.g_pos[g][k];
     }
     for (int k = 0; k < 4; k++) r.quat[k] = k16 ? h->hm.g_quat[g][k] : h->hm64.g_quat[g][k];
-    if (r.body < 0 || r.body >= h->nbody) return mir_set_error(MIR_E_INVALID, "mir_signed_distance: a geom's body lies outside the scene");
+    if (r.body < 0 || r.body >= h->nbody) return query_error(MIR_E_INVALID, who, "a geom's body lies outside the scene");
     double rad = 0.0;
     if (r.type == MIR_GEOM_HULL) {
       const int v0 = (int)r.size[0], nv = (int)r.size[1];
       const int pool = k16 ? K16_MAX_VERT : MIR_MAX_VERT;
-      if (v0 < 0 || nv < 0 || nv > MIR_MAX_HULL_VERT || v0 + nv > pool) return mir_set_error(MIR_E_INVALID, "mir_signed_distance: a hull's vertices lie outside the pool");
+      if (v0 < 0 || nv < 0 || nv > MIR_MAX_HULL_VERT || v0 + nv > pool) return query_error(MIR_E_INVALID, who, "a hull's vertices lie outside the pool");
       double v[MIR_MAX_HULL_VERT][3];
       for (int i = 0; i < nv; i++) {
         for (int k = 0; k < 3; k++) v[i][k] = k16 ? h->hm.hverts[v0 + i][k] : h->hm64.hverts[v0 + i][k];
@@ -341,7 +190,7 @@ int build_tab(MirScene* h) {
       }
       r.p0 = (int)(fan.planes.size() / 4);
       r.t0 = (int)(fan.tris.size() / 12);
-      if (!hull_fan_build(v, nv, fan)) return mir_set_error(MIR_E_INVALID, "mir_signed_distance: a hull geom has no volume (its vertices lie in one plane)");
+      if (!hull_fan_build(v, nv, fan)) return query_error(MIR_E_INVALID, who, "a hull geom has no volume (its vertices lie in one plane)");
       r.np = (int)(fan.planes.size() / 4) - r.p0;
       r.nt = (int)(fan.tris.size() / 12) - r.t0;
     }
@@ -367,7 +216,13 @@ int build_tab(MirScene* h) {
 
 }  // namespace
 
-static_assert(sizeof(DistTab) % 16 == 0 && sizeof(DistGeom) % 16 == 0, "the planes and triangles behind the table are 16-byte rows");
+// the table of the handle for the entry points that read it (this file and mir_plan.hip); the verdict on a hull without volume is kept
+int mir_dist_table(MirScene* h, const char* who) {
+  int rc = MIR_OK;
+  if (h->dist_state == 0) h->dist_state = (rc = build_tab(h, who)) == MIR_OK ? 1 : (rc == MIR_E_INVALID ? -1 : 0);
+  else if (h->dist_state < 0) rc = query_error(MIR_E_INVALID, who, "a hull geom has no volume (its vertices lie in one plane)");
+  return rc;
+}
 
 extern "C" int mir_dist_query_sizeof(void) { return (int)sizeof(MirDistQuery); }
 
@@ -405,9 +260,7 @@ extern "C" int mir_signed_distance(MirHandle h, const MirDistQuery* q, const flo
   DeviceGuard guard(h->device);  // (the table's allocation and the pose refresh, too)
   int rc = MIR_OK;
   do {
-    if (h->dist_state == 0) h->dist_state = (rc = build_tab(h)) == MIR_OK ? 1 : (rc == MIR_E_INVALID ? -1 : 0);
-    else if (h->dist_state < 0) rc = query_error(MIR_E_INVALID, who, "a hull geom has no volume (its vertices lie in one plane)");
-    if (rc != MIR_OK) break;
+    if ((rc = mir_dist_table(h, who)) != MIR_OK) break;
     if (R == 0 || (!distance && !geom && !closest && !normal && !row_min && !row_argmin)) break;  // (nothing asked for)
     // link poses: the rasteriser's pose cache, refreshed when the state has moved since it was written; not touched with qpos rows
     if (!qpos && !h->poses_current && (rc = mir_refresh_poses(h, stream)) != MIR_OK) break;

@@ -1,0 +1,558 @@
+// mir_plan.hip — batched collision-checked motion planning (mir_plan_path) and the swept clearance of a given trajectory
+// (mir_path_clearance); include/mirigid.h, DESIGN.md "Motion planning".
+//
+// What it serves: for a list of envs, one launch takes each row's arm from a start configuration to a goal configuration through
+// configurations whose sphere model (probe spheres that ride on links, as in mir_signed_distance) keeps `margin` from every geom that is
+// not skipped: RRT-Connect in the space of the D planned dofs, shortcut smoothing, resampling to W waypoints.  The second entry point
+// streams a caller's trajectory through the same configuration check and reports the lowest clearance per segment.
+//
+// Mapping: one workgroup of one wave64 per row, as mir_dist.hip.  WSYNC() only; nothing travels from lane to lane through global memory.
+//   Row set-up.  The row's full start configuration (nq floats) goes to LDS; forward kinematics with lane = body (joint_local, composed
+//   parent before child); the geom records are built ONCE (dist_build_records): the host guarantees that every geom that is tested rides
+//   on a body without a planned dof above it.
+//   clear(q).  Lane j < D writes planned dof j into the LDS row; the bodies below a planned dof (bit 15 of their word) are recomputed,
+//   every other body keeps its pose; the probes in chunks of 64 through dist_probe_min; the wave minimum of (distance - radius).
+//   A configuration is a float per lane: lane j holds dof j, lanes >= D hold 0.
+//   Trees.  Two trees in dynamic LDS: coordinates [tree][dof][node] (lanes stride over nodes: conflict free) and a 16-bit parent.
+// Bounds: every loop is bounded by max_iterations, max_nodes, the 4096 samples of an edge (PLAN_MAX_SUB: n_sub is clamped), the
+//   MIR_PLAN_MAX_POLY nodes of a polyline, smooth_passes, num_waypoints or (mir_path_clearance) the K points of the caller's path.  No
+//   input can keep a wave running: a configuration or a geom pose that is not finite counts as blocked, a nearest-node index is
+//   clamped to the tree.
+// Stores: plain dword stores by lanes 0 .. D-1 (or lane 0).  No atomics, no scratch, no cross-wave barrier.
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <cmath>
+#include <cstring>
+
+#include "mir_model.h"
+#include "mir_model64.h"
+#include "mir_scene.h"
+
+#define G 16
+#include "mir_dev.h"
+
+#include "mir_query.h"
+
+#include "mir_dist_body.h"
+
+namespace {
+
+constexpr int PLAN_MAX_DOF = 16;
+constexpr int PLAN_MAX_SUB = 4096;  // samples of one edge
+constexpr int PLAN_NO_PARENT = 0xffff;
+
+struct PlanArgs {
+  const DistTab* tab;
+  const float *planes, *tris;
+  const float* qpos;    // the scene's state (rows of qst floats, addressed like the public layout)
+  const float* qpos_o;  // (R, nq) public layout, nullable
+  int qst, B, n_rows, N, nbody, nq, depth_max, D;
+  int W, max_nodes, max_iter, smooth, ignore, K;
+  uint32_t seed;
+  float resolution, step, margin, max_distance;
+  unsigned long long skip;
+  const float* probes;
+  const long long* env_idx;
+  const float* goal;  // mir_plan_path: (R, D); mir_path_clearance: paths (R, K, D)
+  JointPtrs m;
+  float* path;
+  int32_t* status;
+  float* poly;
+  int32_t *n_poly, *stats;
+  float *seg_min, *row_min;
+  int32_t* first_blocked;
+  float lo[PLAN_MAX_DOF], hi[PLAN_MAX_DOF];
+  int32_t qadr[PLAN_MAX_DOF];
+  uint32_t body[MIR_MAX_BODY];    // parent | jtype << 8 | depth << 10 | (a planned dof on its path to the world) << 15
+  uint8_t link[DIST_MAX_PROBES];  // all zero when every probe stands in the world
+};
+static_assert(sizeof(PlanArgs) <= 4096, "kernel arguments");
+
+// the fixed part of the LDS (the trees follow in dynamic LDS)
+struct PlanLds {
+  float xp[MIR_MAX_BODY][4], xq[MIR_MAX_BODY][4];
+  float rec[MIR_MAX_GEOM * DIST_REC];
+  float qrow[MIR_MAX_Q];
+  float qs[PLAN_MAX_DOF];
+  float poly[MIR_PLAN_MAX_POLY][PLAN_MAX_DOF];
+  float cum[MIR_PLAN_MAX_POLY];
+};
+
+// ---- random numbers: u(env, c, j) in [0, 1), keyed by the env index
+__device__ __forceinline__ uint32_t plan_mix(uint32_t x) {
+  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ float plan_u(uint32_t seed, uint32_t env, uint32_t c, uint32_t j) {
+  const uint32_t x = plan_mix(plan_mix(plan_mix(seed ^ env) ^ c) ^ j);
+  return (float)(x >> 8) * 5.9604644775390625e-8f;  // 2^-24
+}
+
+// x / y with one refinement of the quotient (x >= 0, y > 0): within an ulp of the exact quotient whatever the division flags of the build
+__device__ __forceinline__ float div_refined(float x, float y) {
+  const float r = 1.0f / y;
+  const float t = x * r;
+  return fmaf(fmaf(-t, y, x), r, t);
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
+  return v;
+}
+
+// what a row carries through its launch (wave-uniform but for `lane`)
+struct PlanRow {
+  const PlanArgs& a;
+  PlanLds& L;
+  int lane, count, checked;
+  bool bad;  // a geom record is not finite (a free body's pose in the row is not): every clearance is -INFINITY
+
+  // forward kinematics, lane = body: every body (all) or the bodies below a planned dof; the arithmetic of mir_dist_kernel
+  __device__ __forceinline__ void fk(bool all) {
+    const bool isb = lane < a.nbody;
+    const int b = isb ? lane : 0;
+    const uint32_t bw = a.body[b];
+    const int par = bw & 0xff, jt = (bw >> 8) & 3, depth = (bw >> 10) & 31;
+    const bool mine = isb && (all || ((bw >> 15) & 1u));
+    const JointLocal jl = joint_local(mine && b > 0, b, jt, L.qrow, a.m);
+    V3 P = jl.P;
+    Q4 Qx = jl.Qx;
+    for (int lvl = 0; lvl <= a.depth_max; lvl++) {
+      if (mine && depth == lvl) {
+        if (lvl > 0) {
+          const V3 pp = ld3(L.xp[par]);
+          const Q4 pq = ld4(L.xq[par]);
+          P = pp + qrot(pq, P);
+          Qx = qmul(pq, Qx);
+        }
+        st3(L.xp[b], P);
+        st4(L.xq[b], Qx);
+      }
+      WSYNC();
+    }
+  }
+
+  // the lowest (signed distance - radius) over the probes at the poses in LDS, max_distance when nothing is that near.  A probe centre
+  // that is not finite (a NaN or an infinity in the configuration reaches it through the forward kinematics) gives -INFINITY, blocked:
+  // left to the comparisons of dist_probe_min such a probe would lose against every geom and count as a miss, which is clear.
+  __device__ __forceinline__ float clearance_at_poses() {
+    float mn = INFINITY;
+    unsigned long long nan = 0ull;
+    for (int base = 0; base < a.N; base += 64) {
+      const bool valid = base + lane < a.N;
+      const int probe = valid ? base + lane : a.N - 1;
+      const float* const pr = a.probes + (size_t)probe * 4;
+      const float radius = pr[3];
+      const int lk = a.link[probe];
+      const V3 pw = ld3(L.xp[lk]) + qrot(ld4(L.xq[lk]), ld3(pr));
+      const DistBest w = dist_probe_min(L.rec, count, a.planes, a.tris, pw, radius, a.max_distance);
+      const bool hit = w.bestk >= 0 && w.best <= a.max_distance;
+      const float dist = hit ? w.best : a.max_distance;
+      nan |= __ballot(valid && (nonfinite(pw.x) || nonfinite(pw.y) || nonfinite(pw.z)));
+      if (valid) mn = fminf(mn, dist);
+    }
+    mn = wave_min(mn);
+    return nan != 0ull || bad ? -INFINITY : mn;
+  }
+
+  // clear(q): the clearance of configuration q (lane j: planned dof j)
+  __device__ __forceinline__ float clearance(float q) {
+    if (a.ignore) return a.max_distance;
+    if (__ballot(lane < a.D && nonfinite(q)) != 0ull) {  // (not a configuration: blocked, and kept out of the row)
+      checked++;
+      return -INFINITY;
+    }
+    if (lane < a.D) L.qrow[a.qadr[lane]] = q;
+    WSYNC();
+    fk(false);
+    checked++;
+    return clearance_at_poses();
+  }
+
+  // samples of the edge a -> b: n_sub = max(1, ceil(max_j |b_j - a_j| / resolution)), at most PLAN_MAX_SUB
+  __device__ __forceinline__ int n_sub(float diff) const {
+    const float m = wave_max(lane < a.D ? fabsf(diff) : 0.0f);
+    return __builtin_amdgcn_readfirstlane((int)fminf(fmaxf(ceilf(div_refined(m, a.resolution)), 1.0f), (float)PLAN_MAX_SUB));
+  }
+  __device__ __forceinline__ static float sample(float av, float bv, float diff, int i, int n) {
+    return i == n ? bv : av + div_refined((float)i, (float)n) * diff;  // (the last sample is b's bits)
+  }
+
+  // edge(a, b): the samples i = 1 .. n_sub in order; the first blocked one ends the check
+  __device__ __forceinline__ bool edge(float av, float bv) {
+    const float diff = bv - av;
+    const int n = n_sub(diff);
+    for (int i = 1; i <= n; i++)
+      if (!(clearance(sample(av, bv, diff, i, n)) >= a.margin)) return false;
+    return true;
+  }
+
+  // sum_j v_j^2 over the planned dofs, j ascending, the same value in every lane
+  __device__ __forceinline__ float norm2(float v) {
+    if (lane < a.D) L.qs[lane] = v;
+    WSYNC();
+    float acc = 0.0f;
+    for (int j = 0; j < a.D; j++) {
+      const float e = L.qs[j];
+      acc = acc + e * e;
+    }
+    WSYNC();
+    return acc;
+  }
+};
+
+// ---- row set-up shared by the two kernels: the start row, every body's pose, the geom records
+__device__ __forceinline__ void plan_setup(PlanRow& r, int row, int env) {
+  const PlanArgs& a = r.a;
+  const float* const src = a.qpos_o ? a.qpos_o + (size_t)row * a.nq : a.qpos + (size_t)env * a.qst;
+  for (int i = r.lane; i < a.nq; i += 64) r.L.qrow[i] = src[i];
+  WSYNC();
+  r.fk(true);
+  r.count = a.ignore ? 0 : __builtin_amdgcn_readfirstlane(dist_build_records(a.tab, a.skip, r.lane, r.L.xp, r.L.xq, r.L.rec));
+  bool badrec = false;
+  if (r.lane < r.count)
+    for (int k = 5; k <= 16; k++) badrec = badrec || nonfinite(r.L.rec[r.lane * DIST_REC + k]);  // the geom's centre and axes
+  r.bad = __ballot(badrec) != 0ull;
+}
+
+__device__ __forceinline__ int plan_env(const PlanArgs& a, int row) {
+  const int env = a.env_idx ? (int)a.env_idx[row] : row;
+  return env < 0 ? 0 : (env >= a.B ? a.B - 1 : env);  // (an index outside the batch is clamped, as in mir_link_kinematics)
+}
+
+extern __shared__ float plan_dyn[];
+
+__global__ __launch_bounds__(64) void mir_plan_kernel(PlanArgs a) {
+  __shared__ PlanLds L;
+  const int lane = threadIdx.x, row = blockIdx.x, D = a.D, MN = a.max_nodes;
+  const int env = plan_env(a, row);
+  float* const tree = plan_dyn;                                                        // [2][D][MN]
+  uint16_t* const parent = reinterpret_cast<uint16_t*>(plan_dyn + (size_t)2 * D * MN);  // [2][MN]
+  PlanRow r{a, L, lane, 0, 0, false};
+  plan_setup(r, row, env);
+  const bool isd = lane < D;
+  const int dj = isd ? lane : 0;
+  const float lo = a.lo[dj], hi = a.hi[dj];
+  const float sv = isd ? L.qrow[a.qadr[dj]] : 0.0f;
+  const float gv = isd ? a.goal[(size_t)row * D + dj] : 0.0f;
+  WSYNC();
+
+  auto node = [&](int t, int n) { return isd ? tree[((size_t)t * D + dj) * MN + n] : 0.0f; };
+  auto add = [&](int t, int n, float v, int par) {
+    if (isd) tree[((size_t)t * D + dj) * MN + n] = v;
+    if (lane == 0) parent[t * MN + n] = (uint16_t)par;
+    WSYNC();
+  };
+  // nearest node of tree t (cnt nodes) to q: squared L2 distance over the planned dofs, j ascending; the lower index wins a tie
+  auto nearest = [&](int t, int cnt, float q, float& d2) {
+    if (isd) L.qs[lane] = q;
+    WSYNC();
+    float bd = INFINITY;
+    int bi = 0x7fffffff;
+    for (int n = lane; n < cnt; n += 64) {
+      float acc = 0.0f;
+      for (int j = 0; j < D; j++) {
+        const float e = tree[((size_t)t * D + j) * MN + n] - L.qs[j];
+        acc = acc + e * e;
+      }
+      if (acc < bd) { bd = acc; bi = n; }  // (nodes ascend: the lower index keeps a tie)
+    }
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) {
+      const float om = __shfl_xor(bd, off);
+      const int oi = __shfl_xor(bi, off);
+      if (om < bd || (om == bd && oi < bi)) { bd = om; bi = oi; }
+    }
+    WSYNC();
+    d2 = bd;
+    bi = __builtin_amdgcn_readfirstlane(bi);
+    return bi < cnt ? bi : 0;
+  };
+
+  int status = MIR_PLAN_OK, iterations = 0, na = 1, nb = 1, npoly = 1;
+  const bool outside = isd && !(gv >= lo && gv <= hi);
+  if (__ballot(outside) != 0ull) status = MIR_PLAN_GOAL_OUT_OF_LIMITS;
+  else if (!(r.clearance(sv) >= a.margin)) status = MIR_PLAN_START_IN_COLLISION;
+  else if (!(r.clearance(gv) >= a.margin)) status = MIR_PLAN_GOAL_IN_COLLISION;
+  else if (r.edge(sv, gv)) {
+    if (isd) { L.poly[0][lane] = sv; L.poly[1][lane] = gv; }
+    npoly = 2;
+  } else {
+    add(0, 0, sv, PLAN_NO_PARENT);
+    add(1, 0, gv, PLAN_NO_PARENT);
+    status = MIR_PLAN_ITERATION_LIMIT;
+    for (int it = 0; it < a.max_iter; it++) {
+      iterations = it + 1;
+      const int t = it & 1, o = t ^ 1;
+      int ct = t ? nb : na, co = t ? na : nb;
+      const float qr = isd ? lo + plan_u(a.seed, (uint32_t)env, (uint32_t)it, (uint32_t)dj) * (hi - lo) : 0.0f;
+      float d2;
+      const int near = nearest(t, ct, qr, d2);
+      const float nv = node(t, near);
+      const float qn = nv + fminf(1.0f, a.step / sqrtf(d2)) * (qr - nv);
+      if (!r.edge(nv, qn)) continue;
+      if (ct >= MN) { status = MIR_PLAN_NODE_LIMIT; break; }
+      add(t, ct, qn, near);
+      const int inew = ct++;
+      // connect: from the other tree's nearest node towards q_new, at most `step` at a time
+      int ci = nearest(o, co, qn, d2);
+      float cv = node(o, ci);
+      bool met = false, full = false;
+      for (int k = 0; k < MN; k++) {  // (every pass adds a node or leaves)
+        const float diff = qn - cv;
+        const float d = sqrtf(r.norm2(diff));
+        const bool last = d <= a.step;
+        const float tv = last ? qn : cv + (a.step / d) * diff;
+        if (!r.edge(cv, tv)) break;
+        if (co >= MN) { full = true; break; }
+        add(o, co, tv, ci);
+        ci = co++;
+        cv = tv;
+        if (last) { met = true; break; }
+      }
+      na = t ? co : ct;
+      nb = t ? ct : co;
+      if (full) { status = MIR_PLAN_NODE_LIMIT; break; }
+      if (!met) continue;
+      // extract: the parents of both trees into one polyline, start first
+      const int ia = t ? ci : inew, ib = t ? inew : ci;
+      int la = 0, lb = 0;
+      for (int n = ia; n != PLAN_NO_PARENT && la <= MN; n = __builtin_amdgcn_readfirstlane((int)parent[n])) la++;
+      for (int n = ib; n != PLAN_NO_PARENT && lb <= MN; n = __builtin_amdgcn_readfirstlane((int)parent[MN + n])) lb++;
+      if (la + lb - 1 > MIR_PLAN_MAX_POLY) { status = MIR_PLAN_PATH_TOO_LONG; break; }
+      int n = ia;
+      for (int p = la - 1; p >= 0; p--) {
+        if (isd) L.poly[p][lane] = node(0, n);
+        n = __builtin_amdgcn_readfirstlane((int)parent[n]);
+      }
+      n = __builtin_amdgcn_readfirstlane((int)parent[MN + ib]);  // (the meeting node is in both trees: once)
+      for (int p = la; p < la + lb - 1; p++) {
+        if (isd) L.poly[p][lane] = node(1, n);
+        n = __builtin_amdgcn_readfirstlane((int)parent[MN + n]);
+      }
+      npoly = la + lb - 1;
+      status = MIR_PLAN_OK;
+      break;
+    }
+  }
+  if (status != MIR_PLAN_OK) {  // the arm stays put: the start W times, a polyline of one node
+    if (isd) L.poly[0][lane] = sv;
+    npoly = 1;
+  }
+  WSYNC();
+
+  // ---- smooth: shortcuts between two nodes of the polyline
+  for (int s = 0; s < a.smooth && npoly >= 3; s++) {
+    const float u0 = plan_u(a.seed, (uint32_t)env, 0x80000000u | (uint32_t)s, 0u), u1 = plan_u(a.seed, (uint32_t)env, 0x80000000u | (uint32_t)s, 1u);
+    const int i = min((int)(u0 * (float)(npoly - 2)), npoly - 3);
+    const int j = i + 2 + min((int)(u1 * (float)(npoly - 2 - i)), npoly - 3 - i);
+    if (!r.edge(isd ? L.poly[i][lane] : 0.0f, isd ? L.poly[j][lane] : 0.0f)) continue;
+    for (int k = j; k < npoly; k++)  // (every lane moves its own column)
+      if (isd) L.poly[i + 1 + k - j][lane] = L.poly[k][lane];
+    npoly -= j - i - 1;
+  }
+  WSYNC();
+
+  // ---- resample: W configurations at equal steps of the cumulative L2 length
+  float total = 0.0f;
+  for (int k = 0; k + 1 < npoly; k++) {
+    const float d = sqrtf(r.norm2(isd ? L.poly[k + 1][lane] - L.poly[k][lane] : 0.0f));
+    if (lane == 0) L.cum[k] = total;
+    total = total + d;
+    if (lane == 0) L.cum[k + 1] = total;
+  }
+  WSYNC();
+  {
+    float* const out = a.path + (size_t)row * a.W * D;
+    int k = 0;
+    for (int w = 0; w < a.W; w++) {
+      float q;
+      if (npoly == 1 || w == 0) q = isd ? L.poly[0][lane] : 0.0f;
+      else if (w == a.W - 1) q = isd ? L.poly[npoly - 1][lane] : 0.0f;
+      else {
+        const float f = div_refined((float)w, (float)(a.W - 1));
+        float t = f;  // (a polyline of one segment: the fraction itself, no length enters)
+        if (npoly > 2) {
+          const float s = f * total;
+          while (k < npoly - 2 && L.cum[k + 1] <= s) k++;
+          const float c0 = L.cum[k], len = L.cum[k + 1] - c0;
+          t = len > 0.0f ? fminf(div_refined(s - c0, len), 1.0f) : 0.0f;
+        }
+        const float p0 = isd ? L.poly[k][lane] : 0.0f, p1 = isd ? L.poly[k + 1][lane] : 0.0f;
+        q = p0 + t * (p1 - p0);
+      }
+      if (isd) out[(size_t)w * D + lane] = q;
+    }
+  }
+  if (a.poly) {
+    float* const out = a.poly + (size_t)row * MIR_PLAN_MAX_POLY * D;
+    for (int k = 0; k < MIR_PLAN_MAX_POLY; k++)
+      if (isd) out[(size_t)k * D + lane] = k < npoly ? L.poly[k][lane] : 0.0f;
+  }
+  if (lane == 0) {
+    a.status[row] = status;
+    if (a.n_poly) a.n_poly[row] = npoly;
+    if (a.stats) {
+      int32_t* const st = a.stats + (size_t)row * 4;
+      st[0] = iterations; st[1] = na; st[2] = nb; st[3] = r.checked;
+    }
+  }
+}
+
+// the swept check on its own: every sample of the edge rule on every segment of the caller's path, no early exit
+__global__ __launch_bounds__(64) void mir_path_clear_kernel(PlanArgs a) {
+  __shared__ PlanLds L;
+  const int lane = threadIdx.x, row = blockIdx.x, D = a.D;
+  PlanRow r{a, L, lane, 0, 0, false};
+  plan_setup(r, row, plan_env(a, row));
+  const bool isd = lane < D;
+  const float* const p = a.goal + (size_t)row * a.K * D;
+  float rmin = INFINITY;
+  int first = -1;
+  float av = isd ? p[lane] : 0.0f;
+  for (int k = 0; k + 1 < a.K; k++) {
+    const float bv = isd ? p[(size_t)(k + 1) * D + lane] : 0.0f;
+    float smin = k == 0 ? r.clearance(av) : INFINITY;  // (a segment's first point counts only for segment 0)
+    const float diff = bv - av;
+    const int n = r.n_sub(diff);
+    for (int i = 1; i <= n; i++) smin = fminf(smin, r.clearance(PlanRow::sample(av, bv, diff, i, n)));
+    if (a.seg_min && lane == 0) a.seg_min[(size_t)row * (a.K - 1) + k] = smin;
+    rmin = fminf(rmin, smin);
+    if (first < 0 && smin < a.margin) first = k;
+    av = bv;
+  }
+  if (lane == 0) {
+    if (a.row_min) a.row_min[row] = rmin;
+    if (a.first_blocked) a.first_blocked[row] = first;
+  }
+}
+
+// ---- host: what the two entry points share.  Fills `a` but for the outputs; every refusal launches nothing.
+int plan_front(MirHandle h, const MirPlanQuery* q, const char* who, bool planner, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+               const int64_t* env_idx, int32_t n_rows, const float* qpos_start, PlanArgs& a, long long& R) {
+  if (!h || !q || !probes || !dof_qadr) return query_error(MIR_E_INVALID, who, "null argument");
+  if (q->struct_size != (int32_t)sizeof(MirPlanQuery)) return query_error(MIR_E_INVALID, who, "struct_size is not sizeof(MirPlanQuery)");
+  if (q->n_probes < 1) return query_error(MIR_E_INVALID, who, "n_probes < 1");
+  if (q->n_dofs < 1 || q->n_dofs > PLAN_MAX_DOF) return query_error(MIR_E_INVALID, who, "n_dofs outside 1 .. 16");
+  if (!std::isfinite(q->resolution) || !(q->resolution > 0.0f)) return query_error(MIR_E_INVALID, who, "resolution must be finite and > 0");
+  if (!std::isfinite(q->margin) || !(q->margin >= 0.0f)) return query_error(MIR_E_INVALID, who, "margin must be finite and >= 0");
+  if (!std::isfinite(q->max_distance) || !(q->max_distance > q->margin)) return query_error(MIR_E_INVALID, who, "max_distance must be finite and > margin");
+  if (q->flags & ~(uint32_t)MIR_PLAN_IGNORE_COLLISION) return query_error(MIR_E_INVALID, who, "unknown flag bit");
+  if (h->ngeom < 64 && (q->skip_geoms >> h->ngeom)) return query_error(MIR_E_INVALID, who, "skip_geoms names a geom at or above ngeom");
+  if (planner) {
+    if (q->num_waypoints < 2) return query_error(MIR_E_INVALID, who, "num_waypoints < 2");
+    if (q->max_nodes < 2) return query_error(MIR_E_INVALID, who, "max_nodes < 2");
+    if (q->max_iterations < 0 || q->smooth_passes < 0) return query_error(MIR_E_INVALID, who, "negative max_iterations or smooth_passes");
+    if (!std::isfinite(q->step) || !(q->step > 0.0f)) return query_error(MIR_E_INVALID, who, "step must be finite and > 0");
+  }
+  if (h->pending) return query_error(MIR_E_INVALID, who, "a step is pending (mir_step_end first)");
+  if (env_idx && n_rows < 0) return query_error(MIR_E_INVALID, who, "negative n_rows");
+  R = env_idx ? n_rows : h->B;
+  const int N = q->n_probes, D = q->n_dofs;
+  if (N > DIST_MAX_PROBES) return query_error(MIR_E_CAPACITY, who, "more than 1024 probes in one call");
+  memset(&a, 0, sizeof a);
+  if (probe_link)
+    for (int i = 0; i < N; i++) {
+      if (probe_link[i] < 0 || probe_link[i] >= h->nbody) return query_error(MIR_E_INVALID, who, "probe_link outside 0 .. nbody - 1");
+      a.link[i] = (uint8_t)probe_link[i];
+    }
+  const ModelView mv(h);
+  // the planned dofs: the scalar joint behind each qpos address, its limits
+  bool planned[MIR_MAX_BODY] = {false}, moves[MIR_MAX_BODY] = {false};
+  for (int j = 0; j < D; j++) {
+    int body = -1;
+    for (int b = 1; b < h->nbody; b++) {
+      const int jt = mv.jtype(b);
+      if ((jt == MIR_JNT_REVOLUTE || jt == MIR_JNT_PRISMATIC) && mv.qadr(b) == dof_qadr[j]) body = b;
+    }
+    if (body < 0) return query_error(MIR_E_INVALID, who, "dof_qadr is not the qpos address of a revolute or prismatic joint");
+    if (planned[body]) return query_error(MIR_E_INVALID, who, "dof_qadr names a joint twice");
+    planned[body] = true;
+    double lo, hi;
+    int limited;
+    mv.limits(body, lo, hi, limited);
+    if (!limited || !(hi > lo)) return query_error(MIR_E_INVALID, who, "a planned dof has no limits");
+    if ((hi - lo) / (double)q->resolution > (double)PLAN_MAX_SUB) return query_error(MIR_E_INVALID, who, "a planned dof's range exceeds 4096 x resolution");
+    a.lo[j] = (float)lo; a.hi[j] = (float)hi; a.qadr[j] = dof_qadr[j];
+  }
+  int depth_max = 0;
+  for (int b = 1; b < h->nbody; b++) {  // (body order: a parent comes before its children)
+    const int par = mv.parent(b), jt = mv.jtype(b);
+    const bool chained = par > 0 && jt != MIR_JNT_FREE;
+    const int depth = chained ? (int)((a.body[par] >> 10) & 31) + 1 : 0;
+    if (depth >= G) return query_error(MIR_E_CAPACITY, who, "path longer than 16 bodies");
+    moves[b] = planned[b] || (chained && moves[par]);
+    a.body[b] = (uint32_t)par | (uint32_t)jt << 8 | (uint32_t)depth << 10 | (uint32_t)(moves[b] ? 1 : 0) << 15;
+    if (depth > depth_max) depth_max = depth;
+  }
+  a.ignore = (q->flags & MIR_PLAN_IGNORE_COLLISION) ? 1 : 0;
+  if (!a.ignore)
+    for (int g = 0; g < h->ngeom; g++) {
+      const int b = h->kernel == 16 ? h->hm.g_body[g] : h->hm64.g_body[g];
+      if (!((q->skip_geoms >> g) & 1ull) && b >= 0 && b < h->nbody && moves[b])
+        return query_error(MIR_E_INVALID, who, "a geom that is not skipped rides on a planned joint (a moving obstacle is out of scope: skip it)");
+    }
+  if (planner) {
+    const size_t lds = sizeof(PlanLds) + (size_t)2 * (size_t)q->max_nodes * (4 * (size_t)D + 2);
+    if (q->max_nodes > 0xfffe || lds > 65536) return query_error(MIR_E_CAPACITY, who, "the two trees do not fit 64 KB of LDS (max_nodes x n_dofs)");
+  }
+  a.qpos = h->qpos; a.qpos_o = qpos_start; a.qst = h->pt.qst; a.B = h->B; a.n_rows = (int)R; a.N = N; a.nbody = h->nbody; a.nq = h->nq;
+  a.depth_max = depth_max; a.D = D;
+  a.resolution = q->resolution; a.margin = q->margin; a.max_distance = q->max_distance; a.skip = q->skip_geoms;
+  a.probes = probes; a.env_idx = reinterpret_cast<const long long*>(env_idx);
+  a.m = mv.joint_pointers();
+  return MIR_OK;
+}
+
+int plan_launch(MirHandle h, const char* who, void (*kernel)(PlanArgs), PlanArgs& a, long long R, size_t dyn, void* stream) {
+  DeviceGuard guard(h->device);  // (the table's allocation, too)
+  const int rc = mir_dist_table(h, who);
+  if (rc != MIR_OK) return rc;
+  const char* const tab = static_cast<const char*>(h->dist_tab);
+  a.tab = reinterpret_cast<const DistTab*>(tab);
+  a.planes = reinterpret_cast<const float*>(tab + sizeof(DistTab));
+  a.tris = a.planes + 4 * (size_t)h->dist_nplane;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)R), dim3(64), dyn, (hipStream_t)stream, a);
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? MIR_OK : mir_set_error(MIR_E_HIP, hipGetErrorString(e));
+}
+
+}  // namespace
+
+extern "C" int mir_plan_query_sizeof(void) { return (int)sizeof(MirPlanQuery); }
+
+extern "C" int mir_plan_path(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+                             const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal, float* path,
+                             int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
+  static const char who[] = "mir_plan_path";
+  if (!qpos_goal || !path || !status) return query_error(MIR_E_INVALID, who, "null argument");
+  PlanArgs a;
+  long long R = 0;
+  const int rc = plan_front(h, q, who, true, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
+  if (rc != MIR_OK || R == 0) return rc;
+  a.W = q->num_waypoints; a.max_nodes = q->max_nodes; a.max_iter = q->max_iterations; a.smooth = q->smooth_passes; a.seed = q->seed; a.step = q->step;
+  a.goal = qpos_goal; a.path = path; a.status = status; a.poly = poly; a.n_poly = n_poly; a.stats = stats;
+  return plan_launch(h, who, mir_plan_kernel, a, R, (size_t)2 * (size_t)a.max_nodes * (4 * (size_t)a.D + 2), stream);
+}
+
+extern "C" int mir_path_clearance(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+                                  const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* paths, int32_t K,
+                                  float* seg_min, float* row_min, int32_t* row_first_blocked, void* stream) {
+  static const char who[] = "mir_path_clearance";
+  if (!paths) return query_error(MIR_E_INVALID, who, "null argument");
+  if (K < 2) return query_error(MIR_E_INVALID, who, "K < 2");
+  PlanArgs a;
+  long long R = 0;
+  const int rc = plan_front(h, q, who, false, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
+  if (rc != MIR_OK || R == 0 || (!seg_min && !row_min && !row_first_blocked)) return rc;
+  a.K = K; a.goal = paths; a.seg_min = seg_min; a.row_min = row_min; a.first_blocked = row_first_blocked;
+  return plan_launch(h, who, mir_path_clear_kernel, a, R, 0, stream);
+}

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirRayQuery, MirSceneSpec, MirTaskQuery, MirVisualSpec, make_acc_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_ray_query, make_task_query  # noqa: F401
+from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirSceneSpec, MirTaskQuery, MirVisualSpec, make_acc_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -146,6 +146,11 @@ def load_library() -> C.CDLL:
     lib.mir_dist_query_sizeof.restype = C.c_int
     lib.mir_signed_distance.argtypes = [vp, C.POINTER(MirDistQuery), vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_signed_distance.restype = C.c_int
+    lib.mir_plan_query_sizeof.restype = C.c_int
+    lib.mir_plan_path.argtypes = [vp, C.POINTER(MirPlanQuery), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_plan_path.restype = C.c_int
+    lib.mir_path_clearance.argtypes = [vp, C.POINTER(MirPlanQuery), vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
+    lib.mir_path_clearance.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
@@ -164,6 +169,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRayQuery (rebuild the library)")
     if lib.mir_dist_query_sizeof() != C.sizeof(MirDistQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirDistQuery (rebuild the library)")
+    if lib.mir_plan_query_sizeof() != C.sizeof(MirPlanQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirPlanQuery (rebuild the library)")
     if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
     _lib = lib
@@ -925,6 +932,80 @@ class MirScene(StepHelpers):
                                                  _ptr(out.get("normal")), _ptr(out.get("row_min")), _ptr(out.get("row_argmin")), self._stream()))
         if R > 0:
             self.distance_launches = self.__dict__.get("distance_launches", 0) + 1
+        return out
+
+    def _plan_front(self, probes, links, dof_qadr, env_idx, qpos_start):
+        """the arguments mir_plan_path and mir_path_clearance share -> (probes on the device, links, dof addresses, row list, R, start rows)"""
+        if not isinstance(probes, torch.Tensor):
+            probes = torch.as_tensor(np.ascontiguousarray(probes, dtype=np.float32))
+        p = probes.to(device=self.device, dtype=torch.float32).contiguous()
+        if p.dim() != 2 or p.shape[1] != 4 or p.shape[0] < 1:
+            raise ValueError(f"probes must be (N, 4) with N >= 1, got {tuple(p.shape)}")
+        lk = None
+        if links is not None:
+            lk = np.ascontiguousarray(links.cpu().numpy() if isinstance(links, torch.Tensor) else links, dtype=np.int32).reshape(-1)
+            if lk.shape[0] != p.shape[0]:
+                raise ValueError(f"links must be ({p.shape[0]},), got {lk.shape}")
+        qa = np.ascontiguousarray(dof_qadr, dtype=np.int32).reshape(-1)
+        idx = None
+        if env_idx is not None:
+            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        R = self.num_envs if idx is None else int(idx.numel())
+        if qpos_start is not None:
+            qpos_start = torch.as_tensor(qpos_start, device=self.device).to(torch.float32).contiguous()
+            if tuple(qpos_start.shape) != (R, self.nq):
+                raise ValueError(f"qpos_start must be ({R}, {self.nq}), got {tuple(qpos_start.shape)}")
+        return p, lk, qa, idx, R, qpos_start
+
+    def plan_path(self, probes, links, dof_qadr, qpos_goal, env_idx=None, qpos_start=None, num_waypoints: int = 100, max_nodes: int = 256,
+                  max_iterations: int = 2000, smooth_passes: int = 64, ignore_collision: bool = False, seed: int = 0, resolution: float = 0.05,
+                  step: float = 0.3, margin: float = 0.0, max_distance: float = 1.0, skip_geoms=0) -> dict:
+        """mir_plan_path: for the envs `env_idx` (None: all), ONE launch plans a collision-checked path for the planned dofs `dof_qadr`
+        (qpos addresses of D limited scalar joints) from `qpos_start` ((R, nq) full rows in the layout of get_state(); None: the current
+        state) to `qpos_goal` (R, D): RRT-Connect, shortcut smoothing, resampling (include/mirigid.h has the algorithm).  `probes` (N, 4)
+        / `links` (N,) are the sphere model as in signed_distance(); every geom not in `skip_geoms` is an obstacle and must not ride on a
+        planned joint.  -> dict of fresh device tensors: path (R, W, D), status (R,) int32 (spec.PLAN_STATUS), poly (R, 128, D) the
+        polyline behind the waypoints, n_poly (R,), stats (R, 4): iterations, nodes of the two trees, configurations checked.  A row
+        that fails holds its start W times.  The call changes nothing a later call can see."""
+        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
+        D = int(qa.shape[0])
+        goal = torch.as_tensor(qpos_goal, device=self.device).to(torch.float32).contiguous()
+        if tuple(goal.shape) != (R, D):
+            raise ValueError(f"qpos_goal must be ({R}, {D}), got {tuple(goal.shape)}")
+        q = make_plan_query(p.shape[0], D, num_waypoints, max_nodes, max_iterations, smooth_passes, ignore_collision, seed, resolution, step,
+                            margin, max_distance, skip_geoms)
+        W = max(int(num_waypoints), 0)
+        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        out = {"path": new(W, D), "status": new(dtype=torch.int32), "poly": new(PLAN_MAX_POLY, D), "n_poly": new(dtype=torch.int32),
+               "stats": new(4, dtype=torch.int32)}
+        self._check(self.lib.mir_plan_path(self.h, C.byref(q), _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p),
+                                           qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(goal), _ptr(out["path"]),
+                                           _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]), _ptr(out["stats"]), self._stream()))
+        if R > 0:
+            self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
+        return out
+
+    def path_clearance(self, probes, links, dof_qadr, paths, env_idx=None, qpos_start=None, resolution: float = 0.05, margin: float = 0.0,
+                       max_distance: float = 1.0, skip_geoms=0) -> dict:
+        """mir_path_clearance: the swept check of the trajectories `paths` (R, K, D) over the planned dofs `dof_qadr`, in ONE launch:
+        every configuration the edge rule of mir_plan_path samples on every segment (at most `resolution` apart in every joint) is
+        evaluated like signed_distance(row_min=True) on the sphere model.  -> seg_min (R, K-1), row_min (R,), row_first_blocked (R,)
+        int32: the first segment whose minimum is < margin, -1: none.  Everything else as plan_path()."""
+        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
+        D = int(qa.shape[0])
+        paths = torch.as_tensor(paths, device=self.device).to(torch.float32).contiguous()
+        if paths.dim() != 3 or paths.shape[0] != R or paths.shape[2] != D or paths.shape[1] < 2:
+            raise ValueError(f"paths must be ({R}, K >= 2, {D}), got {tuple(paths.shape)}")
+        K = int(paths.shape[1])
+        q = make_plan_query(p.shape[0], D, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
+        out = {"seg_min": torch.empty((R, K - 1), dtype=torch.float32, device=self.device),
+               "row_min": torch.empty((R,), dtype=torch.float32, device=self.device),
+               "row_first_blocked": torch.empty((R,), dtype=torch.int32, device=self.device)}
+        self._check(self.lib.mir_path_clearance(self.h, C.byref(q), _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p),
+                                                qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(paths), K,
+                                                _ptr(out["seg_min"]), _ptr(out["row_min"]), _ptr(out["row_first_blocked"]), self._stream()))
+        if R > 0:
+            self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
         return out
 
     def render(self, cam: MirCameraSpec, vis: MirVisualSpec, mode: int = 0, env_offset: Optional[torch.Tensor] = None,

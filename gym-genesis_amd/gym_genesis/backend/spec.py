@@ -469,6 +469,48 @@ def make_dist_query(n_probes: int, max_distance: float = 1.0, skip_geoms=()) -> 
     return q
 
 
+PLAN_MAX_POLY = 128  # MIR_PLAN_MAX_POLY: nodes of the polyline mir_plan_path returns (include/mirigid.h)
+PLAN_MAX_DOF = 16
+PLAN_IGNORE_COLLISION = 1
+PLAN_STATUS = ("OK", "GOAL_OUT_OF_LIMITS", "START_IN_COLLISION", "GOAL_IN_COLLISION", "NODE_LIMIT", "ITERATION_LIMIT", "PATH_TOO_LONG")
+(PLAN_OK, PLAN_GOAL_OUT_OF_LIMITS, PLAN_START_IN_COLLISION, PLAN_GOAL_IN_COLLISION, PLAN_NODE_LIMIT, PLAN_ITERATION_LIMIT,
+ PLAN_PATH_TOO_LONG) = range(7)
+
+
+class MirPlanQuery(C.Structure):
+    """include/mirigid.h: MirPlanQuery (mir_plan_path, mir_path_clearance)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_probes", C.c_int32),
+        ("n_dofs", C.c_int32),
+        ("num_waypoints", C.c_int32),
+        ("max_nodes", C.c_int32),
+        ("max_iterations", C.c_int32),
+        ("smooth_passes", C.c_int32),
+        ("flags", C.c_uint32),
+        ("seed", C.c_uint32),
+        ("resolution", C.c_float),
+        ("step", C.c_float),
+        ("margin", C.c_float),
+        ("max_distance", C.c_float),
+        ("_pad", C.c_int32),
+        ("skip_geoms", C.c_uint64),
+    ]
+
+
+def make_plan_query(n_probes: int, n_dofs: int, num_waypoints: int = 100, max_nodes: int = 256, max_iterations: int = 2000, smooth_passes: int = 64,
+                    ignore_collision: bool = False, seed: int = 0, resolution: float = 0.05, step: float = 0.3, margin: float = 0.0,
+                    max_distance: float = 1.0, skip_geoms=()) -> MirPlanQuery:
+    """skip_geoms: geom indices that are not tested, or the bit mask."""
+    q = MirPlanQuery()
+    q.struct_size = C.sizeof(MirPlanQuery)
+    q.n_probes, q.n_dofs, q.num_waypoints, q.max_nodes = int(n_probes), int(n_dofs), int(num_waypoints), int(max_nodes)
+    q.max_iterations, q.smooth_passes, q.flags, q.seed = int(max_iterations), int(smooth_passes), PLAN_IGNORE_COLLISION if ignore_collision else 0, int(seed) & 0xffffffff
+    q.resolution, q.step, q.margin, q.max_distance = float(resolution), float(step), float(margin), float(max_distance)
+    q.skip_geoms = _geom_mask(skip_geoms)
+    return q
+
+
 IK_DEFAULTS = dict(max_iters=20, respect_joint_limit=1, damping=0.05, pos_tol=5e-4, rot_tol=5e-3, max_step=0.5)
 
 RENDER_PER_ENV, RENDER_GLOBAL = 0, 1

@@ -23,6 +23,10 @@ class _One:
         self.batch_envs = 1
         self.unbatched = True
 
+    def _set_robot(self, view):
+        view.unbatched = True   # (robot.plan_path(...) gives (W, n) and its companions drop the env axis, as the reference's unbatched scene does)
+        super()._set_robot(view)
+
     @staticmethod
     def _squeeze(obs):
         out = {}

@@ -561,6 +561,17 @@ class EntityView:
                 mask |= 1 << g
         return mask
 
+    def _clearance_model(self):
+        """(probes, links, probes on the device, own geom mask): derived once -- the model on the host, its probes on the device"""
+        mir = self._mir
+        model = self.__dict__.get("_sphere_model")
+        if model is None or model[2].device != mir.device:
+            probes, lk = self.collision_spheres()
+            if len(lk) == 0:
+                raise ValueError("no collision sphere to test (an entity without moving links or without geoms on them)")
+            model = self._sphere_model = (probes, lk, torch.as_tensor(probes, device=mir.device), self._own_geoms())
+        return model
+
     def get_clearance(self, qpos=None, envs_idx=None, links=None, with_entity=None, max_distance: float = 1.0, return_detail: bool = False):
         """(R,): the lowest signed distance between this entity's sphere model (collision_spheres(), or what set_collision_spheres()
         put in its place) and every geom that does not belong to the entity itself -- with `with_entity`, only that entity's geoms --
@@ -569,19 +580,14 @@ class EntityView:
         the current state.  `links` (local link indices or LinkViews): only the spheres on those links.  return_detail=True: a dict
         with clearance (R,), sphere (R,) index into the model, link (R,) body index, geom (R,) (-1: nothing within max_distance), closest
         (R, 3) surface point and normal (R, 3) of the minimum.
-        Self-collision (the entity's spheres against its own geoms or each other) is out of scope, and so is what lies between two
-        configurations: a clear start and a clear goal say nothing about the path."""
+        Self-collision (the entity's spheres against its own geoms or each other) is out of scope.  What lies between two
+        configurations is get_path_clearance()'s question -- a clear start and a clear goal say nothing about the path -- and the way
+        from one to the other plan_path()'s."""
         mir = self._mir
         fn = getattr(mir, "signed_distance", None)
         if fn is None:
             raise NotImplementedError("this scene has no signed distance (MirScene.signed_distance / mir_signed_distance)")
-        model = self.__dict__.get("_sphere_model")   # (derived once: the model on the host, its probes on the device)
-        if model is None or model[2].device != mir.device:
-            probes, lk = self.collision_spheres()
-            if len(lk) == 0:
-                raise ValueError("no collision sphere to test (an entity without moving links or without geoms on them)")
-            model = self._sphere_model = (probes, lk, torch.as_tensor(probes, device=mir.device), self._own_geoms())
-        probes, lk, dev_probes, own = model
+        probes, lk, dev_probes, own = self._clearance_model()
         sel = None
         if links is not None:
             want = set(self._link_bodies(links))
@@ -609,6 +615,87 @@ class EntityView:
         """(R,) bool: get_clearance(...) < margin -- the sphere model touches or penetrates something (margin = 0), or comes nearer than
         `margin`.  Self-collision is out of scope (see get_clearance)."""
         return self.get_clearance(qpos=qpos, envs_idx=envs_idx, links=links, with_entity=with_entity, max_distance=max(1.0, 2.0 * float(margin))) < float(margin)
+
+    # ---- motion planning (MirScene.plan_path / path_clearance: mir_plan_path, mir_path_clearance).  The planner is this package's own
+    # (RRT-Connect on the GPU, one wave per env, deterministic in `seed`): parity with Genesis (OMPL) is unpinned.
+    def _plan_args(self, envs_idx, qpos_start, with_entity, ignore_entities, who):
+        mir = self._mir
+        if getattr(mir, "plan_path", None) is None:
+            raise NotImplementedError("this scene has no motion planning (MirScene.plan_path / mir_plan_path)")
+        if not self.dof_idx:
+            raise NotImplementedError(f"{who}: an entity without scalar joints")
+        _, lk, dev_probes, own = self._clearance_model()
+        skip = own
+        if with_entity is not None:
+            skip |= ((1 << len(self._b.geoms)) - 1) & ~with_entity._own_geoms()
+        for e in ignore_entities:
+            skip |= e._own_geoms()
+        idx = _env_index(mir, envs_idx)
+        R = mir.num_envs if idx is None else int(idx.numel())
+        kw = self._full_state_rows(idx, R, qpos=qpos_start, who=who)
+        return dict(probes=dev_probes, links=lk, dof_qadr=self._qcols, env_idx=idx, qpos_start=kw.get("qpos"), skip_geoms=skip), R
+
+    def plan_path(self, qpos_goal, qpos_start=None, timeout=None, smooth_path=True, num_waypoints=100, ignore_collision=False,
+                  planner="RRTConnect", envs_idx=None, return_valid_mask=False, resolution=0.05, step=0.3, margin=0.0, max_nodes=256,
+                  max_iterations=2000, seed=0, with_entity=None, ignore_entities=(), return_detail=False):
+        """``robot.plan_path(qpos_goal=q_goal, num_waypoints=100)`` -> (W, R, n): waypoints in this entity's own dof order (what
+        inverse_kinematics returns and control_dofs_position takes) from `qpos_start` ((R, n); None: the current state) to `qpos_goal`
+        (R, n), through configurations at which the entity's sphere model (collision_spheres()) keeps `margin` from every geom that
+        does not belong to the entity -- with `with_entity`, only that entity's geoms; the geoms of `ignore_entities` (a cube in the
+        fingers, the cube the hand reaches for) are left out too.  ONE launch for all rows (MirScene.plan_path / mir_plan_path, where
+        the algorithm is written down: RRT-Connect with `step`, edges checked every `resolution` rad / m per joint, at most `max_nodes`
+        per tree and `max_iterations` samples, 64 shortcut attempts when `smooth_path`, resampled at equal arc length).  Deterministic in
+        `seed`; a row's plan does not depend on the other rows.  A row without a plan holds its start W times (the arm stays put):
+        return_valid_mask=True -> (path, valid (R,) bool); return_detail=True -> a dict with path, valid, status (R,) int32
+        (spec.PLAN_STATUS), poly (R, 128, n) the polyline behind the waypoints, n_poly (R,) and stats (R, 4).  On an unbatched task
+        (num_envs = 0) every result comes without its env axis: path (W, n), valid a scalar.
+        `timeout` is accepted and ignored: the budget is `max_iterations`, which is deterministic.  Only planner="RRTConnect".
+        The planner is this package's own, not OMPL's: parity with Genesis is unpinned.  Self-collision is out of scope, the other
+        entities stay where they are, and only the sphere model stands for the entity."""
+        if planner != "RRTConnect":
+            raise NotImplementedError(f"planner {planner!r}: only 'RRTConnect' is implemented")
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "plan_path")
+        goal = self._entity_rows(qpos_goal, R, "qpos_goal")
+        r = self._mir.plan_path(qpos_goal=goal, num_waypoints=int(num_waypoints), max_nodes=int(max_nodes), max_iterations=int(max_iterations),
+                                smooth_passes=64 if smooth_path else 0, ignore_collision=bool(ignore_collision), seed=int(seed),
+                                resolution=float(resolution), step=float(step), margin=float(margin), max_distance=max(1.0, 2.0 * float(margin)), **args)
+        one = bool(self.__dict__.get("unbatched"))
+        path = r["path"].permute(1, 0, 2).contiguous()
+        valid = r["status"] == 0
+        detail = {"path": path, "valid": valid, "status": r["status"], "poly": r["poly"], "n_poly": r["n_poly"], "stats": r["stats"]}
+        if one:   # (an unbatched task: no env axis anywhere)
+            detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
+            path, valid = detail["path"], detail["valid"]
+        if return_detail:
+            return detail
+        return (path, valid) if return_valid_mask else path
+
+    def get_path_clearance(self, path, envs_idx=None, qpos_start=None, resolution=0.05, margin=0.0, with_entity=None, ignore_entities=(),
+                           max_distance: float = 1.0, return_detail: bool = False):
+        """(R,): the lowest clearance of this entity's sphere model along the trajectory `path` ((K, R, n) as plan_path returns it, K >= 2)
+        -- at every waypoint and at the configurations between two of them, at most `resolution` apart in every joint -- from ONE launch
+        (MirScene.path_clearance / mir_path_clearance).  The other dofs of the scene are those of `qpos_start` ((R, n) for this entity;
+        None: the current state).  return_detail=True: a dict with clearance (R,), seg_min (R, K-1) per segment and first_blocked (R,):
+        the first segment that comes nearer than `margin`, -1: none.  Self-collision is out of scope (see get_clearance)."""
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "get_path_clearance")
+        p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
+        if self.__dict__.get("unbatched") and p.dim() == 2:
+            p = p[:, None]
+        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != len(self._qcols) or p.shape[0] < 2:
+            raise ValueError(f"path must be (K >= 2, {R}, {len(self._qcols)}), got {tuple(p.shape)}")
+        r = self._mir.path_clearance(paths=p.permute(1, 0, 2).contiguous(), resolution=float(resolution), margin=float(margin),
+                                     max_distance=max(float(max_distance), 2.0 * float(margin)), **args)
+        out = {"clearance": r["row_min"], "seg_min": r["seg_min"], "first_blocked": r["row_first_blocked"]}
+        if self.__dict__.get("unbatched"):
+            out = {k: v[0] for k, v in out.items()}
+        return out if return_detail else out["clearance"]
+
+    def path_in_collision(self, path, margin: float = 0.0, envs_idx=None, qpos_start=None, resolution=0.05, with_entity=None,
+                          ignore_entities=()) -> torch.Tensor:
+        """(R,) bool: get_path_clearance(path, ...) < margin -- somewhere along the trajectory the sphere model touches or penetrates
+        something (margin = 0) or comes nearer than `margin`."""
+        return self.get_path_clearance(path, envs_idx=envs_idx, qpos_start=qpos_start, resolution=resolution, margin=margin, with_entity=with_entity,
+                                       ignore_entities=ignore_entities, max_distance=max(1.0, 2.0 * float(margin))) < float(margin)
 
     def get_link(self, name: str) -> LinkView:
         return LinkView(self._mir, self._b.body_index(name), name)

@@ -707,7 +707,8 @@ int mir_raycast(MirHandle h, const MirRayQuery* q, const float* dirs /* (N,3) de
  * MIR_E_INVALID: a NULL handle, query or probes; struct_size != sizeof(MirDistQuery); n_probes < 1; a max_distance that is not finite
  * or not > 0; an unknown flag bit; a skip_geoms bit at or above ngeom; a probe_link outside 0 .. nbody - 1; a call while a
  * mir_step_begin is open; a hull without volume.  MIR_E_CAPACITY: N > 1024; R x N beyond 2^31 - 1.  None of them launches anything.
- * Not covered: self-collision of the sphere model, swept volumes, robot geoms other than through spheres.
+ * Not covered: self-collision of the sphere model, robot geoms other than through spheres.  What lies BETWEEN two
+ * configurations is mir_path_clearance's question, and the way from one to the other mir_plan_path's (below).
  * (An added struct and entry point: MIR_VERSION and every other struct stay as they are.) */
 typedef struct MirDistQuery {
   int32_t  struct_size;   /* = sizeof(MirDistQuery) */
@@ -724,6 +725,100 @@ int mir_signed_distance(MirHandle h, const MirDistQuery* q,
                         const float* qpos /* (R,nq) device, nullable: evaluate at these configurations, not the current state */,
                         float* distance /* (R,N) */, int32_t* geom /* (R,N) */, float* closest /* (R,N,3) */, float* normal /* (R,N,3) */,
                         float* row_min /* (R) */, int32_t* row_argmin /* (R) */, void* stream);
+
+/* ---- motion planning: batched collision-checked paths between two configurations ------------------------
+ * `robot.plan_path(qpos_goal=q, num_waypoints=100)`: for R rows, ONE launch takes each row's arm from a start configuration to a goal
+ * configuration through configurations whose sphere model (probes and probe_link exactly as in mir_signed_distance) keeps `margin`
+ * from every geom that is not skipped.  mir_path_clearance answers the other question, "is this trajectory I already have clear?":
+ * the swept check that mir_signed_distance disclaims.  Both read the state (or the start rows given) and the compiled model and write
+ * only their outputs; rows, env_idx and clamping as in mir_signed_distance.  Parity with Genesis (OMPL) is unpinned: the planner is
+ * this library's own, fixed in every detail below so that a reference can mirror it.  Self-collision stays out of scope.
+ * Planned dofs.  dof_qadr (D), HOST: the qpos address of each planned dof, a revolute or prismatic joint with limits (an unlimited
+ *   one, an address that is no such joint, a joint named twice: MIR_E_INVALID).  A configuration is the D values in this order.
+ *   Every other entry of the row -- other joints, free bodies -- stays at qpos_start (R, nq), or at the current state when it is NULL.
+ *   Every geom that is tested must ride on a body with no planned dof on its path to the world (MIR_E_INVALID otherwise: a moving
+ *   obstacle is out of scope; put the arm's own geoms, and what it carries, into skip_geoms).
+ * clear(q): the planned dofs of the row set to q, forward kinematics, the lowest (signed distance - radius) over the probes, capped at
+ *   max_distance: clear when >= margin.  A configuration with a NaN or an infinity in it, one that puts a probe centre at such a
+ *   value, and every configuration of a row in which a tested geom's pose is not finite (a free body's qpos) have the clearance
+ *   -infinity: blocked, never "nothing near".
+ * edge(a, b): n_sub = max(1, ceil(max_j |b_j - a_j| / resolution)), at most 4096; the configurations a + (i / n_sub)(b - a),
+ *   i = 1 .. n_sub in order (the last one is b itself), the first blocked one ends the check.  Both quotients are float32 divisions
+ *   refined by one Newton step (within an ulp of the exact quotient, independent of the build's division flags).  A query whose
+ *   (hi_j - lo_j) / resolution exceeds 4096 for a planned dof is refused, so that inside the limits no edge reaches the cap.  Only the
+ *   goal is checked against the limits: a start (or a point of a mir_path_clearance trajectory) so far outside them that an edge
+ *   would need more than 4096 samples is sampled 4096 times, more coarsely than `resolution`, and nothing reports it.
+ * u(env, c, j) = (x >> 8) 2^-24, x = mix(mix(mix(seed ^ env) ^ c) ^ j), mix = the 32-bit finaliser of MurmurHash3; env is the ENV
+ *   index, not the row: a row's plan does not depend on the other rows of the call.
+ * Algorithm (RRT-Connect).  1. goal outside [lo, hi] in a planned dof: GOAL_OUT_OF_LIMITS.  2. start not clear: START_IN_COLLISION;
+ *   goal not clear: GOAL_IN_COLLISION.  3. edge(start, goal) holds: the polyline is [start, goal], iterations = 0.  4. Otherwise
+ *   Ta = {start}, Tb = {goal}; for it = 0 .. max_iterations - 1 (iterations = it + 1): the active tree is Ta on even it, Tb on odd;
+ *   q_rand_j = lo_j + u(env, it, j)(hi_j - lo_j); near = the node of the active tree nearest to q_rand (squared L2 over the planned
+ *   dofs, summed j ascending; the lower index on a tie); q_new = near + min(1, step / |q_rand - near|)(q_rand - near); if
+ *   edge(near, q_new) fails, next iteration; q_new joins the active tree.  Connect: c = the node of the other tree nearest to q_new;
+ *   repeat: d = |q_new - c|; the target is q_new itself when d <= step, else c + (step / d)(q_new - c); if edge(c, target) fails, stop;
+ *   the target joins the other tree with parent c and becomes c; when it was q_new the trees have met.  A node that has to join a tree
+ *   of max_nodes nodes: NODE_LIMIT.  After the last iteration: ITERATION_LIMIT.  5. The parents of both trees give the polyline, start
+ *   first, the meeting node once; more than MIR_PLAN_MAX_POLY nodes: PATH_TOO_LONG.  6. For s = 0 .. smooth_passes - 1, while the
+ *   polyline has n >= 3 nodes: i = min(floor(u(env, 0x80000000 | s, 0) (n - 2)), n - 3), j = i + 2 + min(floor(u(env, 0x80000000 | s, 1)
+ *   (n - 2 - i)), n - 3 - i) (float32 products); if edge(poly[i], poly[j]) holds the nodes between them are deleted.  7. Waypoint w of
+ *   W = num_waypoints: the start's bits for w = 0, the goal's for w = W - 1, else the point at arc length (w / (W - 1)) x total of the
+ *   polyline (L2 over the planned dofs), by linear interpolation inside its segment; a polyline of one segment is interpolated at
+ *   t = w / (W - 1) itself.
+ * Outputs.  path (R, W, D); status (R): MIR_PLAN_*; poly (R, MIR_PLAN_MAX_POLY, D), nullable: the polyline after smoothing, zeros behind
+ *   its n_poly (R, nullable) nodes; stats (R, 4), nullable: iterations, nodes of Ta, nodes of Tb, configurations checked.  A row that
+ *   fails returns its start W times (the arm stays put) and a polyline of one node.
+ *   MIR_PLAN_IGNORE_COLLISION: every clear() is true and nothing is evaluated: the straight line (limits are still checked).
+ * mir_path_clearance.  paths (R, K, D), K >= 2: seg_min (R, K-1) = the lowest clear() value over the samples of the edge rule on each
+ *   segment (the segment's first point counts for segment 0 only); row_min (R); row_first_blocked (R) = the first segment whose minimum
+ *   is < margin, or -1.  Every sample is evaluated, K is streamed.  It reads n_probes, n_dofs, resolution, margin, max_distance, flags
+ *   and skip_geoms of the query.  All three outputs NULL: MIR_OK without a launch.
+ * The trees live in LDS: sizeof of the fixed part + 2 max_nodes (4 D + 2) bytes must fit 64 KB, else MIR_E_CAPACITY, as N > 1024.
+ * MIR_E_INVALID: a NULL handle, query, probes, dof_qadr, goal, path or status; a struct_size that is not sizeof(MirPlanQuery); n_probes
+ * < 1; n_dofs outside 1 .. 16; num_waypoints < 2; max_nodes < 2; negative max_iterations or smooth_passes; resolution or step not
+ * finite or <= 0; margin < 0; max_distance <= margin; an unknown flag bit; a skip_geoms bit at or above ngeom; a probe_link outside
+ * 0 .. nbody - 1; a call while a mir_step_begin is open; a hull without volume; K < 2.  None of them launches anything.
+ * A call changes nothing a later call can see, as for mir_signed_distance.
+ * (Added structs and entry points: MIR_VERSION and every other struct stay as they are.) */
+#define MIR_PLAN_MAX_POLY 128
+#define MIR_PLAN_IGNORE_COLLISION 1u /* MirPlanQuery.flags */
+#define MIR_PLAN_OK 0
+#define MIR_PLAN_GOAL_OUT_OF_LIMITS 1
+#define MIR_PLAN_START_IN_COLLISION 2
+#define MIR_PLAN_GOAL_IN_COLLISION 3
+#define MIR_PLAN_NODE_LIMIT 4
+#define MIR_PLAN_ITERATION_LIMIT 5
+#define MIR_PLAN_PATH_TOO_LONG 6
+typedef struct MirPlanQuery {
+  int32_t  struct_size;     /* = sizeof(MirPlanQuery) */
+  int32_t  n_probes;        /* N, 1 .. 1024 */
+  int32_t  n_dofs;          /* D, 1 .. 16 */
+  int32_t  num_waypoints;   /* W >= 2 */
+  int32_t  max_nodes;       /* per tree, >= 2 */
+  int32_t  max_iterations;  /* >= 0 */
+  int32_t  smooth_passes;   /* >= 0 */
+  uint32_t flags;           /* MIR_PLAN_IGNORE_COLLISION; unknown bits are MIR_E_INVALID */
+  uint32_t seed;
+  float    resolution;      /* > 0: the largest joint step between two checked configurations */
+  float    step;            /* > 0: the L2 length of a tree extension */
+  float    margin;          /* >= 0 */
+  float    max_distance;    /* > margin: the cap of a clearance */
+  int32_t  _pad;
+  uint64_t skip_geoms;      /* bit g set: geom g is not tested */
+} MirPlanQuery;
+int mir_plan_query_sizeof(void);
+int mir_plan_path(MirHandle h, const MirPlanQuery* q,
+                  const float* probes /* (N,4) device */, const int32_t* probe_link /* (N) HOST, nullable */,
+                  const int32_t* dof_qadr /* (D) HOST: qpos address of each planned dof; revolute or prismatic only */,
+                  const int64_t* env_idx /* device, nullable */, int32_t n_rows,
+                  const float* qpos_start /* (R,nq) device, nullable = the current state */, const float* qpos_goal /* (R,D) */,
+                  float* path /* (R,W,D) */, int32_t* status /* (R) */, float* poly /* (R,MIR_PLAN_MAX_POLY,D) nullable */,
+                  int32_t* n_poly /* (R) nullable */, int32_t* stats /* (R,4) nullable */, void* stream);
+int mir_path_clearance(MirHandle h, const MirPlanQuery* q,
+                       const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+                       const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+                       const float* paths /* (R,K,D) */, int32_t K,
+                       float* seg_min /* (R,K-1) */, float* row_min /* (R) */, int32_t* row_first_blocked /* (R) */, void* stream);
 
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
