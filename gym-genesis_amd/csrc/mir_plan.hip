@@ -19,6 +19,13 @@
 //   input can keep a wave running: a configuration or a geom pose that is not finite counts as blocked, a nearest-node index is
 //   clamped to the tree.
 // Stores: plain dword stores by lanes 0 .. D-1 (or lane 0).  No atomics, no scratch, no cross-wave barrier.
+//
+// Self-collision (mir_plan_path_self, mir_path_clearance_self): both kernels are templates on SELF; the instantiation without it is the
+//   code of mir_plan_path / mir_path_clearance.  With it, clearance_at_poses() also stores every probe's world centre and radius to a
+//   sphere list in dynamic LDS (behind the trees), the E extra probes behind the first N included; self_clearance() walks it: lane =
+//   probe i in chunks of 64, a loop over j through the list (self_probe_min of mir_self_body.h: a chunk of the list per lane, sphere j
+//   to all lanes by v_readlane), the pair filter as one bit of link_mask[link_i], one wave reduction.  s(i, j) is symmetric, so chunk
+//   c of the i's meets the j's from chunk c on.  Bounded by N + E; the mask travels in the kernel arguments.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -37,6 +44,8 @@
 
 #include "mir_dist_body.h"
 
+#include "mir_self_body.h"
+
 namespace {
 
 constexpr int PLAN_MAX_DOF = 16;
@@ -49,9 +58,11 @@ struct PlanArgs {
   const float* qpos;    // the scene's state (rows of qst floats, addressed like the public layout)
   const float* qpos_o;  // (R, nq) public layout, nullable
   int qst, B, n_rows, N, nbody, nq, depth_max, D;
+  int NS;  // N + E: the probes of the self test (the first N are those of the scene test)
   int W, max_nodes, max_iter, smooth, ignore, K;
   uint32_t seed;
   float resolution, step, margin, max_distance;
+  float self_margin, self_max;
   unsigned long long skip;
   const float* probes;
   const long long* env_idx;
@@ -62,11 +73,13 @@ struct PlanArgs {
   float* poly;
   int32_t *n_poly, *stats;
   float *seg_min, *row_min;
+  float *seg_self_min, *row_self_min;
   int32_t* first_blocked;
   float lo[PLAN_MAX_DOF], hi[PLAN_MAX_DOF];
   int32_t qadr[PLAN_MAX_DOF];
   uint32_t body[MIR_MAX_BODY];    // parent | jtype << 8 | depth << 10 | (a planned dof on its path to the world) << 15
   uint8_t link[DIST_MAX_PROBES];  // all zero when every probe stands in the world
+  uint32_t link_mask[MIR_MAX_BODY];  // SELF: bit b of word a: the spheres on body a are tested against those on body b
 };
 static_assert(sizeof(PlanArgs) <= 4096, "kernel arguments");
 
@@ -109,11 +122,15 @@ __device__ __forceinline__ float wave_max(float v) {
 }
 
 // what a row carries through its launch (wave-uniform but for `lane`)
+enum { SELF_LIST = 0, SELF_IGNORED = 1, SELF_BLOCKED = 2 };  // what the last clearance() left for self_clearance()
+template <bool SELF>
 struct PlanRow {
   const PlanArgs& a;
   PlanLds& L;
   int lane, count, checked;
   bool bad;  // a geom record is not finite (a free body's pose in the row is not): every clearance is -INFINITY
+  float* sph;  // SELF: the sphere list, (centre, radius) x NS in dynamic LDS
+  int self_state;
 
   // forward kinematics, lane = body: every body (all) or the bodies below a planned dof; the arithmetic of mir_dist_kernel
   __device__ __forceinline__ void fk(bool all) {
@@ -158,16 +175,59 @@ struct PlanRow {
       const float dist = hit ? w.best : a.max_distance;
       nan |= __ballot(valid && (nonfinite(pw.x) || nonfinite(pw.y) || nonfinite(pw.z)));
       if (valid) mn = fminf(mn, dist);
+      if constexpr (SELF)
+        if (valid) {
+          st3(sph + 4 * probe, pw);
+          sph[4 * probe + 3] = radius;
+        }
+    }
+    if constexpr (SELF) {
+      unsigned long long nan_x = 0ull;
+      for (int base = a.N; base < a.NS; base += 64) {  // the extra probes: a centre for the list, no scene test
+        const bool valid = base + lane < a.NS;
+        const int probe = valid ? base + lane : a.NS - 1;
+        const float* const pr = a.probes + (size_t)probe * 4;
+        const int lk = a.link[probe];
+        const V3 pw = ld3(L.xp[lk]) + qrot(ld4(L.xq[lk]), ld3(pr));
+        nan_x |= __ballot(valid && (nonfinite(pw.x) || nonfinite(pw.y) || nonfinite(pw.z)));
+        if (valid) {
+          st3(sph + 4 * probe, pw);
+          sph[4 * probe + 3] = pr[3];
+        }
+      }
+      self_state = (nan | nan_x) != 0ull ? SELF_BLOCKED : SELF_LIST;
     }
     mn = wave_min(mn);
     return nan != 0ull || bad ? -INFINITY : mn;
   }
 
+  // the self clearance of the configuration the last clearance() evaluated: the lowest s(i, j) over the enabled pairs of the sphere
+  // list, capped at self_max; -INFINITY when a probe centre (or the configuration) is not finite
+  __device__ __forceinline__ float self_clearance() {
+    if (self_state == SELF_IGNORED) return a.self_max;
+    if (self_state == SELF_BLOCKED) return -INFINITY;
+    WSYNC();  // (the list is written)
+    float mn = a.self_max;
+    for (int base = 0; base < a.NS; base += 64) {
+      const bool valid = base + lane < a.NS;
+      const int i = valid ? base + lane : a.NS - 1;
+      const SelfBest w = self_probe_min<false>(sph, a.link, a.NS, base, i, valid ? a.link_mask[a.link[i]] : 0u, lane);
+      mn = fminf(mn, w.best);
+    }
+    mn = wave_min(mn);
+    WSYNC();  // (before the next configuration overwrites the list)
+    return mn;
+  }
+
   // clear(q): the clearance of configuration q (lane j: planned dof j)
   __device__ __forceinline__ float clearance(float q) {
-    if (a.ignore) return a.max_distance;
+    if (a.ignore) {
+      self_state = SELF_IGNORED;
+      return a.max_distance;
+    }
     if (__ballot(lane < a.D && nonfinite(q)) != 0ull) {  // (not a configuration: blocked, and kept out of the row)
       checked++;
+      self_state = SELF_BLOCKED;
       return -INFINITY;
     }
     if (lane < a.D) L.qrow[a.qadr[lane]] = q;
@@ -186,12 +246,20 @@ struct PlanRow {
     return i == n ? bv : av + div_refined((float)i, (float)n) * diff;  // (the last sample is b's bits)
   }
 
+  // clear(q): the scene test, then (SELF, and only when the scene test holds) the self test
+  __device__ __forceinline__ bool clear(float q) {
+    if (!(clearance(q) >= a.margin)) return false;
+    if constexpr (SELF)
+      if (!(self_clearance() >= a.self_margin)) return false;
+    return true;
+  }
+
   // edge(a, b): the samples i = 1 .. n_sub in order; the first blocked one ends the check
   __device__ __forceinline__ bool edge(float av, float bv) {
     const float diff = bv - av;
     const int n = n_sub(diff);
     for (int i = 1; i <= n; i++)
-      if (!(clearance(sample(av, bv, diff, i, n)) >= a.margin)) return false;
+      if (!clear(sample(av, bv, diff, i, n))) return false;
     return true;
   }
 
@@ -210,7 +278,8 @@ struct PlanRow {
 };
 
 // ---- row set-up shared by the two kernels: the start row, every body's pose, the geom records
-__device__ __forceinline__ void plan_setup(PlanRow& r, int row, int env) {
+template <class Row>
+__device__ __forceinline__ void plan_setup(Row& r, int row, int env) {
   const PlanArgs& a = r.a;
   const float* const src = a.qpos_o ? a.qpos_o + (size_t)row * a.nq : a.qpos + (size_t)env * a.qst;
   for (int i = r.lane; i < a.nq; i += 64) r.L.qrow[i] = src[i];
@@ -230,13 +299,14 @@ __device__ __forceinline__ int plan_env(const PlanArgs& a, int row) {
 
 extern __shared__ float plan_dyn[];
 
+template <bool SELF>
 __global__ __launch_bounds__(64) void mir_plan_kernel(PlanArgs a) {
   __shared__ PlanLds L;
   const int lane = threadIdx.x, row = blockIdx.x, D = a.D, MN = a.max_nodes;
   const int env = plan_env(a, row);
   float* const tree = plan_dyn;                                                        // [2][D][MN]
   uint16_t* const parent = reinterpret_cast<uint16_t*>(plan_dyn + (size_t)2 * D * MN);  // [2][MN]
-  PlanRow r{a, L, lane, 0, 0, false};
+  PlanRow<SELF> r{a, L, lane, 0, 0, false, plan_dyn + (size_t)(2 * D + 1) * MN, SELF_LIST};  // (2 MN 16-bit parents are MN floats)
   plan_setup(r, row, env);
   const bool isd = lane < D;
   const int dj = isd ? lane : 0;
@@ -281,7 +351,9 @@ __global__ __launch_bounds__(64) void mir_plan_kernel(PlanArgs a) {
   const bool outside = isd && !(gv >= lo && gv <= hi);
   if (__ballot(outside) != 0ull) status = MIR_PLAN_GOAL_OUT_OF_LIMITS;
   else if (!(r.clearance(sv) >= a.margin)) status = MIR_PLAN_START_IN_COLLISION;
+  else if (SELF && !(r.self_clearance() >= a.self_margin)) status = MIR_PLAN_START_IN_SELF_COLLISION;
   else if (!(r.clearance(gv) >= a.margin)) status = MIR_PLAN_GOAL_IN_COLLISION;
+  else if (SELF && !(r.self_clearance() >= a.self_margin)) status = MIR_PLAN_GOAL_IN_SELF_COLLISION;
   else if (r.edge(sv, gv)) {
     if (isd) { L.poly[0][lane] = sv; L.poly[1][lane] = gv; }
     npoly = 2;
@@ -408,37 +480,58 @@ __global__ __launch_bounds__(64) void mir_plan_kernel(PlanArgs a) {
 }
 
 // the swept check on its own: every sample of the edge rule on every segment of the caller's path, no early exit
+template <bool SELF>
 __global__ __launch_bounds__(64) void mir_path_clear_kernel(PlanArgs a) {
   __shared__ PlanLds L;
   const int lane = threadIdx.x, row = blockIdx.x, D = a.D;
-  PlanRow r{a, L, lane, 0, 0, false};
+  PlanRow<SELF> r{a, L, lane, 0, 0, false, plan_dyn, SELF_LIST};
   plan_setup(r, row, plan_env(a, row));
   const bool isd = lane < D;
   const float* const p = a.goal + (size_t)row * a.K * D;
-  float rmin = INFINITY;
+  float rmin = INFINITY, rself = INFINITY;
   int first = -1;
   float av = isd ? p[lane] : 0.0f;
   for (int k = 0; k + 1 < a.K; k++) {
     const float bv = isd ? p[(size_t)(k + 1) * D + lane] : 0.0f;
     float smin = k == 0 ? r.clearance(av) : INFINITY;  // (a segment's first point counts only for segment 0)
+    float sself = INFINITY;
+    if constexpr (SELF)
+      if (k == 0) sself = r.self_clearance();
     const float diff = bv - av;
     const int n = r.n_sub(diff);
-    for (int i = 1; i <= n; i++) smin = fminf(smin, r.clearance(PlanRow::sample(av, bv, diff, i, n)));
+    for (int i = 1; i <= n; i++) {
+      smin = fminf(smin, r.clearance(PlanRow<SELF>::sample(av, bv, diff, i, n)));
+      if constexpr (SELF) sself = fminf(sself, r.self_clearance());
+    }
     if (a.seg_min && lane == 0) a.seg_min[(size_t)row * (a.K - 1) + k] = smin;
     rmin = fminf(rmin, smin);
-    if (first < 0 && smin < a.margin) first = k;
+    bool blocked = smin < a.margin;
+    if constexpr (SELF) {
+      if (a.seg_self_min && lane == 0) a.seg_self_min[(size_t)row * (a.K - 1) + k] = sself;
+      rself = fminf(rself, sself);
+      blocked = blocked || sself < a.self_margin;
+    }
+    if (first < 0 && blocked) first = k;
     av = bv;
   }
   if (lane == 0) {
     if (a.row_min) a.row_min[row] = rmin;
+    if constexpr (SELF)
+      if (a.row_self_min) a.row_self_min[row] = rself;
     if (a.first_blocked) a.first_blocked[row] = first;
   }
 }
 
 // ---- host: what the two entry points share.  Fills `a` but for the outputs; every refusal launches nothing.
-int plan_front(MirHandle h, const MirPlanQuery* q, const char* who, bool planner, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
-               const int64_t* env_idx, int32_t n_rows, const float* qpos_start, PlanArgs& a, long long& R) {
+// `self`: the call is one of the two *_self entry points and `sq` is its MirSelfQuery (checked here); else sq is not read.
+int plan_front(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, const char* who, bool planner, const float* probes,
+               const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start, PlanArgs& a,
+               long long& R) {
   if (!h || !q || !probes || !dof_qadr) return query_error(MIR_E_INVALID, who, "null argument");
+  if (self) {
+    const int rc = self_query_check(h, sq, who);
+    if (rc != MIR_OK) return rc;
+  }
   if (q->struct_size != (int32_t)sizeof(MirPlanQuery)) return query_error(MIR_E_INVALID, who, "struct_size is not sizeof(MirPlanQuery)");
   if (q->n_probes < 1) return query_error(MIR_E_INVALID, who, "n_probes < 1");
   if (q->n_dofs < 1 || q->n_dofs > PLAN_MAX_DOF) return query_error(MIR_E_INVALID, who, "n_dofs outside 1 .. 16");
@@ -457,10 +550,11 @@ int plan_front(MirHandle h, const MirPlanQuery* q, const char* who, bool planner
   if (env_idx && n_rows < 0) return query_error(MIR_E_INVALID, who, "negative n_rows");
   R = env_idx ? n_rows : h->B;
   const int N = q->n_probes, D = q->n_dofs;
-  if (N > DIST_MAX_PROBES) return query_error(MIR_E_CAPACITY, who, "more than 1024 probes in one call");
+  const long long NS = (long long)N + (self ? sq->n_extra : 0);
+  if (NS > DIST_MAX_PROBES) return query_error(MIR_E_CAPACITY, who, "more than 1024 probes in one call");
   memset(&a, 0, sizeof a);
   if (probe_link)
-    for (int i = 0; i < N; i++) {
+    for (int i = 0; i < (int)NS; i++) {
       if (probe_link[i] < 0 || probe_link[i] >= h->nbody) return query_error(MIR_E_INVALID, who, "probe_link outside 0 .. nbody - 1");
       a.link[i] = (uint8_t)probe_link[i];
     }
@@ -501,8 +595,15 @@ int plan_front(MirHandle h, const MirPlanQuery* q, const char* who, bool planner
         return query_error(MIR_E_INVALID, who, "a geom that is not skipped rides on a planned joint (a moving obstacle is out of scope: skip it)");
     }
   if (planner) {
-    const size_t lds = sizeof(PlanLds) + (size_t)2 * (size_t)q->max_nodes * (4 * (size_t)D + 2);
-    if (q->max_nodes > 0xfffe || lds > 65536) return query_error(MIR_E_CAPACITY, who, "the two trees do not fit 64 KB of LDS (max_nodes x n_dofs)");
+    const size_t lds = sizeof(PlanLds) + (size_t)2 * (size_t)q->max_nodes * (4 * (size_t)D + 2) + (self ? 16 * (size_t)NS : 0);
+    if (q->max_nodes > 0xfffe || lds > 65536)
+      return query_error(MIR_E_CAPACITY, who, self ? "the two trees and the sphere list do not fit 64 KB of LDS (max_nodes x n_dofs, n_probes + n_extra)"
+                                                    : "the two trees do not fit 64 KB of LDS (max_nodes x n_dofs)");
+  }
+  a.NS = (int)NS;
+  if (self) {
+    a.self_margin = sq->self_margin; a.self_max = sq->max_distance;
+    memcpy(a.link_mask, sq->link_mask, sizeof a.link_mask);
   }
   a.qpos = h->qpos; a.qpos_o = qpos_start; a.qst = h->pt.qst; a.B = h->B; a.n_rows = (int)R; a.N = N; a.nbody = h->nbody; a.nq = h->nq;
   a.depth_max = depth_max; a.D = D;
@@ -525,34 +626,65 @@ int plan_launch(MirHandle h, const char* who, void (*kernel)(PlanArgs), PlanArgs
   return e == hipSuccess ? MIR_OK : mir_set_error(MIR_E_HIP, hipGetErrorString(e));
 }
 
+int plan_entry(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, const char* who, const float* probes, const int32_t* probe_link,
+               const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal, float* path,
+               int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
+  if (!qpos_goal || !path || !status) return query_error(MIR_E_INVALID, who, "null argument");
+  PlanArgs a;
+  long long R = 0;
+  const int rc = plan_front(h, q, self, sq, who, true, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
+  if (rc != MIR_OK || R == 0) return rc;
+  a.W = q->num_waypoints; a.max_nodes = q->max_nodes; a.max_iter = q->max_iterations; a.smooth = q->smooth_passes; a.seed = q->seed; a.step = q->step;
+  a.goal = qpos_goal; a.path = path; a.status = status; a.poly = poly; a.n_poly = n_poly; a.stats = stats;
+  const size_t trees = (size_t)2 * (size_t)a.max_nodes * (4 * (size_t)a.D + 2);
+  return self ? plan_launch(h, who, mir_plan_kernel<true>, a, R, trees + 16 * (size_t)a.NS, stream) : plan_launch(h, who, mir_plan_kernel<false>, a, R, trees, stream);
+}
+
+int path_clear_entry(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, const char* who, const float* probes,
+                     const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+                     const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min, float* row_self_min,
+                     int32_t* row_first_blocked, void* stream) {
+  if (!paths) return query_error(MIR_E_INVALID, who, "null argument");
+  if (K < 2) return query_error(MIR_E_INVALID, who, "K < 2");
+  PlanArgs a;
+  long long R = 0;
+  const int rc = plan_front(h, q, self, sq, who, false, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
+  if (rc != MIR_OK || R == 0 || (!seg_min && !seg_self_min && !row_min && !row_self_min && !row_first_blocked)) return rc;
+  a.K = K; a.goal = paths; a.seg_min = seg_min; a.row_min = row_min; a.first_blocked = row_first_blocked;
+  a.seg_self_min = seg_self_min; a.row_self_min = row_self_min;
+  return self ? plan_launch(h, who, mir_path_clear_kernel<true>, a, R, 16 * (size_t)a.NS, stream) : plan_launch(h, who, mir_path_clear_kernel<false>, a, R, 0, stream);
+}
+
 }  // namespace
 
 extern "C" int mir_plan_query_sizeof(void) { return (int)sizeof(MirPlanQuery); }
+extern "C" int mir_self_query_sizeof(void) { return (int)sizeof(MirSelfQuery); }
 
 extern "C" int mir_plan_path(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
                              const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal, float* path,
                              int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
-  static const char who[] = "mir_plan_path";
-  if (!qpos_goal || !path || !status) return query_error(MIR_E_INVALID, who, "null argument");
-  PlanArgs a;
-  long long R = 0;
-  const int rc = plan_front(h, q, who, true, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
-  if (rc != MIR_OK || R == 0) return rc;
-  a.W = q->num_waypoints; a.max_nodes = q->max_nodes; a.max_iter = q->max_iterations; a.smooth = q->smooth_passes; a.seed = q->seed; a.step = q->step;
-  a.goal = qpos_goal; a.path = path; a.status = status; a.poly = poly; a.n_poly = n_poly; a.stats = stats;
-  return plan_launch(h, who, mir_plan_kernel, a, R, (size_t)2 * (size_t)a.max_nodes * (4 * (size_t)a.D + 2), stream);
+  return plan_entry(h, q, false, nullptr, "mir_plan_path", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, qpos_goal, path, status, poly, n_poly,
+                    stats, stream);
+}
+
+extern "C" int mir_plan_path_self(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const float* probes, const int32_t* probe_link,
+                                  const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal,
+                                  float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
+  return plan_entry(h, q, true, sq, "mir_plan_path_self", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, qpos_goal, path, status, poly,
+                    n_poly, stats, stream);
 }
 
 extern "C" int mir_path_clearance(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
                                   const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* paths, int32_t K,
                                   float* seg_min, float* row_min, int32_t* row_first_blocked, void* stream) {
-  static const char who[] = "mir_path_clearance";
-  if (!paths) return query_error(MIR_E_INVALID, who, "null argument");
-  if (K < 2) return query_error(MIR_E_INVALID, who, "K < 2");
-  PlanArgs a;
-  long long R = 0;
-  const int rc = plan_front(h, q, who, false, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
-  if (rc != MIR_OK || R == 0 || (!seg_min && !row_min && !row_first_blocked)) return rc;
-  a.K = K; a.goal = paths; a.seg_min = seg_min; a.row_min = row_min; a.first_blocked = row_first_blocked;
-  return plan_launch(h, who, mir_path_clear_kernel, a, R, 0, stream);
+  return path_clear_entry(h, q, false, nullptr, "mir_path_clearance", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, paths, K, seg_min,
+                          nullptr, row_min, nullptr, row_first_blocked, stream);
+}
+
+extern "C" int mir_path_clearance_self(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const float* probes, const int32_t* probe_link,
+                                       const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+                                       const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min, float* row_self_min,
+                                       int32_t* row_first_blocked, void* stream) {
+  return path_clear_entry(h, q, true, sq, "mir_path_clearance_self", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, paths, K, seg_min,
+                          seg_self_min, row_min, row_self_min, row_first_blocked, stream);
 }

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirSceneSpec, MirTaskQuery, MirVisualSpec, make_acc_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_task_query  # noqa: F401
+from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_self_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -151,6 +151,13 @@ def load_library() -> C.CDLL:
     lib.mir_plan_path.restype = C.c_int
     lib.mir_path_clearance.argtypes = [vp, C.POINTER(MirPlanQuery), vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp]
     lib.mir_path_clearance.restype = C.c_int
+    lib.mir_self_query_sizeof.restype = C.c_int
+    lib.mir_self_distance.argtypes = [vp, C.POINTER(MirSelfQuery), i32, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.mir_self_distance.restype = C.c_int
+    lib.mir_plan_path_self.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_plan_path_self.restype = C.c_int
+    lib.mir_path_clearance_self.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.mir_path_clearance_self.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
@@ -171,6 +178,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirDistQuery (rebuild the library)")
     if lib.mir_plan_query_sizeof() != C.sizeof(MirPlanQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirPlanQuery (rebuild the library)")
+    if lib.mir_self_query_sizeof() != C.sizeof(MirSelfQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirSelfQuery (rebuild the library)")
     if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
     _lib = lib
@@ -934,6 +943,54 @@ class MirScene(StepHelpers):
             self.distance_launches = self.__dict__.get("distance_launches", 0) + 1
         return out
 
+    def self_distance(self, probes, links, link_mask, env_idx=None, qpos=None, max_distance: float = 1.0, n_extra: int = 0,
+                      other: bool = False, row_min: bool = False) -> dict:
+        """mir_self_distance: the sphere model `probes` (N + E, 4) / `links` (N + E,) (as in signed_distance(); the last `n_extra` are
+        the self-only spheres, which this call treats like the others) against ITSELF, for the envs `env_idx` (None: all), in ONE
+        launch.  `link_mask` (32,) words: bit b of word a = the spheres on body a are tested against those on body b (symmetric, zero
+        diagonal).  distance (R, N + E) = per sphere the lowest |ci - cj| - ri - rj over the spheres it is tested against, max_distance
+        when none is that near; other (R, N + E) int32 = that sphere, -1: none; row_min: adds row_min (R,) and row_pair (R, 2) int32,
+        the lowest distance of the row and its pair (i < j; (-1, -1): none).  `qpos` (R, nq) is evaluated instead of the rows' current
+        state.  Fresh device tensors on the current stream; the call changes nothing a later call can see."""
+        if not isinstance(probes, torch.Tensor):
+            probes = torch.as_tensor(np.ascontiguousarray(probes, dtype=np.float32))
+        p = probes.to(device=self.device, dtype=torch.float32).contiguous()
+        if p.dim() != 2 or p.shape[1] != 4 or p.shape[0] - int(n_extra) < 1:
+            raise ValueError(f"probes must be (N + n_extra, 4) with N >= 1, got {tuple(p.shape)} with n_extra = {n_extra}")
+        NS = int(p.shape[0])
+        lk = None
+        if links is not None:
+            lk = np.ascontiguousarray(links.cpu().numpy() if isinstance(links, torch.Tensor) else links, dtype=np.int32).reshape(-1)
+            if lk.shape[0] != NS:
+                raise ValueError(f"links must be ({NS},), got {lk.shape}")
+        sq = make_self_query(link_mask, n_extra, 0.0, max_distance)
+        idx = None
+        if env_idx is not None:
+            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        R = self.num_envs if idx is None else int(idx.numel())
+        if qpos is not None:
+            qpos = torch.as_tensor(qpos, device=self.device).to(torch.float32).contiguous()
+            if tuple(qpos.shape) != (R, self.nq):
+                raise ValueError(f"qpos must be ({R}, {self.nq}), got {tuple(qpos.shape)}")
+        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        out = {"distance": new(NS)}
+        if other:
+            out["other"] = new(NS, dtype=torch.int32)
+        if row_min:
+            out["row_min"], out["row_pair"] = new(), new(2, dtype=torch.int32)
+        self._check(self.lib.mir_self_distance(self.h, C.byref(sq), NS - int(n_extra), _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p),
+                                               _ptr(idx), R, _ptr(qpos), _ptr(out["distance"]), _ptr(out.get("other")), _ptr(out.get("row_min")),
+                                               _ptr(out.get("row_pair")), self._stream()))
+        if R > 0:
+            self.self_launches = self.__dict__.get("self_launches", 0) + 1
+        return out
+
+    @staticmethod
+    def _self_query(self_model, n_total):
+        """self_model = dict(link_mask (32,), n_extra, self_margin, max_distance) -> (MirSelfQuery, N: the probes of the scene test)"""
+        sq = make_self_query(self_model["link_mask"], self_model.get("n_extra", 0), self_model.get("self_margin", 0.0), self_model.get("max_distance", 1.0))
+        return sq, n_total - int(sq.n_extra)
+
     def _plan_front(self, probes, links, dof_qadr, env_idx, qpos_start):
         """the arguments mir_plan_path and mir_path_clearance share -> (probes on the device, links, dof addresses, row list, R, start rows)"""
         if not isinstance(probes, torch.Tensor):
@@ -959,51 +1016,67 @@ class MirScene(StepHelpers):
 
     def plan_path(self, probes, links, dof_qadr, qpos_goal, env_idx=None, qpos_start=None, num_waypoints: int = 100, max_nodes: int = 256,
                   max_iterations: int = 2000, smooth_passes: int = 64, ignore_collision: bool = False, seed: int = 0, resolution: float = 0.05,
-                  step: float = 0.3, margin: float = 0.0, max_distance: float = 1.0, skip_geoms=0) -> dict:
+                  step: float = 0.3, margin: float = 0.0, max_distance: float = 1.0, skip_geoms=0, self_model=None) -> dict:
         """mir_plan_path: for the envs `env_idx` (None: all), ONE launch plans a collision-checked path for the planned dofs `dof_qadr`
         (qpos addresses of D limited scalar joints) from `qpos_start` ((R, nq) full rows in the layout of get_state(); None: the current
         state) to `qpos_goal` (R, D): RRT-Connect, shortcut smoothing, resampling (include/mirigid.h has the algorithm).  `probes` (N, 4)
         / `links` (N,) are the sphere model as in signed_distance(); every geom not in `skip_geoms` is an obstacle and must not ride on a
         planned joint.  -> dict of fresh device tensors: path (R, W, D), status (R,) int32 (spec.PLAN_STATUS), poly (R, 128, D) the
         polyline behind the waypoints, n_poly (R,), stats (R, 4): iterations, nodes of the two trees, configurations checked.  A row
-        that fails holds its start W times.  The call changes nothing a later call can see."""
+        that fails holds its start W times.  The call changes nothing a later call can see.
+        `self_model` = dict(link_mask (32,) words, n_extra, self_margin, max_distance): mir_plan_path_self -- a configuration must
+        also keep `self_margin` between the spheres of the links the mask enables; the last `n_extra` probes take part in that test
+        only; statuses 7 and 8 (START / GOAL_IN_SELF_COLLISION)."""
         p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
         D = int(qa.shape[0])
+        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
         goal = torch.as_tensor(qpos_goal, device=self.device).to(torch.float32).contiguous()
         if tuple(goal.shape) != (R, D):
             raise ValueError(f"qpos_goal must be ({R}, {D}), got {tuple(goal.shape)}")
-        q = make_plan_query(p.shape[0], D, num_waypoints, max_nodes, max_iterations, smooth_passes, ignore_collision, seed, resolution, step,
+        q = make_plan_query(N, D, num_waypoints, max_nodes, max_iterations, smooth_passes, ignore_collision, seed, resolution, step,
                             margin, max_distance, skip_geoms)
         W = max(int(num_waypoints), 0)
         new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
         out = {"path": new(W, D), "status": new(dtype=torch.int32), "poly": new(PLAN_MAX_POLY, D), "n_poly": new(dtype=torch.int32),
                "stats": new(4, dtype=torch.int32)}
-        self._check(self.lib.mir_plan_path(self.h, C.byref(q), _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p),
-                                           qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(goal), _ptr(out["path"]),
-                                           _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]), _ptr(out["stats"]), self._stream()))
+        fn, head = (self.lib.mir_plan_path, (self.h, C.byref(q))) if sq is None else (self.lib.mir_plan_path_self, (self.h, C.byref(q), C.byref(sq)))
+        self._check(fn(*head, _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p), qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
+                       _ptr(qpos_start), _ptr(goal), _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]),
+                       _ptr(out["stats"]), self._stream()))
         if R > 0:
             self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
         return out
 
     def path_clearance(self, probes, links, dof_qadr, paths, env_idx=None, qpos_start=None, resolution: float = 0.05, margin: float = 0.0,
-                       max_distance: float = 1.0, skip_geoms=0) -> dict:
+                       max_distance: float = 1.0, skip_geoms=0, self_model=None) -> dict:
         """mir_path_clearance: the swept check of the trajectories `paths` (R, K, D) over the planned dofs `dof_qadr`, in ONE launch:
         every configuration the edge rule of mir_plan_path samples on every segment (at most `resolution` apart in every joint) is
         evaluated like signed_distance(row_min=True) on the sphere model.  -> seg_min (R, K-1), row_min (R,), row_first_blocked (R,)
-        int32: the first segment whose minimum is < margin, -1: none.  Everything else as plan_path()."""
+        int32: the first segment whose minimum is < margin, -1: none.  Everything else as plan_path().  With `self_model`
+        (mir_path_clearance_self): also seg_self_min (R, K-1) and row_self_min (R,), and row_first_blocked counts either test."""
         p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
         D = int(qa.shape[0])
+        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
         paths = torch.as_tensor(paths, device=self.device).to(torch.float32).contiguous()
         if paths.dim() != 3 or paths.shape[0] != R or paths.shape[2] != D or paths.shape[1] < 2:
             raise ValueError(f"paths must be ({R}, K >= 2, {D}), got {tuple(paths.shape)}")
         K = int(paths.shape[1])
-        q = make_plan_query(p.shape[0], D, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
+        q = make_plan_query(N, D, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
         out = {"seg_min": torch.empty((R, K - 1), dtype=torch.float32, device=self.device),
                "row_min": torch.empty((R,), dtype=torch.float32, device=self.device),
                "row_first_blocked": torch.empty((R,), dtype=torch.int32, device=self.device)}
-        self._check(self.lib.mir_path_clearance(self.h, C.byref(q), _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p),
-                                                qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(paths), K,
-                                                _ptr(out["seg_min"]), _ptr(out["row_min"]), _ptr(out["row_first_blocked"]), self._stream()))
+        lkp = None if lk is None else lk.ctypes.data_as(C.c_void_p)
+        if sq is None:
+            self._check(self.lib.mir_path_clearance(self.h, C.byref(q), _ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start),
+                                                    _ptr(paths), K, _ptr(out["seg_min"]), _ptr(out["row_min"]), _ptr(out["row_first_blocked"]),
+                                                    self._stream()))
+        else:
+            out["seg_self_min"] = torch.empty((R, K - 1), dtype=torch.float32, device=self.device)
+            out["row_self_min"] = torch.empty((R,), dtype=torch.float32, device=self.device)
+            self._check(self.lib.mir_path_clearance_self(self.h, C.byref(q), C.byref(sq), _ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
+                                                         _ptr(qpos_start), _ptr(paths), K, _ptr(out["seg_min"]), _ptr(out["seg_self_min"]),
+                                                         _ptr(out["row_min"]), _ptr(out["row_self_min"]), _ptr(out["row_first_blocked"]),
+                                                         self._stream()))
         if R > 0:
             self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
         return out

@@ -472,9 +472,10 @@ def make_dist_query(n_probes: int, max_distance: float = 1.0, skip_geoms=()) -> 
 PLAN_MAX_POLY = 128  # MIR_PLAN_MAX_POLY: nodes of the polyline mir_plan_path returns (include/mirigid.h)
 PLAN_MAX_DOF = 16
 PLAN_IGNORE_COLLISION = 1
-PLAN_STATUS = ("OK", "GOAL_OUT_OF_LIMITS", "START_IN_COLLISION", "GOAL_IN_COLLISION", "NODE_LIMIT", "ITERATION_LIMIT", "PATH_TOO_LONG")
+PLAN_STATUS = ("OK", "GOAL_OUT_OF_LIMITS", "START_IN_COLLISION", "GOAL_IN_COLLISION", "NODE_LIMIT", "ITERATION_LIMIT", "PATH_TOO_LONG",
+               "START_IN_SELF_COLLISION", "GOAL_IN_SELF_COLLISION")
 (PLAN_OK, PLAN_GOAL_OUT_OF_LIMITS, PLAN_START_IN_COLLISION, PLAN_GOAL_IN_COLLISION, PLAN_NODE_LIMIT, PLAN_ITERATION_LIMIT,
- PLAN_PATH_TOO_LONG) = range(7)
+ PLAN_PATH_TOO_LONG, PLAN_START_IN_SELF_COLLISION, PLAN_GOAL_IN_SELF_COLLISION) = range(9)
 
 
 class MirPlanQuery(C.Structure):
@@ -508,6 +509,31 @@ def make_plan_query(n_probes: int, n_dofs: int, num_waypoints: int = 100, max_no
     q.max_iterations, q.smooth_passes, q.flags, q.seed = int(max_iterations), int(smooth_passes), PLAN_IGNORE_COLLISION if ignore_collision else 0, int(seed) & 0xffffffff
     q.resolution, q.step, q.margin, q.max_distance = float(resolution), float(step), float(margin), float(max_distance)
     q.skip_geoms = _geom_mask(skip_geoms)
+    return q
+
+
+class MirSelfQuery(C.Structure):
+    """include/mirigid.h: MirSelfQuery (mir_self_distance, mir_plan_path_self, mir_path_clearance_self)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_extra", C.c_int32),
+        ("self_margin", C.c_float),
+        ("max_distance", C.c_float),
+        ("flags", C.c_uint32),
+        ("link_mask", C.c_uint32 * MIR_MAX_BODY),
+    ]
+
+
+def make_self_query(link_mask, n_extra: int = 0, self_margin: float = 0.0, max_distance: float = 1.0) -> MirSelfQuery:
+    """link_mask: (32,) words, bit b of word a = the spheres on body a are tested against those on body b (symmetric, zero diagonal);
+    None: nothing is tested."""
+    q = MirSelfQuery()
+    q.struct_size = C.sizeof(MirSelfQuery)
+    q.n_extra, q.self_margin, q.max_distance, q.flags = int(n_extra), float(self_margin), float(max_distance), 0
+    words = [0] * MIR_MAX_BODY if link_mask is None else [int(w) & 0xffffffff for w in link_mask]
+    if len(words) != MIR_MAX_BODY:
+        raise ValueError(f"link_mask must hold {MIR_MAX_BODY} words, got {len(words)}")
+    q.link_mask[:] = words
     return q
 
 

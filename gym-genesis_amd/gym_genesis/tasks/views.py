@@ -487,11 +487,12 @@ class EntityView:
             return custom[0].copy(), custom[1].copy()
         return self._derive_spheres(spacing)[:2]
 
-    def _derive_spheres(self, spacing=None):
-        """collision_spheres() from the geoms -> (probes, probe_link, the geom each sphere belongs to)"""
+    def _derive_spheres(self, spacing=None, on_links=None):
+        """collision_spheres() from the geoms -> (probes, probe_link, the geom each sphere belongs to); `on_links`: the bodies whose
+        geoms are taken instead of the covered links'"""
         from ..backend import spec as S
 
-        covered, probes, links, geoms = set(self._covered_links()), [], [], []
+        covered, probes, links, geoms = set(self._covered_links() if on_links is None else on_links), [], [], []
 
         def rot(q, v):
             w, u = q[0], np.asarray(q[1:], float)
@@ -552,6 +553,7 @@ class EntityView:
             raise ValueError("sphere centres must be finite and radii >= 0")
         self._spheres = (p, lk)
         self.__dict__.pop("_sphere_model", None)
+        self.__dict__.pop("_self_model", None)
 
     def _own_geoms(self) -> int:
         """bit mask of the geoms on this entity's links (the way sensors.Lidar computes skip_geoms)"""
@@ -580,7 +582,8 @@ class EntityView:
         the current state.  `links` (local link indices or LinkViews): only the spheres on those links.  return_detail=True: a dict
         with clearance (R,), sphere (R,) index into the model, link (R,) body index, geom (R,) (-1: nothing within max_distance), closest
         (R, 3) surface point and normal (R, 3) of the minimum.
-        Self-collision (the entity's spheres against its own geoms or each other) is out of scope.  What lies between two
+        The entity's spheres against each other are get_self_clearance()'s question; its spheres against its own geoms are not
+        tested.  What lies between two
         configurations is get_path_clearance()'s question -- a clear start and a clear goal say nothing about the path -- and the way
         from one to the other plan_path()'s."""
         mir = self._mir
@@ -613,18 +616,174 @@ class EntityView:
 
     def in_collision(self, qpos=None, envs_idx=None, margin: float = 0.0, links=None, with_entity=None) -> torch.Tensor:
         """(R,) bool: get_clearance(...) < margin -- the sphere model touches or penetrates something (margin = 0), or comes nearer than
-        `margin`.  Self-collision is out of scope (see get_clearance)."""
+        `margin`.  The scene only: in_self_collision() tests the sphere model against itself."""
         return self.get_clearance(qpos=qpos, envs_idx=envs_idx, links=links, with_entity=with_entity, max_distance=max(1.0, 2.0 * float(margin))) < float(margin)
+
+    # ---- self-collision (MirScene.self_distance / mir_self_distance): the sphere model against itself.  A pair of links is tested
+    # unless it is the same link, parent and child, or already overlapping at the neutral configuration (Genesis's
+    # enable_neutral_collision=False rule).  What stays out: link geoms other than through spheres, and a carried object against the
+    # arm (give the hand spheres for it with set_collision_spheres).
+    def _neutral_poses(self, neutral_qpos=None) -> dict:
+        """float64 forward kinematics of this entity's links at `neutral_qpos` ((n,) in the entity's dof order; None: zero clipped into
+        the joint limits) -> ({body: (position, quaternion)} relative to the root's parent, the rotation q, v -> q v q*)"""
+        dofs, first, nd = self._b.dofs, {}, {0: 0, 1: 1, 2: 1, 3: 6}
+        k = 0
+        for i, b in enumerate(self._b.bodies):
+            first[i] = k
+            k += nd[b["jtype"]] if i > 0 else 0
+        q = np.zeros(len(self.dof_idx)) if neutral_qpos is None else np.asarray(neutral_qpos, float).reshape(-1)
+        if q.shape[0] != len(self.dof_idx):
+            raise ValueError(f"neutral_qpos must be ({len(self.dof_idx)},), got {q.shape}")
+
+        def value(d):
+            v = q[self.dof_idx.index(d)] if d in self.dof_idx else 0.0
+            return float(np.clip(v, *dofs[d]["range"])) if neutral_qpos is None and dofs[d]["limited"] else float(v)
+
+        def qmul(a, b):
+            return np.array([a[0] * b[0] - a[1] * b[1] - a[2] * b[2] - a[3] * b[3], a[0] * b[1] + a[1] * b[0] + a[2] * b[3] - a[3] * b[2],
+                             a[0] * b[2] - a[1] * b[3] + a[2] * b[0] + a[3] * b[1], a[0] * b[3] + a[1] * b[2] - a[2] * b[1] + a[3] * b[0]])
+
+        def qrot(a, v):
+            t = 2.0 * np.cross(a[1:], v)
+            return v + a[0] * t + np.cross(a[1:], t)
+
+        poses = {}
+        for b in self.link_idx:   # (body order: a parent comes before its children)
+            body = self._b.bodies[b]
+            P, Q, ax = np.asarray(body["pos"], float), np.asarray(body["quat"], float), np.asarray(body["axis"], float)
+            if body["jtype"] == 1:
+                h = 0.5 * value(first[b])
+                Q = qmul(Q, np.append(np.cos(h), ax * np.sin(h)))
+            elif body["jtype"] == 2:
+                P = P + qrot(Q, value(first[b]) * ax)
+            if b != self.root and body["jtype"] != 3:
+                pp, pq = poses[body["parent"]]
+                P, Q = pp + qrot(pq, P), qmul(pq, Q)
+            poses[b] = (P, Q)
+        return poses, qrot
+
+    def self_collision_model(self, neutral_qpos=None, spacing=None):
+        """-> (probes (N + E, 4) float32, probe_link (N + E,) int32, n_extra = E, link_mask (32,) uint32): what the self test reads.
+        The first N spheres are collision_spheres() unchanged.  The E extra spheres are derived by the same rules (at `spacing`) from
+        the geoms of the entity's links that collision_spheres() leaves out -- a base bolted to the floor -- and take part in the self
+        test only: a base sphere sits in the floor by construction.  link_mask[a] bit b: the spheres on body a are tested against
+        those on body b; symmetric, zero diagonal.  Set for every pair of the entity's links that carry spheres except the same link,
+        parent and child, and every pair whose spheres overlap (lowest |ci - cj| - ri - rj < 0, float64) at `neutral_qpos` ((n,) in
+        this entity's dof order; None: the zero configuration clipped into the joint limits) -- Genesis's
+        enable_neutral_collision=False rule.  set_self_collision_pairs() edits the mask.  The model is derived once and kept; a call
+        with `neutral_qpos` or `spacing` derives it again, and set_collision_spheres() drops it."""
+        model = self.__dict__.get("_self_model")
+        if model is None or neutral_qpos is not None or spacing is not None:
+            probes, lk = self.collision_spheres()
+            rest = [b for b in self.link_idx if b not in set(self._covered_links())]
+            xp, xl, _ = self._derive_spheres(spacing, on_links=rest)
+            allp, alll = np.concatenate([probes, xp]).astype(np.float32), np.concatenate([lk, xl]).astype(np.int32)
+            poses, qrot = self._neutral_poses(neutral_qpos)
+            centre = np.stack([poses[int(b)][0] + qrot(poses[int(b)][1], c[:3].astype(float)) for c, b in zip(allp, alll)]) if len(alll) else np.zeros((0, 3))
+            radius = allp[:, 3].astype(float)
+            mask = np.zeros(32, np.uint32)
+            on = sorted(set(int(b) for b in alll))
+            for a in on:
+                for b in on:
+                    if a >= b or self._b.bodies[b]["parent"] == a or self._b.bodies[a]["parent"] == b:
+                        continue
+                    ia, ib = np.flatnonzero(alll == a), np.flatnonzero(alll == b)
+                    gap = np.linalg.norm(centre[ia][:, None] - centre[ib][None], axis=2) - radius[ia][:, None] - radius[ib][None]
+                    if gap.min() < 0.0:
+                        continue   # (already touching at the neutral configuration: the model's own coarseness, not a collision)
+                    mask[a] |= np.uint32(1 << b)
+                    mask[b] |= np.uint32(1 << a)
+            model = self._self_model = (allp, alll, int(len(xl)), mask)
+            self.__dict__.pop("_self_dev", None)
+        return model[0].copy(), model[1].copy(), model[2], model[3].copy()
+
+    def set_self_collision_pairs(self, pairs=None, disable=()) -> None:
+        """Edit the pair filter of the self test.  `pairs`: the link pairs that are tested, replacing the derived set (None: keep it);
+        `disable`: pairs taken out.  A link is a name, a LinkView of this entity or a local link index."""
+        self.self_collision_model()
+        probes, lk, n_extra, mask = self._self_model
+
+        def body(l):
+            return self._b.body_index(l) if isinstance(l, str) else self._link_body(l)
+
+        def put(m, a, b, on):
+            a, b = body(a), body(b)
+            if a == b or a not in self.link_idx or b not in self.link_idx:
+                raise ValueError("a self-collision pair names two different links of this entity")
+            for x, y in ((a, b), (b, a)):
+                m[x] = (int(m[x]) | (1 << y)) if on else (int(m[x]) & ~(1 << y))
+
+        mask = mask.copy()
+        if pairs is not None:
+            mask[:] = 0
+            for a, b in pairs:
+                put(mask, a, b, True)
+        for a, b in disable:
+            put(mask, a, b, False)
+        self._self_model = (probes, lk, n_extra, mask)
+
+    def self_collision_pairs(self) -> list:
+        """the link pairs the self test covers, as local link indices (a, b) with a < b: what set_self_collision_pairs(pairs=...) takes"""
+        mask, lk = self.self_collision_model()[3], self.link_idx
+        return [(i, j) for i in range(len(lk)) for j in range(i + 1, len(lk)) if (int(mask[lk[i]]) >> lk[j]) & 1]
+
+    def _self_args(self, self_margin=0.0, max_distance=1.0):
+        """the self model as MirScene takes it: (probes on the device, links, dict for self_model=)"""
+        if not (np.isfinite(self_margin) and self_margin >= 0.0):
+            raise ValueError(f"self_margin must be finite and >= 0, got {self_margin}")
+        self.self_collision_model()
+        probes, lk, n_extra, mask = self._self_model
+        if len(lk) - n_extra < 1:
+            raise ValueError("no collision sphere to test (an entity without moving links or without geoms on them)")
+        dev = self.__dict__.get("_self_dev")
+        if dev is None or dev.device != self._mir.device:
+            dev = self._self_dev = torch.as_tensor(probes, device=self._mir.device)
+        return dev, lk, dict(link_mask=mask, n_extra=n_extra, self_margin=float(self_margin), max_distance=max(float(max_distance), 2.0 * float(self_margin)))
+
+    def get_self_clearance(self, qpos=None, envs_idx=None, max_distance: float = 1.0, return_detail: bool = False):
+        """(R,): the lowest signed distance |ci - cj| - ri - rj between two spheres of this entity's self model
+        (self_collision_model()) that ride on a pair of links the filter enables, from ONE launch (MirScene.self_distance /
+        mir_self_distance); negative = the spheres overlap by that much, max_distance when no pair is that near.  `qpos` (R, n) in this
+        entity's own dof order: AT that configuration; None: at the current state.  return_detail=True: a dict with clearance (R,),
+        spheres (R, 2) indices into the self model (-1: none) and links (R, 2) their body indices (-1: none)."""
+        mir = self._mir
+        fn = getattr(mir, "self_distance", None)
+        if fn is None:
+            raise NotImplementedError("this scene has no self-collision queries (MirScene.self_distance / mir_self_distance)")
+        dev, lk, sm = self._self_args(0.0, max_distance)
+        idx = _env_index(mir, envs_idx)
+        R = mir.num_envs if idx is None else int(idx.numel())
+        kw = self._full_state_rows(idx, R, qpos=qpos, who="get_self_clearance")
+        r = fn(dev, links=lk, link_mask=sm["link_mask"], env_idx=idx, max_distance=float(max_distance), n_extra=sm["n_extra"], row_min=True, **kw)
+        if not return_detail:
+            return r["row_min"]
+        pair = r["row_pair"].long()
+        links = torch.as_tensor(lk, device=mir.device).long()[pair.clamp(min=0)]
+        return {"clearance": r["row_min"], "spheres": pair, "links": torch.where(pair >= 0, links, torch.full_like(links, -1))}
+
+    def in_self_collision(self, qpos=None, envs_idx=None, margin: float = 0.0) -> torch.Tensor:
+        """(R,) bool: get_self_clearance(...) < margin -- two spheres of the self model on an enabled pair of links touch or overlap
+        (margin = 0), or come nearer than `margin`."""
+        return self.get_self_clearance(qpos=qpos, envs_idx=envs_idx, max_distance=max(1.0, 2.0 * float(margin))) < float(margin)
+
+    def _self_on(self, self_collision) -> bool:
+        """self_collision=None follows the scene's enable_self_collision option"""
+        return bool(self._b.opt.get("enable_self_collision", 0)) if self_collision is None else bool(self_collision)
 
     # ---- motion planning (MirScene.plan_path / path_clearance: mir_plan_path, mir_path_clearance).  The planner is this package's own
     # (RRT-Connect on the GPU, one wave per env, deterministic in `seed`): parity with Genesis (OMPL) is unpinned.
-    def _plan_args(self, envs_idx, qpos_start, with_entity, ignore_entities, who):
+    def _plan_args(self, envs_idx, qpos_start, with_entity, ignore_entities, who, self_collision=None, self_margin=0.0):
         mir = self._mir
         if getattr(mir, "plan_path", None) is None:
             raise NotImplementedError("this scene has no motion planning (MirScene.plan_path / mir_plan_path)")
         if not self.dof_idx:
             raise NotImplementedError(f"{who}: an entity without scalar joints")
         _, lk, dev_probes, own = self._clearance_model()
+        extra = {}
+        if self._self_on(self_collision):
+            if getattr(mir, "self_distance", None) is None:
+                raise NotImplementedError("this scene has no self-collision queries (MirScene.self_distance / mir_self_distance)")
+            dev_probes, lk, extra["self_model"] = self._self_args(self_margin)
         skip = own
         if with_entity is not None:
             skip |= ((1 << len(self._b.geoms)) - 1) & ~with_entity._own_geoms()
@@ -633,11 +792,11 @@ class EntityView:
         idx = _env_index(mir, envs_idx)
         R = mir.num_envs if idx is None else int(idx.numel())
         kw = self._full_state_rows(idx, R, qpos=qpos_start, who=who)
-        return dict(probes=dev_probes, links=lk, dof_qadr=self._qcols, env_idx=idx, qpos_start=kw.get("qpos"), skip_geoms=skip), R
+        return dict(probes=dev_probes, links=lk, dof_qadr=self._qcols, env_idx=idx, qpos_start=kw.get("qpos"), skip_geoms=skip, **extra), R
 
     def plan_path(self, qpos_goal, qpos_start=None, timeout=None, smooth_path=True, num_waypoints=100, ignore_collision=False,
                   planner="RRTConnect", envs_idx=None, return_valid_mask=False, resolution=0.05, step=0.3, margin=0.0, max_nodes=256,
-                  max_iterations=2000, seed=0, with_entity=None, ignore_entities=(), return_detail=False):
+                  max_iterations=2000, seed=0, with_entity=None, ignore_entities=(), return_detail=False, self_collision=None, self_margin=0.0):
         """``robot.plan_path(qpos_goal=q_goal, num_waypoints=100)`` -> (W, R, n): waypoints in this entity's own dof order (what
         inverse_kinematics returns and control_dofs_position takes) from `qpos_start` ((R, n); None: the current state) to `qpos_goal`
         (R, n), through configurations at which the entity's sphere model (collision_spheres()) keeps `margin` from every geom that
@@ -650,11 +809,14 @@ class EntityView:
         (spec.PLAN_STATUS), poly (R, 128, n) the polyline behind the waypoints, n_poly (R,) and stats (R, 4).  On an unbatched task
         (num_envs = 0) every result comes without its env axis: path (W, n), valid a scalar.
         `timeout` is accepted and ignored: the budget is `max_iterations`, which is deterministic.  Only planner="RRTConnect".
-        The planner is this package's own, not OMPL's: parity with Genesis is unpinned.  Self-collision is out of scope, the other
-        entities stay where they are, and only the sphere model stands for the entity."""
+        `self_collision` (None: the scene's enable_self_collision option): a configuration must also keep `self_margin` between the
+        spheres of the self model (self_collision_model(): the sphere model plus the spheres of a bolted base, link pairs filtered by
+        the neutral rule); status 7 / 8 = the start / the goal is in self-collision (mir_plan_path_self).
+        The planner is this package's own, not OMPL's: parity with Genesis is unpinned.  The other entities stay where they are, only
+        the sphere model stands for the entity, and a carried object is not tested against the arm (give the hand spheres for it)."""
         if planner != "RRTConnect":
             raise NotImplementedError(f"planner {planner!r}: only 'RRTConnect' is implemented")
-        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "plan_path")
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "plan_path", self_collision, self_margin)
         goal = self._entity_rows(qpos_goal, R, "qpos_goal")
         r = self._mir.plan_path(qpos_goal=goal, num_waypoints=int(num_waypoints), max_nodes=int(max_nodes), max_iterations=int(max_iterations),
                                 smooth_passes=64 if smooth_path else 0, ignore_collision=bool(ignore_collision), seed=int(seed),
@@ -671,13 +833,16 @@ class EntityView:
         return (path, valid) if return_valid_mask else path
 
     def get_path_clearance(self, path, envs_idx=None, qpos_start=None, resolution=0.05, margin=0.0, with_entity=None, ignore_entities=(),
-                           max_distance: float = 1.0, return_detail: bool = False):
+                           max_distance: float = 1.0, return_detail: bool = False, self_collision=None, self_margin=0.0):
         """(R,): the lowest clearance of this entity's sphere model along the trajectory `path` ((K, R, n) as plan_path returns it, K >= 2)
         -- at every waypoint and at the configurations between two of them, at most `resolution` apart in every joint -- from ONE launch
         (MirScene.path_clearance / mir_path_clearance).  The other dofs of the scene are those of `qpos_start` ((R, n) for this entity;
         None: the current state).  return_detail=True: a dict with clearance (R,), seg_min (R, K-1) per segment and first_blocked (R,):
-        the first segment that comes nearer than `margin`, -1: none.  Self-collision is out of scope (see get_clearance)."""
-        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "get_path_clearance")
+        the first segment that comes nearer than `margin`, -1: none.
+        `self_collision` (None: the scene's enable_self_collision option) adds the self test of plan_path() on the same samples
+        (mir_path_clearance_self): the detail gains self_clearance (R,) and self_seg_min (R, K-1), first_blocked counts either test, and
+        without detail the result is min(clearance - margin, self_clearance - self_margin) + margin, so that "< margin" asks both."""
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "get_path_clearance", self_collision, self_margin)
         p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
         if self.__dict__.get("unbatched") and p.dim() == 2:
             p = p[:, None]
@@ -686,16 +851,21 @@ class EntityView:
         r = self._mir.path_clearance(paths=p.permute(1, 0, 2).contiguous(), resolution=float(resolution), margin=float(margin),
                                      max_distance=max(float(max_distance), 2.0 * float(margin)), **args)
         out = {"clearance": r["row_min"], "seg_min": r["seg_min"], "first_blocked": r["row_first_blocked"]}
+        if "self_model" in args:
+            out["self_clearance"], out["self_seg_min"] = r["row_self_min"], r["seg_self_min"]
         if self.__dict__.get("unbatched"):
             out = {k: v[0] for k, v in out.items()}
-        return out if return_detail else out["clearance"]
+        if return_detail or "self_model" not in args:
+            return out if return_detail else out["clearance"]
+        return torch.minimum(out["clearance"] - float(margin), out["self_clearance"] - float(self_margin)) + float(margin)
 
     def path_in_collision(self, path, margin: float = 0.0, envs_idx=None, qpos_start=None, resolution=0.05, with_entity=None,
-                          ignore_entities=()) -> torch.Tensor:
+                          ignore_entities=(), self_collision=None, self_margin=0.0) -> torch.Tensor:
         """(R,) bool: get_path_clearance(path, ...) < margin -- somewhere along the trajectory the sphere model touches or penetrates
-        something (margin = 0) or comes nearer than `margin`."""
+        something (margin = 0) or comes nearer than `margin`; with `self_collision`, or itself nearer than `self_margin`."""
         return self.get_path_clearance(path, envs_idx=envs_idx, qpos_start=qpos_start, resolution=resolution, margin=margin, with_entity=with_entity,
-                                       ignore_entities=ignore_entities, max_distance=max(1.0, 2.0 * float(margin))) < float(margin)
+                                       ignore_entities=ignore_entities, max_distance=max(1.0, 2.0 * float(margin)), self_collision=self_collision,
+                                       self_margin=self_margin) < float(margin)
 
     def get_link(self, name: str) -> LinkView:
         return LinkView(self._mir, self._b.body_index(name), name)

@@ -707,8 +707,9 @@ int mir_raycast(MirHandle h, const MirRayQuery* q, const float* dirs /* (N,3) de
  * MIR_E_INVALID: a NULL handle, query or probes; struct_size != sizeof(MirDistQuery); n_probes < 1; a max_distance that is not finite
  * or not > 0; an unknown flag bit; a skip_geoms bit at or above ngeom; a probe_link outside 0 .. nbody - 1; a call while a
  * mir_step_begin is open; a hull without volume.  MIR_E_CAPACITY: N > 1024; R x N beyond 2^31 - 1.  None of them launches anything.
- * Not covered: self-collision of the sphere model, robot geoms other than through spheres.  What lies BETWEEN two
- * configurations is mir_path_clearance's question, and the way from one to the other mir_plan_path's (below).
+ * Not covered: robot geoms other than through spheres.  The sphere model against ITSELF is mir_self_distance's question
+ * (below, "self-collision"); what lies BETWEEN two configurations is mir_path_clearance's, and the way from one to the other
+ * mir_plan_path's (below).
  * (An added struct and entry point: MIR_VERSION and every other struct stay as they are.) */
 typedef struct MirDistQuery {
   int32_t  struct_size;   /* = sizeof(MirDistQuery) */
@@ -732,7 +733,8 @@ int mir_signed_distance(MirHandle h, const MirDistQuery* q,
  * from every geom that is not skipped.  mir_path_clearance answers the other question, "is this trajectory I already have clear?":
  * the swept check that mir_signed_distance disclaims.  Both read the state (or the start rows given) and the compiled model and write
  * only their outputs; rows, env_idx and clamping as in mir_signed_distance.  Parity with Genesis (OMPL) is unpinned: the planner is
- * this library's own, fixed in every detail below so that a reference can mirror it.  Self-collision stays out of scope.
+ * this library's own, fixed in every detail below so that a reference can mirror it.  These two entry points test the sphere model
+ * against the scene only; mir_plan_path_self and mir_path_clearance_self (below, "self-collision") add the model against itself.
  * Planned dofs.  dof_qadr (D), HOST: the qpos address of each planned dof, a revolute or prismatic joint with limits (an unlimited
  *   one, an address that is no such joint, a joint named twice: MIR_E_INVALID).  A configuration is the D values in this order.
  *   Every other entry of the row -- other joints, free bodies -- stays at qpos_start (R, nq), or at the current state when it is NULL.
@@ -819,6 +821,73 @@ int mir_path_clearance(MirHandle h, const MirPlanQuery* q,
                        const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
                        const float* paths /* (R,K,D) */, int32_t K,
                        float* seg_min /* (R,K-1) */, float* row_min /* (R) */, int32_t* row_first_blocked /* (R) */, void* stream);
+
+/* ---- self-collision: the sphere model against itself ----------------------------------------------------
+ * Genesis plans with self-collision whenever the scene enables it.  Here the arm is its sphere model (mir_signed_distance), so the self
+ * test is sphere against sphere: mir_self_distance answers it at the state or at candidate configurations, and mir_plan_path_self /
+ * mir_path_clearance_self are mir_plan_path / mir_path_clearance with the self test added to clear(q).
+ * The model.  probes (N + E, 4) and probe_link (N + E), as in mir_signed_distance: the first N probes are the sphere model of the scene
+ *   test; the E = n_extra probes behind them take part in the self test ONLY (the spheres of a base bolted to the floor, which sit in
+ *   the floor by construction).  N + E <= 1024, else MIR_E_CAPACITY.
+ * The pair filter.  link_mask[a] bit b set: the spheres on body a are tested against the spheres on body b.  The mask must be symmetric
+ *   with a zero diagonal and name no body at or above nbody (MIR_E_INVALID otherwise).  An all-zero mask is legal: nothing is tested.
+ * s(i, j), float32: d = c_i - c_j per component (world centres, the forward kinematics of mir_signed_distance), n2 = fma(d_z, d_z,
+ *   fma(d_y, d_y, d_x d_x)), s = sqrt(n2) - (r_i + r_j), the root within an ulp (the hardware's v_sqrt_f32).  s(i, j) and s(j, i) are
+ *   the same bits.
+ * Per probe i: self_i = the lowest s(i, j) over j = 0 .. N + E - 1 with bit link[j] of link_mask[link[i]] set, j ascending, the lower j on
+ *   a tie (a strict < replaces the holder).
+ * mir_self_distance.  distance (R, N + E) = self_i and other (R, N + E) = its j when self_i <= max_distance; else max_distance and -1.
+ *   row_min (R) = the lowest distance of the row over the probes that have a partner, row_pair (R, 2) = (i, other_i) of the lowest i
+ *   that holds it: i < j, the lowest i, then the lowest j.  A row without a partner within max_distance: max_distance and (-1, -1).
+ *   A row in which a probe centre is not finite: every distance and row_min are -infinity (blocked, as in the planner), other and
+ *   row_pair are -1.  Poses (pose cache or qpos rows), rows, env_idx, clamping, "every output is nullable", "a call changes nothing a
+ *   later call can see" and MIR_E_CAPACITY (N + E > 1024; R x (N + E) beyond 2^31 - 1) are those of mir_signed_distance.  self_margin
+ *   is checked and otherwise not read.
+ * mir_plan_path_self / mir_path_clearance_self.  Every argument of mir_plan_path / mir_path_clearance keeps its meaning; q->n_probes is
+ *   N, and probes / probe_link hold N + sq->n_extra entries.  self(q) = min(min_i self_i, sq->max_distance) at the poses of clear(q),
+ *   -infinity where clear(q)'s value is -infinity for a configuration or a probe centre (any of the N + E) that is not finite.
+ *   clear(q) holds when the scene clearance (the first N probes, the arithmetic of mir_plan_path) is >= margin AND self(q) >=
+ *   self_margin; the planner evaluates self(q) only when the scene test holds.  Step 2 of the algorithm becomes: start's scene test
+ *   fails: START_IN_COLLISION; its self test fails: START_IN_SELF_COLLISION; then the goal's scene test: GOAL_IN_COLLISION; its self
+ *   test: GOAL_IN_SELF_COLLISION (for one configuration the scene test decides first).  Everything else of the algorithm is
+ *   unchanged, so with an all-zero mask and n_extra = 0 every output is that of mir_plan_path / mir_path_clearance bit for bit.
+ *   mir_path_clearance_self: seg_min / row_min are the scene values as before; seg_self_min (R, K-1) / row_self_min (R) the lowest
+ *   self(q) over the same samples; row_first_blocked = the first segment with seg_min < margin or seg_self_min < self_margin, or -1.
+ *   All five outputs NULL: MIR_OK without a launch.  MIR_PLAN_IGNORE_COLLISION switches both tests off (the values reported are
+ *   q->max_distance and sq->max_distance).
+ *   The sphere list lives in LDS behind the trees: the fixed part + 2 max_nodes (4 D + 2) + 16 (N + E) bytes must fit 64 KB, else
+ *   MIR_E_CAPACITY.
+ * MIR_E_INVALID, besides the refusals of the entry point each one extends: a NULL sq; struct_size != sizeof(MirSelfQuery); n_extra
+ * < 0; self_margin < 0 or not finite; max_distance <= self_margin or not finite; an unknown flag bit; a mask that is not symmetric,
+ * has a diagonal bit or a bit at or above nbody.  None of them launches anything.
+ * Not covered: link geoms other than through spheres; a carried object against the arm (give the hand spheres for it).
+ * (Added structs and entry points: MIR_VERSION, MirDistQuery, MirPlanQuery and the entry points above stay as they are.) */
+#define MIR_PLAN_START_IN_SELF_COLLISION 7
+#define MIR_PLAN_GOAL_IN_SELF_COLLISION 8
+typedef struct MirSelfQuery {
+  int32_t  struct_size;    /* = sizeof(MirSelfQuery) */
+  int32_t  n_extra;        /* E >= 0: probes behind the first N, self test only */
+  float    self_margin;    /* >= 0 */
+  float    max_distance;   /* > self_margin, finite: the cap of a self distance */
+  uint32_t flags;          /* 0; unknown bits are MIR_E_INVALID */
+  uint32_t link_mask[MIR_MAX_BODY]; /* bit b of word a: body a's spheres against body b's; symmetric, zero diagonal */
+} MirSelfQuery;
+int mir_self_query_sizeof(void);
+int mir_self_distance(MirHandle h, const MirSelfQuery* sq, int32_t n_probes /* N */,
+                      const float* probes /* (N+E,4) device */, const int32_t* probe_link /* (N+E) HOST, nullable */,
+                      const int64_t* env_idx /* device, nullable */, int32_t n_rows, const float* qpos /* (R,nq) device, nullable */,
+                      float* distance /* (R,N+E) */, int32_t* other /* (R,N+E) */, float* row_min /* (R) */,
+                      int32_t* row_pair /* (R,2) */, void* stream);
+int mir_plan_path_self(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq,
+                       const float* probes /* (N+E,4) device */, const int32_t* probe_link /* (N+E) HOST, nullable */,
+                       const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+                       const float* qpos_goal, float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream);
+int mir_path_clearance_self(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq,
+                            const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+                            const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+                            const float* paths /* (R,K,D) */, int32_t K,
+                            float* seg_min /* (R,K-1) */, float* seg_self_min /* (R,K-1) */, float* row_min /* (R) */,
+                            float* row_self_min /* (R) */, int32_t* row_first_blocked /* (R) */, void* stream);
 
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
