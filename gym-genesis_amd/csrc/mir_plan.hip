@@ -26,6 +26,13 @@
 //   probe i in chunks of 64, a loop over j through the list (self_probe_min of mir_self_body.h: a chunk of the list per lane, sphere j
 //   to all lanes by v_readlane), the pair filter as one bit of link_mask[link_i], one wave reduction.  s(i, j) is symmetric, so chunk
 //   c of the i's meets the j's from chunk c on.  Bounded by N + E; the mask travels in the kernel arguments.
+//
+// Carried object (mir_plan_path_carry, mir_path_clearance_carry): a further template parameter, CARRY; the four instantiations without
+//   it are the code of the four entry points above.  With it, plan_setup() takes the row's grasp transform (the carried body's pose in
+//   the attach link's frame: from the start row's forward kinematics, or the caller's row) into seven registers (the same value in every lane), and the
+//   partial fk() ends with one more step: lane 0 overwrites the carried body's pose in LDS by link o grasp.  The probes that ride on
+//   the carried body then follow the hand through clearance_at_poses() and self_clearance() unchanged.  A grasp that is not finite or
+//   has a zero quaternion sets `bad` (and blocks the self test): every clearance of the row is -INFINITY.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
@@ -80,6 +87,10 @@ struct PlanArgs {
   uint32_t body[MIR_MAX_BODY];    // parent | jtype << 8 | depth << 10 | (a planned dof on its path to the world) << 15
   uint8_t link[DIST_MAX_PROBES];  // all zero when every probe stands in the world
   uint32_t link_mask[MIR_MAX_BODY];  // SELF: bit b of word a: the spheres on body a are tested against those on body b
+  // CARRY: the carried body, the link it follows, the grasp rows (R, 7) (nullable: from the start row), the grasp each row used (nullable)
+  int carry_body, carry_link;
+  const float* grasp;
+  float* grasp_used;
 };
 static_assert(sizeof(PlanArgs) <= 4096, "kernel arguments");
 
@@ -123,14 +134,17 @@ __device__ __forceinline__ float wave_max(float v) {
 
 // what a row carries through its launch (wave-uniform but for `lane`)
 enum { SELF_LIST = 0, SELF_IGNORED = 1, SELF_BLOCKED = 2 };  // what the last clearance() left for self_clearance()
-template <bool SELF>
+template <bool SELF, bool CARRY>
 struct PlanRow {
+  static constexpr bool carry = CARRY;
   const PlanArgs& a;
   PlanLds& L;
   int lane, count, checked;
   bool bad;  // a geom record is not finite (a free body's pose in the row is not): every clearance is -INFINITY
   float* sph;  // SELF: the sphere list, (centre, radius) x NS in dynamic LDS
   int self_state;
+  V3 gp;  // CARRY: the grasp transform, the carried body in the attach link's frame (wave-uniform)
+  Q4 gq;
 
   // forward kinematics, lane = body: every body (all) or the bodies below a planned dof; the arithmetic of mir_dist_kernel
   __device__ __forceinline__ void fk(bool all) {
@@ -155,6 +169,16 @@ struct PlanRow {
       }
       WSYNC();
     }
+    if constexpr (CARRY)
+      if (!all) {  // the carried body follows its link: link o grasp (its qpos entry is never read again, never written)
+        if (lane == 0) {
+          const V3 lp = ld3(L.xp[a.carry_link]);
+          const Q4 lq = ld4(L.xq[a.carry_link]);
+          st3(L.xp[a.carry_body], lp + qrot(lq, gp));
+          st4(L.xq[a.carry_body], qmul(lq, gq));
+        }
+        WSYNC();
+      }
   }
 
   // the lowest (signed distance - radius) over the probes at the poses in LDS, max_distance when nothing is that near.  A probe centre
@@ -195,7 +219,7 @@ struct PlanRow {
           sph[4 * probe + 3] = pr[3];
         }
       }
-      self_state = (nan | nan_x) != 0ull ? SELF_BLOCKED : SELF_LIST;
+      self_state = (nan | nan_x) != 0ull || (CARRY && bad) ? SELF_BLOCKED : SELF_LIST;
     }
     mn = wave_min(mn);
     return nan != 0ull || bad ? -INFINITY : mn;
@@ -290,6 +314,33 @@ __device__ __forceinline__ void plan_setup(Row& r, int row, int env) {
   if (r.lane < r.count)
     for (int k = 5; k <= 16; k++) badrec = badrec || nonfinite(r.L.rec[r.lane * DIST_REC + k]);  // the geom's centre and axes
   r.bad = __ballot(badrec) != 0ull;
+  if constexpr (Row::carry) {  // the grasp transform of the row, the same value in every lane (seven vector registers: the scalar file is full)
+    V3 p;
+    Q4 q;
+    bool zero = false;
+    if (a.grasp) {
+      const float* const g = a.grasp + (size_t)row * 7;
+      const Q4 raw = ld4(g + 3);
+      p = ld3(g);
+      zero = raw.w * raw.w + raw.x * raw.x + raw.y * raw.y + raw.z * raw.z < 1e-30f;  // (what qnormalize turns into the identity)
+      q = qnormalize(raw);
+    } else {
+      const V3 lp = ld3(r.L.xp[a.carry_link]);
+      const Q4 lc = qconj(ld4(r.L.xq[a.carry_link]));
+      p = qrot(lc, ld3(r.L.xp[a.carry_body]) - lp);
+      q = qmul(lc, ld4(r.L.xq[a.carry_body]));
+    }
+    r.gp = p;
+    r.gq = q;
+    const bool nf = nonfinite(r.gp.x) || nonfinite(r.gp.y) || nonfinite(r.gp.z) || nonfinite(r.gq.w) || nonfinite(r.gq.x) || nonfinite(r.gq.y) ||
+                    nonfinite(r.gq.z);
+    r.bad = r.bad || __ballot(nf || zero) != 0ull;
+    if (a.grasp_used && r.lane == 0) {
+      float* const o = a.grasp_used + (size_t)row * 7;
+      st3(o, r.gp);
+      st4(o + 3, r.gq);
+    }
+  }
 }
 
 __device__ __forceinline__ int plan_env(const PlanArgs& a, int row) {
@@ -299,14 +350,14 @@ __device__ __forceinline__ int plan_env(const PlanArgs& a, int row) {
 
 extern __shared__ float plan_dyn[];
 
-template <bool SELF>
+template <bool SELF, bool CARRY>
 __global__ __launch_bounds__(64) void mir_plan_kernel(PlanArgs a) {
   __shared__ PlanLds L;
   const int lane = threadIdx.x, row = blockIdx.x, D = a.D, MN = a.max_nodes;
   const int env = plan_env(a, row);
   float* const tree = plan_dyn;                                                        // [2][D][MN]
   uint16_t* const parent = reinterpret_cast<uint16_t*>(plan_dyn + (size_t)2 * D * MN);  // [2][MN]
-  PlanRow<SELF> r{a, L, lane, 0, 0, false, plan_dyn + (size_t)(2 * D + 1) * MN, SELF_LIST};  // (2 MN 16-bit parents are MN floats)
+  PlanRow<SELF, CARRY> r{a, L, lane, 0, 0, false, plan_dyn + (size_t)(2 * D + 1) * MN, SELF_LIST};  // (2 MN 16-bit parents are MN floats)
   plan_setup(r, row, env);
   const bool isd = lane < D;
   const int dj = isd ? lane : 0;
@@ -480,11 +531,11 @@ __global__ __launch_bounds__(64) void mir_plan_kernel(PlanArgs a) {
 }
 
 // the swept check on its own: every sample of the edge rule on every segment of the caller's path, no early exit
-template <bool SELF>
+template <bool SELF, bool CARRY>
 __global__ __launch_bounds__(64) void mir_path_clear_kernel(PlanArgs a) {
   __shared__ PlanLds L;
   const int lane = threadIdx.x, row = blockIdx.x, D = a.D;
-  PlanRow<SELF> r{a, L, lane, 0, 0, false, plan_dyn, SELF_LIST};
+  PlanRow<SELF, CARRY> r{a, L, lane, 0, 0, false, plan_dyn, SELF_LIST};
   plan_setup(r, row, plan_env(a, row));
   const bool isd = lane < D;
   const float* const p = a.goal + (size_t)row * a.K * D;
@@ -500,7 +551,7 @@ __global__ __launch_bounds__(64) void mir_path_clear_kernel(PlanArgs a) {
     const float diff = bv - av;
     const int n = r.n_sub(diff);
     for (int i = 1; i <= n; i++) {
-      smin = fminf(smin, r.clearance(PlanRow<SELF>::sample(av, bv, diff, i, n)));
+      smin = fminf(smin, r.clearance(PlanRow<SELF, CARRY>::sample(av, bv, diff, i, n)));
       if constexpr (SELF) sself = fminf(sself, r.self_clearance());
     }
     if (a.seg_min && lane == 0) a.seg_min[(size_t)row * (a.K - 1) + k] = smin;
@@ -523,11 +574,13 @@ __global__ __launch_bounds__(64) void mir_path_clear_kernel(PlanArgs a) {
 }
 
 // ---- host: what the two entry points share.  Fills `a` but for the outputs; every refusal launches nothing.
-// `self`: the call is one of the two *_self entry points and `sq` is its MirSelfQuery (checked here); else sq is not read.
-int plan_front(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, const char* who, bool planner, const float* probes,
+// `self`: the call has a self test and `sq` is its MirSelfQuery (checked here); else sq is not read.  `carry`: the call is one of the two
+// *_carry entry points and `cq` is its MirCarryQuery (checked here, behind the refusals of the entry point it extends); else cq is not read.
+int plan_front(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, bool carry, const MirCarryQuery* cq, const char* who, bool planner,
+               const float* probes,
                const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start, PlanArgs& a,
                long long& R) {
-  if (!h || !q || !probes || !dof_qadr) return query_error(MIR_E_INVALID, who, "null argument");
+  if (!h || !q || !probes || !dof_qadr || (carry && !cq)) return query_error(MIR_E_INVALID, who, "null argument");
   if (self) {
     const int rc = self_query_check(h, sq, who);
     if (rc != MIR_OK) return rc;
@@ -594,6 +647,23 @@ int plan_front(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery
       if (!((q->skip_geoms >> g) & 1ull) && b >= 0 && b < h->nbody && moves[b])
         return query_error(MIR_E_INVALID, who, "a geom that is not skipped rides on a planned joint (a moving obstacle is out of scope: skip it)");
     }
+  if (carry) {
+    if (cq->struct_size != (int32_t)sizeof(MirCarryQuery)) return query_error(MIR_E_INVALID, who, "struct_size is not sizeof(MirCarryQuery)");
+    if (cq->flags) return query_error(MIR_E_INVALID, who, "unknown flag bit in MirCarryQuery");
+    const int cb = cq->body, cl = cq->link;
+    if (cb < 1 || cb >= h->nbody || mv.jtype(cb) != MIR_JNT_FREE) return query_error(MIR_E_INVALID, who, "the carried body is not a free-joint body");
+    for (int b = 1; b < h->nbody; b++)
+      if (mv.parent(b) == cb) return query_error(MIR_E_INVALID, who, "the carried body has a child body");
+    if (cl < 0 || cl >= h->nbody) return query_error(MIR_E_INVALID, who, "the attach link is outside 0 .. nbody - 1");
+    if (cl == cb) return query_error(MIR_E_INVALID, who, "the attach link is the carried body");
+    if (!a.ignore)
+      for (int g = 0; g < h->ngeom; g++) {
+        const int b = h->kernel == 16 ? h->hm.g_body[g] : h->hm64.g_body[g];
+        if (b == cb && !((q->skip_geoms >> g) & 1ull))
+          return query_error(MIR_E_INVALID, who, "a geom of the carried body is not skipped (it rides on the planned joints: skip it)");
+      }
+    a.carry_body = cb; a.carry_link = cl;
+  }
   if (planner) {
     const size_t lds = sizeof(PlanLds) + (size_t)2 * (size_t)q->max_nodes * (4 * (size_t)D + 2) + (self ? 16 * (size_t)NS : 0);
     if (q->max_nodes > 0xfffe || lds > 65536)
@@ -626,33 +696,41 @@ int plan_launch(MirHandle h, const char* who, void (*kernel)(PlanArgs), PlanArgs
   return e == hipSuccess ? MIR_OK : mir_set_error(MIR_E_HIP, hipGetErrorString(e));
 }
 
-int plan_entry(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, const char* who, const float* probes, const int32_t* probe_link,
-               const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal, float* path,
-               int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
+int plan_entry(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, bool carry, const MirCarryQuery* cq, const char* who,
+               const float* probes, const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+               const float* grasp, const float* qpos_goal, float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, float* grasp_used,
+               void* stream) {
   if (!qpos_goal || !path || !status) return query_error(MIR_E_INVALID, who, "null argument");
   PlanArgs a;
   long long R = 0;
-  const int rc = plan_front(h, q, self, sq, who, true, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
+  const int rc = plan_front(h, q, self, sq, carry, cq, who, true, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
   if (rc != MIR_OK || R == 0) return rc;
+  a.grasp = grasp; a.grasp_used = grasp_used;
   a.W = q->num_waypoints; a.max_nodes = q->max_nodes; a.max_iter = q->max_iterations; a.smooth = q->smooth_passes; a.seed = q->seed; a.step = q->step;
   a.goal = qpos_goal; a.path = path; a.status = status; a.poly = poly; a.n_poly = n_poly; a.stats = stats;
   const size_t trees = (size_t)2 * (size_t)a.max_nodes * (4 * (size_t)a.D + 2);
-  return self ? plan_launch(h, who, mir_plan_kernel<true>, a, R, trees + 16 * (size_t)a.NS, stream) : plan_launch(h, who, mir_plan_kernel<false>, a, R, trees, stream);
+  const size_t dyn = trees + (self ? 16 * (size_t)a.NS : 0);
+  if (carry) return plan_launch(h, who, self ? mir_plan_kernel<true, true> : mir_plan_kernel<false, true>, a, R, dyn, stream);
+  return plan_launch(h, who, self ? mir_plan_kernel<true, false> : mir_plan_kernel<false, false>, a, R, dyn, stream);
 }
 
-int path_clear_entry(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, const char* who, const float* probes,
-                     const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
-                     const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min, float* row_self_min,
-                     int32_t* row_first_blocked, void* stream) {
+int path_clear_entry(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, bool carry, const MirCarryQuery* cq, const char* who,
+                     const float* probes, const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows,
+                     const float* qpos_start, const float* grasp, const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min,
+                     float* row_self_min, int32_t* row_first_blocked, float* grasp_used, void* stream) {
   if (!paths) return query_error(MIR_E_INVALID, who, "null argument");
   if (K < 2) return query_error(MIR_E_INVALID, who, "K < 2");
+  if (!self && (seg_self_min || row_self_min)) return query_error(MIR_E_INVALID, who, "seg_self_min / row_self_min without a MirSelfQuery");
   PlanArgs a;
   long long R = 0;
-  const int rc = plan_front(h, q, self, sq, who, false, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
-  if (rc != MIR_OK || R == 0 || (!seg_min && !seg_self_min && !row_min && !row_self_min && !row_first_blocked)) return rc;
+  const int rc = plan_front(h, q, self, sq, carry, cq, who, false, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
+  if (rc != MIR_OK || R == 0 || (!seg_min && !seg_self_min && !row_min && !row_self_min && !row_first_blocked && !grasp_used)) return rc;
+  a.grasp = grasp; a.grasp_used = grasp_used;
   a.K = K; a.goal = paths; a.seg_min = seg_min; a.row_min = row_min; a.first_blocked = row_first_blocked;
   a.seg_self_min = seg_self_min; a.row_self_min = row_self_min;
-  return self ? plan_launch(h, who, mir_path_clear_kernel<true>, a, R, 16 * (size_t)a.NS, stream) : plan_launch(h, who, mir_path_clear_kernel<false>, a, R, 0, stream);
+  const size_t dyn = self ? 16 * (size_t)a.NS : 0;
+  if (carry) return plan_launch(h, who, self ? mir_path_clear_kernel<true, true> : mir_path_clear_kernel<false, true>, a, R, dyn, stream);
+  return plan_launch(h, who, self ? mir_path_clear_kernel<true, false> : mir_path_clear_kernel<false, false>, a, R, dyn, stream);
 }
 
 }  // namespace
@@ -663,28 +741,46 @@ extern "C" int mir_self_query_sizeof(void) { return (int)sizeof(MirSelfQuery); }
 extern "C" int mir_plan_path(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
                              const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal, float* path,
                              int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
-  return plan_entry(h, q, false, nullptr, "mir_plan_path", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, qpos_goal, path, status, poly, n_poly,
-                    stats, stream);
+  return plan_entry(h, q, false, nullptr, false, nullptr, "mir_plan_path", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr, qpos_goal, path,
+                    status, poly, n_poly, stats, nullptr, stream);
 }
 
 extern "C" int mir_plan_path_self(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const float* probes, const int32_t* probe_link,
                                   const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal,
                                   float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
-  return plan_entry(h, q, true, sq, "mir_plan_path_self", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, qpos_goal, path, status, poly,
-                    n_poly, stats, stream);
+  return plan_entry(h, q, true, sq, false, nullptr, "mir_plan_path_self", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr, qpos_goal, path,
+                    status, poly, n_poly, stats, nullptr, stream);
 }
 
 extern "C" int mir_path_clearance(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
                                   const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* paths, int32_t K,
                                   float* seg_min, float* row_min, int32_t* row_first_blocked, void* stream) {
-  return path_clear_entry(h, q, false, nullptr, "mir_path_clearance", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, paths, K, seg_min,
-                          nullptr, row_min, nullptr, row_first_blocked, stream);
+  return path_clear_entry(h, q, false, nullptr, false, nullptr, "mir_path_clearance", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr, paths,
+                          K, seg_min, nullptr, row_min, nullptr, row_first_blocked, nullptr, stream);
 }
 
 extern "C" int mir_path_clearance_self(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const float* probes, const int32_t* probe_link,
                                        const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
                                        const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min, float* row_self_min,
                                        int32_t* row_first_blocked, void* stream) {
-  return path_clear_entry(h, q, true, sq, "mir_path_clearance_self", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, paths, K, seg_min,
-                          seg_self_min, row_min, row_self_min, row_first_blocked, stream);
+  return path_clear_entry(h, q, true, sq, false, nullptr, "mir_path_clearance_self", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr, paths,
+                          K, seg_min, seg_self_min, row_min, row_self_min, row_first_blocked, nullptr, stream);
+}
+
+extern "C" int mir_carry_query_sizeof(void) { return (int)sizeof(MirCarryQuery); }
+
+extern "C" int mir_plan_path_carry(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const MirCarryQuery* cq, const float* probes,
+                                   const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+                                   const float* grasp, const float* qpos_goal, float* path, int32_t* status, float* poly, int32_t* n_poly,
+                                   int32_t* stats, float* grasp_used, void* stream) {
+  return plan_entry(h, q, sq != nullptr, sq, true, cq, "mir_plan_path_carry", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, grasp, qpos_goal,
+                    path, status, poly, n_poly, stats, grasp_used, stream);
+}
+
+extern "C" int mir_path_clearance_carry(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const MirCarryQuery* cq, const float* probes,
+                                        const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows,
+                                        const float* qpos_start, const float* grasp, const float* paths, int32_t K, float* seg_min, float* seg_self_min,
+                                        float* row_min, float* row_self_min, int32_t* row_first_blocked, float* grasp_used, void* stream) {
+  return path_clear_entry(h, q, sq != nullptr, sq, true, cq, "mir_path_clearance_carry", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, grasp,
+                          paths, K, seg_min, seg_self_min, row_min, row_self_min, row_first_blocked, grasp_used, stream);
 }

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_self_query, make_task_query  # noqa: F401
+from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirCarryQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_carry_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_self_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -157,6 +157,13 @@ def load_library() -> C.CDLL:
     lib.mir_plan_path_self.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_plan_path_self.restype = C.c_int
     lib.mir_path_clearance_self.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), vp, vp, vp, vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp]
+    lib.mir_carry_query_sizeof.restype = C.c_int
+    lib.mir_plan_path_carry.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
+                                        vp, vp, vp, vp, vp]
+    lib.mir_plan_path_carry.restype = C.c_int
+    lib.mir_path_clearance_carry.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp, vp, i32, vp, vp, vp,
+                                             i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_path_clearance_carry.restype = C.c_int
     lib.mir_path_clearance_self.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
@@ -180,6 +187,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirPlanQuery (rebuild the library)")
     if lib.mir_self_query_sizeof() != C.sizeof(MirSelfQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirSelfQuery (rebuild the library)")
+    if lib.mir_carry_query_sizeof() != C.sizeof(MirCarryQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCarryQuery (rebuild the library)")
     if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
     _lib = lib
@@ -1014,9 +1023,19 @@ class MirScene(StepHelpers):
                 raise ValueError(f"qpos_start must be ({R}, {self.nq}), got {tuple(qpos_start.shape)}")
         return p, lk, qa, idx, R, qpos_start
 
+    def _carry_query(self, carry, R):
+        """carry = dict(body, link, grasp=None) -> (MirCarryQuery, the grasp rows (R, 7) on the device or None, grasp_used (R, 7))"""
+        cq = make_carry_query(carry["body"], carry["link"])
+        grasp = carry.get("grasp")
+        if grasp is not None:
+            grasp = torch.as_tensor(grasp, device=self.device).to(torch.float32).contiguous()
+            if tuple(grasp.shape) != (R, 7):
+                raise ValueError(f"grasp must be ({R}, 7): position xyz and quaternion wxyz per row, got {tuple(grasp.shape)}")
+        return cq, grasp, torch.empty((R, 7), dtype=torch.float32, device=self.device)
+
     def plan_path(self, probes, links, dof_qadr, qpos_goal, env_idx=None, qpos_start=None, num_waypoints: int = 100, max_nodes: int = 256,
                   max_iterations: int = 2000, smooth_passes: int = 64, ignore_collision: bool = False, seed: int = 0, resolution: float = 0.05,
-                  step: float = 0.3, margin: float = 0.0, max_distance: float = 1.0, skip_geoms=0, self_model=None) -> dict:
+                  step: float = 0.3, margin: float = 0.0, max_distance: float = 1.0, skip_geoms=0, self_model=None, carry=None) -> dict:
         """mir_plan_path: for the envs `env_idx` (None: all), ONE launch plans a collision-checked path for the planned dofs `dof_qadr`
         (qpos addresses of D limited scalar joints) from `qpos_start` ((R, nq) full rows in the layout of get_state(); None: the current
         state) to `qpos_goal` (R, D): RRT-Connect, shortcut smoothing, resampling (include/mirigid.h has the algorithm).  `probes` (N, 4)
@@ -1026,7 +1045,11 @@ class MirScene(StepHelpers):
         that fails holds its start W times.  The call changes nothing a later call can see.
         `self_model` = dict(link_mask (32,) words, n_extra, self_margin, max_distance): mir_plan_path_self -- a configuration must
         also keep `self_margin` between the spheres of the links the mask enables; the last `n_extra` probes take part in that test
-        only; statuses 7 and 8 (START / GOAL_IN_SELF_COLLISION)."""
+        only; statuses 7 and 8 (START / GOAL_IN_SELF_COLLISION).
+        `carry` = dict(body, link, grasp=None): mir_plan_path_carry -- the free body `body` follows the body `link` by a rigid grasp
+        transform per row, `grasp` (R, 7) = its position xyz and quaternion wxyz in the link's frame (None: the kernel takes it from
+        the start row), and the probes whose link is `body` ride on it; the body's own geoms must be in `skip_geoms`.  With or
+        without `self_model`.  The result gains grasp (R, 7): the transform each row used."""
         p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
         D = int(qa.shape[0])
         sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
@@ -1039,21 +1062,30 @@ class MirScene(StepHelpers):
         new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
         out = {"path": new(W, D), "status": new(dtype=torch.int32), "poly": new(PLAN_MAX_POLY, D), "n_poly": new(dtype=torch.int32),
                "stats": new(4, dtype=torch.int32)}
-        fn, head = (self.lib.mir_plan_path, (self.h, C.byref(q))) if sq is None else (self.lib.mir_plan_path_self, (self.h, C.byref(q), C.byref(sq)))
-        self._check(fn(*head, _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p), qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
-                       _ptr(qpos_start), _ptr(goal), _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]),
-                       _ptr(out["stats"]), self._stream()))
+        lkp = None if lk is None else lk.ctypes.data_as(C.c_void_p)
+        if carry is not None:
+            cq, grasp, out["grasp"] = self._carry_query(carry, R)
+            self._check(self.lib.mir_plan_path_carry(self.h, C.byref(q), None if sq is None else C.byref(sq), C.byref(cq), _ptr(p), lkp,
+                                                     qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(grasp), _ptr(goal),
+                                                     _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]),
+                                                     _ptr(out["stats"]), _ptr(out["grasp"]), self._stream()))
+        else:
+            fn, head = (self.lib.mir_plan_path, (self.h, C.byref(q))) if sq is None else (self.lib.mir_plan_path_self, (self.h, C.byref(q), C.byref(sq)))
+            self._check(fn(*head, _ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
+                           _ptr(qpos_start), _ptr(goal), _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]),
+                           _ptr(out["stats"]), self._stream()))
         if R > 0:
             self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
         return out
 
     def path_clearance(self, probes, links, dof_qadr, paths, env_idx=None, qpos_start=None, resolution: float = 0.05, margin: float = 0.0,
-                       max_distance: float = 1.0, skip_geoms=0, self_model=None) -> dict:
+                       max_distance: float = 1.0, skip_geoms=0, self_model=None, carry=None) -> dict:
         """mir_path_clearance: the swept check of the trajectories `paths` (R, K, D) over the planned dofs `dof_qadr`, in ONE launch:
         every configuration the edge rule of mir_plan_path samples on every segment (at most `resolution` apart in every joint) is
         evaluated like signed_distance(row_min=True) on the sphere model.  -> seg_min (R, K-1), row_min (R,), row_first_blocked (R,)
         int32: the first segment whose minimum is < margin, -1: none.  Everything else as plan_path().  With `self_model`
-        (mir_path_clearance_self): also seg_self_min (R, K-1) and row_self_min (R,), and row_first_blocked counts either test."""
+        (mir_path_clearance_self): also seg_self_min (R, K-1) and row_self_min (R,), and row_first_blocked counts either test.  With
+        `carry` (as in plan_path(): mir_path_clearance_carry) the carried body's probes ride along, and the result gains grasp (R, 7)."""
         p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
         D = int(qa.shape[0])
         sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
@@ -1066,7 +1098,17 @@ class MirScene(StepHelpers):
                "row_min": torch.empty((R,), dtype=torch.float32, device=self.device),
                "row_first_blocked": torch.empty((R,), dtype=torch.int32, device=self.device)}
         lkp = None if lk is None else lk.ctypes.data_as(C.c_void_p)
-        if sq is None:
+        if carry is not None:
+            cq, grasp, out["grasp"] = self._carry_query(carry, R)
+            if sq is not None:
+                out["seg_self_min"] = torch.empty((R, K - 1), dtype=torch.float32, device=self.device)
+                out["row_self_min"] = torch.empty((R,), dtype=torch.float32, device=self.device)
+            self._check(self.lib.mir_path_clearance_carry(self.h, C.byref(q), None if sq is None else C.byref(sq), C.byref(cq), _ptr(p), lkp,
+                                                          qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(grasp), _ptr(paths), K,
+                                                          _ptr(out["seg_min"]), _ptr(out.get("seg_self_min")), _ptr(out["row_min"]),
+                                                          _ptr(out.get("row_self_min")), _ptr(out["row_first_blocked"]), _ptr(out["grasp"]),
+                                                          self._stream()))
+        elif sq is None:
             self._check(self.lib.mir_path_clearance(self.h, C.byref(q), _ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start),
                                                     _ptr(paths), K, _ptr(out["seg_min"]), _ptr(out["row_min"]), _ptr(out["row_first_blocked"]),
                                                     self._stream()))

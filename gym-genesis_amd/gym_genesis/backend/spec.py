@@ -537,6 +537,24 @@ def make_self_query(link_mask, n_extra: int = 0, self_margin: float = 0.0, max_d
     return q
 
 
+class MirCarryQuery(C.Structure):
+    """include/mirigid.h: MirCarryQuery (mir_plan_path_carry, mir_path_clearance_carry)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("body", C.c_int32),
+        ("link", C.c_int32),
+        ("flags", C.c_uint32),
+    ]
+
+
+def make_carry_query(body: int, link: int) -> MirCarryQuery:
+    """body: the carried free body C; link: the body it follows by the row's grasp transform (body indices of the scene)"""
+    q = MirCarryQuery()
+    q.struct_size = C.sizeof(MirCarryQuery)
+    q.body, q.link, q.flags = int(body), int(link), 0
+    return q
+
+
 IK_DEFAULTS = dict(max_iters=20, respect_joint_limit=1, damping=0.05, pos_tol=5e-4, rot_tol=5e-3, max_step=0.5)
 
 RENDER_PER_ENV, RENDER_GLOBAL = 0, 1

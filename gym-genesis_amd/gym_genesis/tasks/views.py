@@ -621,8 +621,8 @@ class EntityView:
 
     # ---- self-collision (MirScene.self_distance / mir_self_distance): the sphere model against itself.  A pair of links is tested
     # unless it is the same link, parent and child, or already overlapping at the neutral configuration (Genesis's
-    # enable_neutral_collision=False rule).  What stays out: link geoms other than through spheres, and a carried object against the
-    # arm (give the hand spheres for it with set_collision_spheres).
+    # enable_neutral_collision=False rule).  What stays out: link geoms other than through spheres.  A carried object against the arm
+    # is the attached_entity= argument of plan_path() / get_path_clearance() / get_carried_clearance().
     def _neutral_poses(self, neutral_qpos=None) -> dict:
         """float64 forward kinematics of this entity's links at `neutral_qpos` ((n,) in the entity's dof order; None: zero clipped into
         the joint limits) -> ({body: (position, quaternion)} relative to the root's parent, the rotation q, v -> q v q*)"""
@@ -772,7 +772,84 @@ class EntityView:
 
     # ---- motion planning (MirScene.plan_path / path_clearance: mir_plan_path, mir_path_clearance).  The planner is this package's own
     # (RRT-Connect on the GPU, one wave per env, deterministic in `seed`): parity with Genesis (OMPL) is unpinned.
-    def _plan_args(self, envs_idx, qpos_start, with_entity, ignore_entities, who, self_collision=None, self_margin=0.0):
+    def attached_links_default(self, ee_link_name) -> list:
+        """the links (body indices) a carried object attached to `ee_link_name` is tested against by default: every link of this
+        entity that carries spheres of the self model, except the attach link, its descendants (the fingers) and every link joined to
+        the attach link through fixed joints only"""
+        bodies, at = self._b.bodies, self._attach_body(ee_link_name)
+        out_of, grew = {at}, True
+        while grew:   # (links joined to the attach link through fixed joints only, up and down)
+            grew = False
+            for b in self.link_idx:
+                par = bodies[b]["parent"]
+                if bodies[b]["jtype"] == 0 and par in self.link_idx and (b in out_of) != (par in out_of):
+                    out_of.update((b, par))
+                    grew = True
+        below = {at}
+        for b in self.link_idx:   # (body order: a parent comes before its children)
+            if bodies[b]["parent"] in below:
+                below.add(b)
+        out_of |= below
+        lk = self.self_collision_model()[1]
+        return [b for b in sorted(set(int(x) for x in lk)) if b not in out_of]
+
+    def _attach_body(self, ee_link_name) -> int:
+        if ee_link_name is None:
+            raise ValueError("attached_entity needs ee_link_name: the link of this entity the object is attached to")
+        b = ee_link_name.idx if isinstance(ee_link_name, LinkView) else self._b.body_index(ee_link_name)
+        if b not in self.link_idx:
+            raise ValueError(f"ee_link_name {ee_link_name!r} is not a link of this entity")
+        return b
+
+    def carried_model(self, attached_entity, ee_link_name, attached_links=None, self_collision=None):
+        """-> (probes (N + E, 4) float32, probe_link (N + E,) int32, n_extra = E, link_mask (32,) uint32, C, Lk): what plan_path() hands
+        to mir_plan_path_carry for `attached_entity` on `ee_link_name`, composed on the host.  The object's spheres (its own
+        collision_spheres(), or what set_collision_spheres() put in their place; they ride on its body C) stand behind the arm's inside
+        the first N, the E self-only spheres of self_collision_model() behind them.  link_mask: the arm-against-arm filter when
+        `self_collision` is on (None: the scene's option), else zero, plus bit b of word C and bit C of word b for every link b of
+        `attached_links` (names, LinkViews or local link indices; None: attached_links_default(); []: none).  Lk: the attach link."""
+        if not isinstance(attached_entity, EntityView) or len(attached_entity.link_idx) != 1 or self._b.bodies[attached_entity.root]["jtype"] != 3:
+            raise ValueError("attached_entity must be an EntityView of one free body (a cube), not an articulated or a fixed entity")
+        C, at = attached_entity.root, self._attach_body(ee_link_name)
+        against = self.attached_links_default(ee_link_name) if attached_links is None else [
+            self._b.body_index(l) if isinstance(l, str) else self._link_body(l) for l in attached_links]
+        if any(b not in self.link_idx for b in against):
+            raise ValueError("attached_links names a link that does not belong to this entity")
+        cp, cl = attached_entity.collision_spheres()
+        if len(cl) == 0:
+            raise ValueError("attached_entity has no collision sphere")
+        self.self_collision_model()
+        probes, lk, n_extra, mask = self._self_model
+        N = len(lk) - n_extra
+        m = mask.copy() if self._self_on(self_collision) else np.zeros(32, np.uint32)
+        for b in against:
+            m[C] |= np.uint32(1 << b)
+            m[b] |= np.uint32(1 << C)
+        return (np.concatenate([probes[:N], cp, probes[N:]]).astype(np.float32), np.concatenate([lk[:N], cl, lk[N:]]).astype(np.int32), n_extra, m,
+                C, at)
+
+    def _carry_args(self, args, R, attached_entity, ee_link_name, grasp_pose, attached_links, self_collision, self_margin):
+        """the carried object composed into the arguments of MirScene.plan_path / path_clearance: carried_model() on the device (kept
+        until one of its inputs changes), the object's geoms skipped, carry=dict(body, link, grasp)"""
+        allp, alll, n_extra, m, C, at = self.carried_model(attached_entity, ee_link_name, attached_links, self_collision)
+        grasp = None
+        if grasp_pose is not None:
+            grasp = torch.as_tensor(grasp_pose, device=self._mir.device).to(torch.float32)
+            if grasp.dim() == 1 and grasp.shape[0] == 7:
+                grasp = grasp[None].expand(R, 7)
+            if tuple(grasp.shape) != (R, 7):
+                raise ValueError(f"grasp_pose must be ({R}, 7) or (7,): position xyz and quaternion wxyz in the link's frame, got {tuple(grasp.shape)}")
+            grasp = grasp.contiguous()
+        kept = self.__dict__.get("_carry_dev")
+        if kept is None or kept[1].device != self._mir.device or kept[0] != allp.tobytes():
+            kept = self._carry_dev = (allp.tobytes(), torch.as_tensor(allp, device=self._mir.device))
+        args.update(probes=kept[1], links=alll, carry=dict(body=C, link=at, grasp=grasp),
+                    self_model=dict(link_mask=m, n_extra=n_extra, self_margin=float(self_margin), max_distance=max(1.0, 2.0 * float(self_margin))))
+        args["skip_geoms"] |= attached_entity._own_geoms()
+        return args
+
+    def _plan_args(self, envs_idx, qpos_start, with_entity, ignore_entities, who, self_collision=None, self_margin=0.0, attached_entity=None,
+                   ee_link_name=None, grasp_pose=None, attached_links=None):
         mir = self._mir
         if getattr(mir, "plan_path", None) is None:
             raise NotImplementedError("this scene has no motion planning (MirScene.plan_path / mir_plan_path)")
@@ -792,11 +869,19 @@ class EntityView:
         idx = _env_index(mir, envs_idx)
         R = mir.num_envs if idx is None else int(idx.numel())
         kw = self._full_state_rows(idx, R, qpos=qpos_start, who=who)
-        return dict(probes=dev_probes, links=lk, dof_qadr=self._qcols, env_idx=idx, qpos_start=kw.get("qpos"), skip_geoms=skip, **extra), R
+        args = dict(probes=dev_probes, links=lk, dof_qadr=self._qcols, env_idx=idx, qpos_start=kw.get("qpos"), skip_geoms=skip, **extra)
+        if attached_entity is not None:
+            if not (np.isfinite(self_margin) and self_margin >= 0.0):
+                raise ValueError(f"self_margin must be finite and >= 0, got {self_margin}")
+            args = self._carry_args(args, R, attached_entity, ee_link_name, grasp_pose, attached_links, self_collision, self_margin)
+        elif ee_link_name is not None or grasp_pose is not None or attached_links is not None:
+            raise ValueError(f"{who}: ee_link_name, grasp_pose and attached_links belong to attached_entity, which is None")
+        return args, R
 
     def plan_path(self, qpos_goal, qpos_start=None, timeout=None, smooth_path=True, num_waypoints=100, ignore_collision=False,
                   planner="RRTConnect", envs_idx=None, return_valid_mask=False, resolution=0.05, step=0.3, margin=0.0, max_nodes=256,
-                  max_iterations=2000, seed=0, with_entity=None, ignore_entities=(), return_detail=False, self_collision=None, self_margin=0.0):
+                  max_iterations=2000, seed=0, with_entity=None, ignore_entities=(), return_detail=False, self_collision=None, self_margin=0.0,
+                  attached_entity=None, ee_link_name=None, grasp_pose=None, attached_links=None):
         """``robot.plan_path(qpos_goal=q_goal, num_waypoints=100)`` -> (W, R, n): waypoints in this entity's own dof order (what
         inverse_kinematics returns and control_dofs_position takes) from `qpos_start` ((R, n); None: the current state) to `qpos_goal`
         (R, n), through configurations at which the entity's sphere model (collision_spheres()) keeps `margin` from every geom that
@@ -812,11 +897,21 @@ class EntityView:
         `self_collision` (None: the scene's enable_self_collision option): a configuration must also keep `self_margin` between the
         spheres of the self model (self_collision_model(): the sphere model plus the spheres of a bolted base, link pairs filtered by
         the neutral rule); status 7 / 8 = the start / the goal is in self-collision (mir_plan_path_self).
-        The planner is this package's own, not OMPL's: parity with Genesis is unpinned.  The other entities stay where they are, only
-        the sphere model stands for the entity, and a carried object is not tested against the arm (give the hand spheres for it)."""
+        `attached_entity` (an EntityView of one free body, the cube in the fingers) with `ee_link_name` (the link of this entity it is
+        attached to): the object is planned for (mir_plan_path_carry).  Genesis calls the attached object `with_entity`; here
+        `with_entity` keeps its meaning above.  The object's spheres (its own collision_spheres(), or what set_collision_spheres() put
+        in their place) follow the link by a rigid grasp transform per row -- `grasp_pose` (R, 7) or (7,): the object's position xyz
+        and quaternion wxyz in the link's frame; None: taken on the device from where the object is at the start -- and are tested
+        against the scene like the arm's and, at `self_margin`, against the spheres of `attached_links` (names, LinkViews or local
+        link indices; None: attached_links_default(), every sphere-carrying link but the attach link, its descendants and what is
+        fixed to it; []: not against the arm), whether or not `self_collision` (arm against arm) is on.  The object's own geoms are
+        left out of the scene test.  return_detail gains grasp (R, 7): the transform each row used.
+        The planner is this package's own, not OMPL's: parity with Genesis is unpinned.  The other entities stay where they are, and
+        only the sphere model stands for the entity and for what it carries."""
         if planner != "RRTConnect":
             raise NotImplementedError(f"planner {planner!r}: only 'RRTConnect' is implemented")
-        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "plan_path", self_collision, self_margin)
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "plan_path", self_collision, self_margin, attached_entity,
+                                  ee_link_name, grasp_pose, attached_links)
         goal = self._entity_rows(qpos_goal, R, "qpos_goal")
         r = self._mir.plan_path(qpos_goal=goal, num_waypoints=int(num_waypoints), max_nodes=int(max_nodes), max_iterations=int(max_iterations),
                                 smooth_passes=64 if smooth_path else 0, ignore_collision=bool(ignore_collision), seed=int(seed),
@@ -825,6 +920,8 @@ class EntityView:
         path = r["path"].permute(1, 0, 2).contiguous()
         valid = r["status"] == 0
         detail = {"path": path, "valid": valid, "status": r["status"], "poly": r["poly"], "n_poly": r["n_poly"], "stats": r["stats"]}
+        if "grasp" in r:
+            detail["grasp"] = r["grasp"]
         if one:   # (an unbatched task: no env axis anywhere)
             detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
             path, valid = detail["path"], detail["valid"]
@@ -833,7 +930,8 @@ class EntityView:
         return (path, valid) if return_valid_mask else path
 
     def get_path_clearance(self, path, envs_idx=None, qpos_start=None, resolution=0.05, margin=0.0, with_entity=None, ignore_entities=(),
-                           max_distance: float = 1.0, return_detail: bool = False, self_collision=None, self_margin=0.0):
+                           max_distance: float = 1.0, return_detail: bool = False, self_collision=None, self_margin=0.0, attached_entity=None,
+                           ee_link_name=None, grasp_pose=None, attached_links=None):
         """(R,): the lowest clearance of this entity's sphere model along the trajectory `path` ((K, R, n) as plan_path returns it, K >= 2)
         -- at every waypoint and at the configurations between two of them, at most `resolution` apart in every joint -- from ONE launch
         (MirScene.path_clearance / mir_path_clearance).  The other dofs of the scene are those of `qpos_start` ((R, n) for this entity;
@@ -841,8 +939,12 @@ class EntityView:
         the first segment that comes nearer than `margin`, -1: none.
         `self_collision` (None: the scene's enable_self_collision option) adds the self test of plan_path() on the same samples
         (mir_path_clearance_self): the detail gains self_clearance (R,) and self_seg_min (R, K-1), first_blocked counts either test, and
-        without detail the result is min(clearance - margin, self_clearance - self_margin) + margin, so that "< margin" asks both."""
-        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "get_path_clearance", self_collision, self_margin)
+        without detail the result is min(clearance - margin, self_clearance - self_margin) + margin, so that "< margin" asks both.
+        `attached_entity`, `ee_link_name`, `grasp_pose`, `attached_links`: the carried object of plan_path() (Genesis names it
+        `with_entity`) on the same samples (mir_path_clearance_carry): its spheres count in clearance, and against the arm in
+        self_clearance, which is then reported whether or not `self_collision` is on; the detail gains grasp (R, 7)."""
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "get_path_clearance", self_collision, self_margin,
+                                  attached_entity, ee_link_name, grasp_pose, attached_links)
         p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
         if self.__dict__.get("unbatched") and p.dim() == 2:
             p = p[:, None]
@@ -853,6 +955,8 @@ class EntityView:
         out = {"clearance": r["row_min"], "seg_min": r["seg_min"], "first_blocked": r["row_first_blocked"]}
         if "self_model" in args:
             out["self_clearance"], out["self_seg_min"] = r["row_self_min"], r["seg_self_min"]
+        if "grasp" in r:
+            out["grasp"] = r["grasp"]
         if self.__dict__.get("unbatched"):
             out = {k: v[0] for k, v in out.items()}
         if return_detail or "self_model" not in args:
@@ -860,12 +964,32 @@ class EntityView:
         return torch.minimum(out["clearance"] - float(margin), out["self_clearance"] - float(self_margin)) + float(margin)
 
     def path_in_collision(self, path, margin: float = 0.0, envs_idx=None, qpos_start=None, resolution=0.05, with_entity=None,
-                          ignore_entities=(), self_collision=None, self_margin=0.0) -> torch.Tensor:
+                          ignore_entities=(), self_collision=None, self_margin=0.0, attached_entity=None, ee_link_name=None, grasp_pose=None,
+                          attached_links=None) -> torch.Tensor:
         """(R,) bool: get_path_clearance(path, ...) < margin -- somewhere along the trajectory the sphere model touches or penetrates
-        something (margin = 0) or comes nearer than `margin`; with `self_collision`, or itself nearer than `self_margin`."""
+        something (margin = 0) or comes nearer than `margin`; with `self_collision`, or itself nearer than `self_margin`; with
+        `attached_entity` (the carried object of plan_path(), which Genesis names `with_entity`), the object's spheres count in both."""
         return self.get_path_clearance(path, envs_idx=envs_idx, qpos_start=qpos_start, resolution=resolution, margin=margin, with_entity=with_entity,
                                        ignore_entities=ignore_entities, max_distance=max(1.0, 2.0 * float(margin)), self_collision=self_collision,
-                                       self_margin=self_margin) < float(margin)
+                                       self_margin=self_margin, attached_entity=attached_entity, ee_link_name=ee_link_name, grasp_pose=grasp_pose,
+                                       attached_links=attached_links) < float(margin)
+
+    def get_carried_clearance(self, qpos=None, attached_entity=None, ee_link_name=None, grasp_pose=None, attached_links=None, envs_idx=None,
+                              with_entity=None, ignore_entities=(), max_distance: float = 1.0, self_collision=None) -> dict:
+        """{clearance (R,), self_clearance (R,)} of ONE configuration with the carried object of plan_path() attached: `qpos` (R, n) in
+        this entity's dof order (None: the current state; the object's grasp is taken there too unless `grasp_pose` is given).
+        clearance: the arm's and the object's spheres against the scene; self_clearance: the object's spheres against the arm (and,
+        with `self_collision`, the arm against itself).  There is no point kernel for this: the two-point trajectory [q, q] goes
+        through mir_path_clearance_carry, which evaluates the configuration twice."""
+        if attached_entity is None:
+            raise ValueError("get_carried_clearance needs attached_entity (and ee_link_name)")
+        args, R = self._plan_args(envs_idx, qpos, with_entity, ignore_entities, "get_carried_clearance", self_collision, 0.0, attached_entity,
+                                  ee_link_name, grasp_pose, attached_links)
+        args["self_model"]["max_distance"] = float(max_distance)
+        q = self.get_dofs_position(envs_idx=envs_idx) if qpos is None else self._entity_rows(qpos, R, "qpos")
+        r = self._mir.path_clearance(paths=torch.stack([q, q], 1).contiguous(), max_distance=float(max_distance), **args)
+        out = {"clearance": r["row_min"], "self_clearance": r["row_self_min"]}
+        return {k: v[0] for k, v in out.items()} if self.__dict__.get("unbatched") else out
 
     def get_link(self, name: str) -> LinkView:
         return LinkView(self._mir, self._b.body_index(name), name)

@@ -860,7 +860,8 @@ int mir_path_clearance(MirHandle h, const MirPlanQuery* q,
  * MIR_E_INVALID, besides the refusals of the entry point each one extends: a NULL sq; struct_size != sizeof(MirSelfQuery); n_extra
  * < 0; self_margin < 0 or not finite; max_distance <= self_margin or not finite; an unknown flag bit; a mask that is not symmetric,
  * has a diagonal bit or a bit at or above nbody.  None of them launches anything.
- * Not covered: link geoms other than through spheres; a carried object against the arm (give the hand spheres for it).
+ * Not covered: link geoms other than through spheres.  A carried object against the scene and against the arm is the question of
+ * mir_plan_path_carry / mir_path_clearance_carry (below, "carried object").
  * (Added structs and entry points: MIR_VERSION, MirDistQuery, MirPlanQuery and the entry points above stay as they are.) */
 #define MIR_PLAN_START_IN_SELF_COLLISION 7
 #define MIR_PLAN_GOAL_IN_SELF_COLLISION 8
@@ -888,6 +889,58 @@ int mir_path_clearance_self(MirHandle h, const MirPlanQuery* q, const MirSelfQue
                             const float* paths /* (R,K,D) */, int32_t K,
                             float* seg_min /* (R,K-1) */, float* seg_self_min /* (R,K-1) */, float* row_min /* (R) */,
                             float* row_self_min /* (R) */, int32_t* row_first_blocked /* (R) */, void* stream);
+
+/* ---- carried object: planning and checking with a grasped body attached to the arm -----------------------
+ * Genesis's plan_path takes an attached object (`ee_link_name` names the link, `with_entity` the object).  Here the object is a free
+ * body of the scene whose pose follows a link of the arm by a rigid transform that is set per row, and whose spheres are probes like
+ * the arm's own: mir_plan_path_carry / mir_path_clearance_carry are mir_plan_path(_self) / mir_path_clearance(_self) with one more
+ * step in clear(q).  sq is nullable: without it there is no self test, and the call extends mir_plan_path / mir_path_clearance.
+ * The attachment.  C = cq->body, a free-joint body without child bodies; Lk = cq->link, any body 0 .. nbody - 1 but C; the grasp
+ *   transform G = (p_G, q_G), the pose of C in Lk's frame, one per row, fixed for the call.
+ * G, once per row at row set-up.  grasp NULL: from the start row (qpos_start, or the state) after the full forward kinematics,
+ *   p_G = qrot(conj(q_L), p_C - p_L), q_G = qmul(conj(q_L), q_C), with (p_L, q_L) and (p_C, q_C) the world poses of Lk and C, q_C the
+ *   free-joint quaternion as the forward kinematics normalises it (float32, the qrot and qmul of that forward kinematics).  Otherwise
+ *   row k of grasp (R, 7), device: p_G = its xyz, q_G = its wxyz normalised by the routine used for free-joint quaternions (n2 = the
+ *   sum of the four squares, times 1 / sqrt(n2) within an ulp).  A row whose G is not finite after this (a NaN or an infinity in the
+ *   grasp row or in the poses it is taken from, squares that overflow), or whose grasp quaternion has n2 < 1e-30 (zero: the free-joint
+ *   routine would make it the identity), is blocked: every clearance of the row, scene and self, is -infinity, as for a geom pose that
+ *   is not finite, and the planner reports START_IN_COLLISION.  grasp_used (R, 7), nullable: the G each row used, xyz then wxyz (the
+ *   identity quaternion for a zero one).  G is computed by the kernel: no host read-back.
+ * clear(q).  After the forward kinematics of the bodies below a planned dof, C's pose is overwritten: p_C = p_L + qrot(q_L, p_G),
+ *   q_C = qmul(q_L, q_G).  Nothing else of clear(q) changes: probes whose probe_link is C ride on that pose; the scene test sees those
+ *   among the first N like any probe; with sq they are in the sphere list, and link_mask[C] says which links they are tested against
+ *   (symmetric, as for every body).  C's entry in the qpos row is never written, and C's own geoms must be in skip_geoms: C counts as
+ *   riding on the planned joints.  Statuses are unchanged: a carried sphere in a geom at the start is START_IN_COLLISION, a carried
+ *   sphere in the arm START_IN_SELF_COLLISION.  A call in which no probe rides on C returns, bit for bit, what the entry point it
+ *   extends returns.
+ * mir_path_clearance_carry: the outputs of mir_path_clearance_self plus grasp_used; seg_self_min and row_self_min must be NULL when sq
+ *   is NULL (MIR_E_INVALID).  All six outputs NULL: MIR_OK without a launch.
+ * MIR_E_INVALID, besides the refusals of the entry point each one extends: a NULL cq; struct_size != sizeof(MirCarryQuery); an unknown
+ * flag bit; C not a free-joint body (outside 1 .. nbody - 1 included) or with a child body; Lk outside 0 .. nbody - 1 or Lk == C; a geom
+ * of C that is not in skip_geoms (unless MIR_PLAN_IGNORE_COLLISION).  None of them launches anything.
+ * Not covered: mir_signed_distance and mir_self_distance with a carried body (send the two-point trajectory [q, q] through
+ * mir_path_clearance_carry); a carried body with geoms that are tested as themselves.
+ * (Added struct and entry points: MIR_VERSION and every other struct and entry point stay as they are.) */
+typedef struct MirCarryQuery {
+  int32_t  struct_size;  /* = sizeof(MirCarryQuery) */
+  int32_t  body;         /* C: the carried body, a free-joint body without children */
+  int32_t  link;         /* Lk: the link C follows */
+  uint32_t flags;        /* 0; unknown bits are MIR_E_INVALID */
+} MirCarryQuery;
+int mir_carry_query_sizeof(void);
+int mir_plan_path_carry(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq /* nullable: no self test */, const MirCarryQuery* cq,
+                        const float* probes /* (N+E,4) device */, const int32_t* probe_link /* (N+E) HOST, nullable */,
+                        const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+                        const float* grasp /* (R,7) device, nullable: from the start row */, const float* qpos_goal,
+                        float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats,
+                        float* grasp_used /* (R,7) nullable */, void* stream);
+int mir_path_clearance_carry(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq /* nullable */, const MirCarryQuery* cq,
+                             const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+                             const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+                             const float* grasp /* (R,7) nullable */, const float* paths /* (R,K,D) */, int32_t K,
+                             float* seg_min /* (R,K-1) */, float* seg_self_min /* (R,K-1), NULL without sq */, float* row_min /* (R) */,
+                             float* row_self_min /* (R), NULL without sq */, int32_t* row_first_blocked /* (R) */,
+                             float* grasp_used /* (R,7) nullable */, void* stream);
 
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
