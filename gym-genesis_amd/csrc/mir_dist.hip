@@ -7,9 +7,9 @@
 // outputs.
 //
 // Mapping: one workgroup of one wave64 per row.
-//   Poses.  Lane = body.  Without qpos the body poses are copied from the pose cache to LDS.  With qpos every lane computes the local
-//   transform of its body from the row (joint_local of mir_query.h) and the world poses are composed parent before child, one round
-//   per tree depth, in LDS (a free body's pose is its qpos pose, as in the oracle's fk).
+//   Poses.  Lane = body.  Without qpos the body poses are copied from the pose cache to LDS (sphere_poses_cached), with qpos they are
+//   composed from the row (sphere_poses_fk).  Those, the row's env, the probe centres and the wave reduction are the front end that
+//   this kernel shares with mir_self.hip and mir_plan.hip: mir_sphere_front.h, like the host's row checks and argument filling.
 //   Geoms.  Lane = geom (ngeom <= 40): the geom's world frame (the arithmetic of mir_ray_kernel's prologue); the geoms whose skip bit
 //   is clear are compacted in geom order by a ballot into an LDS list of 24-float records.
 //   Probes.  Chunks of 64, lane = probe.  A lane reads its link's pose from LDS and walks the list: the record address and the geom
@@ -36,81 +36,35 @@
 #include "mir_dev.h"
 
 #include "mir_query.h"
+#include "mir_sphere_front.h"  // (brings mir_dist_body.h)
 
 #include "mir_hullfan.h"
-
-#include "mir_dist_body.h"
 
 namespace {
 
 struct DistArgs {
-  const DistTab* tab;
-  const float *planes, *tris;
-  const float* poses;  // pose cache (qpos_o == NULL)
-  int pst, B, n_rows, N, nbody, nq, depth_max;
+  SphereRowArgs r;
+  DistTabPtrs t;
+  const float* poses;  // pose cache (r.qpos_o == NULL)
+  int pst, N;
   float max_distance;
   unsigned long long skip;
-  const float* probes;
-  const long long* env_idx;
-  const float* qpos_o;  // (R, nq) public layout, nullable
-  JointPtrs m;
   float *distance, *closest, *normal, *row_min;
   int32_t *geom, *row_argmin;
-  uint32_t body[MIR_MAX_BODY];     // parent | jtype << 8 | depth << 10 (depth: bodies above it that its pose is composed with)
-  uint8_t link[DIST_MAX_PROBES];   // all zero when every probe stands in the world
 };
 static_assert(sizeof(DistArgs) <= 4096, "kernel arguments");
 
 __global__ __launch_bounds__(64) void mir_dist_kernel(DistArgs a) {
   __shared__ float xp[MIR_MAX_BODY][4], xq[MIR_MAX_BODY][4];
   __shared__ float rec[MIR_MAX_GEOM * DIST_REC];
-  const int lane = threadIdx.x;
-  const int row = blockIdx.x;
-  int env = a.env_idx ? (int)a.env_idx[row] : row;
-  env = env < 0 ? 0 : (env >= a.B ? a.B - 1 : env);  // (an index outside the batch is clamped, as in mir_link_kinematics)
+  const int lane = threadIdx.x, row = blockIdx.x;
 
   // ---- body poses, lane = body
-  {
-    const bool isb = lane < a.nbody;
-    const int b = isb ? lane : 0;
-    if (!a.qpos_o) {
-      const float* const pe = a.poses + (size_t)env * 2 * a.pst * 4;
-      V3 P = v3(0, 0, 0);
-      Q4 Qx = Q4{1, 0, 0, 0};
-      if (b > 0) {
-        P = ld3(pe + b * 4);
-        Qx = ld4(pe + (a.pst + b) * 4);
-      }
-      if (isb) {
-        st3(xp[b], P);
-        st4(xq[b], Qx);
-      }
-      WSYNC();
-    } else {
-      const uint32_t bw = a.body[b];
-      const int par = bw & 0xff, jt = (bw >> 8) & 3, depth = (bw >> 10) & 31;
-      const JointLocal jl = joint_local(isb && b > 0, b, jt, a.qpos_o + (size_t)row * a.nq, a.m);
-      V3 P = jl.P;
-      Q4 Qx = jl.Qx;
-      for (int lvl = 0; lvl <= a.depth_max; lvl++) {
-        if (isb && depth == lvl) {
-          if (lvl > 0) {
-            const V3 pp = ld3(xp[par]);
-            const Q4 pq = ld4(xq[par]);
-            P = pp + qrot(pq, P);
-            Qx = qmul(pq, Qx);
-          }
-          st3(xp[b], P);
-          st4(xq[b], Qx);
-        }
-        WSYNC();
-      }
-    }
-  }
+  if (!a.r.qpos_o) sphere_poses_cached(a.poses, a.pst, sphere_row_env(a.r, row), a.r.nbody, lane, xp, xq);
+  else sphere_poses_fk(a.r, a.r.qpos_o + (size_t)row * a.r.nq, true, lane, xp, xq);
 
   // ---- geom records, lane = geom (mir_dist_body.h)
-  int count = dist_build_records(a.tab, a.skip, lane, xp, xq, rec);
-  count = __builtin_amdgcn_readfirstlane(count);
+  const int count = __builtin_amdgcn_readfirstlane(dist_build_records(a.t.tab, a.skip, lane, xp, xq, rec));
 
   // ---- probes, 64 at a time
   float run_min = INFINITY;
@@ -118,23 +72,18 @@ __global__ __launch_bounds__(64) void mir_dist_kernel(DistArgs a) {
   for (int base = 0; base < a.N; base += 64) {
     const bool valid = base + lane < a.N;
     const int probe = valid ? base + lane : a.N - 1;
-    const float* const pr = a.probes + (size_t)probe * 4;
-    const float radius = pr[3];
-    const int lk = a.link[probe];
-    const V3 pw = ld3(xp[lk]) + qrot(ld4(xq[lk]), ld3(pr));  // probe centre, world
-    const DistBest w = dist_probe_min(rec, count, a.planes, a.tris, pw, radius, a.max_distance);
-    const float best = w.best;
-    const int bestk = w.bestk;
+    const ProbeWorld p = probe_world(a.r, probe, xp, xq);
+    const DistBest w = dist_probe_min(rec, count, a.t.planes, a.t.tris, p.c, p.radius, a.max_distance);
     const V3 bc = w.bc, bn = w.bn;  // closest point and normal of the best geom, in its frame
-    const bool hit = bestk >= 0 && best <= a.max_distance;
-    const float dist = hit ? best : a.max_distance;
+    const bool hit = w.bestk >= 0 && w.best <= a.max_distance;
+    const float dist = hit ? w.best : a.max_distance;
     const size_t cell = (size_t)row * a.N + probe;
-    const float* const rb = rec + (hit ? bestk : 0) * DIST_REC;
+    const float* const rb = rec + (hit ? w.bestk : 0) * DIST_REC;
     if (valid) {
       if (a.distance) a.distance[cell] = dist;
       if (a.geom) a.geom[cell] = hit ? __float_as_int(rb[1]) : -1;
       if (a.closest) {
-        V3 o = pw;
+        V3 o = p.c;
         if (hit) o = v3(rb[5] + rb[8] * bc.x + rb[9] * bc.y + rb[10] * bc.z, rb[6] + rb[11] * bc.x + rb[12] * bc.y + rb[13] * bc.z,
                         rb[7] + rb[14] * bc.x + rb[15] * bc.y + rb[16] * bc.z);
         st3(a.closest + cell * 3, o);
@@ -148,15 +97,10 @@ __global__ __launch_bounds__(64) void mir_dist_kernel(DistArgs a) {
     }
   }
   if (a.row_min || a.row_argmin) {  // (uniform over the launch)
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const float om = __shfl_xor(run_min, off);
-      const int oa = __shfl_xor(run_arg, off);
-      if (om < run_min || (om == run_min && oa < run_arg)) { run_min = om; run_arg = oa; }
-    }
+    const ArgMin m = wave_argmin(run_min, run_arg);
     if (lane == 0) {
-      if (a.row_min) a.row_min[row] = run_min;
-      if (a.row_argmin) a.row_argmin[row] = run_arg;
+      if (a.row_min) a.row_min[row] = m.v;
+      if (a.row_argmin) a.row_argmin[row] = m.i;
     }
   }
 }
@@ -236,44 +180,23 @@ extern "C" int mir_signed_distance(MirHandle h, const MirDistQuery* q, const flo
   if (!std::isfinite(q->max_distance) || !(q->max_distance > 0.0f)) return query_error(MIR_E_INVALID, who, "max_distance must be finite and > 0");
   if (q->flags) return query_error(MIR_E_INVALID, who, "unknown flag bit");
   if (h->ngeom < 64 && (q->skip_geoms >> h->ngeom)) return query_error(MIR_E_INVALID, who, "skip_geoms names a geom at or above ngeom");
-  if (h->pending) return query_error(MIR_E_INVALID, who, "a step is pending (mir_step_end first)");
-  if (env_idx && n_rows < 0) return query_error(MIR_E_INVALID, who, "negative n_rows");
-  const long long R = env_idx ? n_rows : h->B, N = q->n_probes;
-  if (N > DIST_MAX_PROBES) return query_error(MIR_E_CAPACITY, who, "more than 1024 probes in one call");
-  if (R * N > 0x7fffffffLL) return query_error(MIR_E_CAPACITY, who, "rows x probes reaches 2^31");
+  int rc;
+  long long R, N = q->n_probes;
+  if ((rc = check_rows(h, env_idx, n_rows, who, R)) != MIR_OK) return rc;
+  if ((rc = check_probe_count(N, R, true, who)) != MIR_OK) return rc;
   DistArgs a;
   memset(&a, 0, sizeof a);
-  if (probe_link)
-    for (int i = 0; i < (int)N; i++) {
-      if (probe_link[i] < 0 || probe_link[i] >= h->nbody) return query_error(MIR_E_INVALID, who, "probe_link outside 0 .. nbody - 1");
-      a.link[i] = (uint8_t)probe_link[i];
-    }
   const ModelView mv(h);
-  int depth_max = 0;
-  for (int b = 1; b < h->nbody; b++) {  // (body order: a parent comes before its children)
-    const int par = mv.parent(b), jt = mv.jtype(b);
-    const int depth = par > 0 && jt != MIR_JNT_FREE ? (int)((a.body[par] >> 10) & 31) + 1 : 0;
-    if (qpos && depth >= G) return query_error(MIR_E_CAPACITY, who, "path longer than 16 bodies");
-    a.body[b] = (uint32_t)par | (uint32_t)jt << 8 | (uint32_t)depth << 10;
-    if (depth > depth_max) depth_max = depth;
-  }
+  const auto refuse = [&](int code, const char* what) { return query_error(code, who, what); };
+  if ((rc = pack_probe_links(probe_link, (int)N, h->nbody, a.r.link, refuse)) != MIR_OK) return rc;
+  if ((rc = build_body_words(mv, h->nbody, qpos != nullptr, nullptr, a.r.body, a.r.depth_max, refuse)) != MIR_OK) return rc;
   DeviceGuard guard(h->device);  // (the table's allocation and the pose refresh, too)
-  int rc = MIR_OK;
-  do {
-    if ((rc = mir_dist_table(h, who)) != MIR_OK) break;
-    if (R == 0 || (!distance && !geom && !closest && !normal && !row_min && !row_argmin)) break;  // (nothing asked for)
-    // link poses: the rasteriser's pose cache, refreshed when the state has moved since it was written; not touched with qpos rows
-    if (!qpos && !h->poses_current && (rc = mir_refresh_poses(h, stream)) != MIR_OK) break;
-    const char* const tab = static_cast<const char*>(h->dist_tab);
-    a.tab = reinterpret_cast<const DistTab*>(tab);
-    a.planes = reinterpret_cast<const float*>(tab + sizeof(DistTab));
-    a.tris = a.planes + 4 * (size_t)h->dist_nplane;
-    a.poses = h->poses; a.pst = h->pt.pst; a.B = h->B; a.n_rows = (int)R; a.N = (int)N; a.nbody = h->nbody; a.nq = h->nq; a.depth_max = depth_max;
-    a.max_distance = q->max_distance; a.skip = q->skip_geoms;
-    a.probes = probes; a.env_idx = reinterpret_cast<const long long*>(env_idx); a.qpos_o = qpos;
-    a.m = mv.joint_pointers();
-    a.distance = distance; a.closest = closest; a.normal = normal; a.row_min = row_min; a.geom = geom; a.row_argmin = row_argmin;
-    rc = launch_rows<64>(h, mir_dist_kernel, R, stream, a);
-  } while (0);
-  return rc;
+  if ((rc = fill_dist_tab(h, who, a.t)) != MIR_OK) return rc;
+  if (R == 0 || (!distance && !geom && !closest && !normal && !row_min && !row_argmin)) return MIR_OK;  // (nothing asked for)
+  // link poses: the rasteriser's pose cache, refreshed when the state has moved since it was written; not touched with qpos rows
+  if (!qpos && !h->poses_current && (rc = mir_refresh_poses(h, stream)) != MIR_OK) return rc;
+  fill_sphere_rows(mv, env_idx, R, qpos, probes, a.r);
+  a.poses = h->poses; a.pst = h->pt.pst; a.N = (int)N; a.max_distance = q->max_distance; a.skip = q->skip_geoms;
+  a.distance = distance; a.closest = closest; a.normal = normal; a.row_min = row_min; a.geom = geom; a.row_argmin = row_argmin;
+  return launch_rows<64>(h, mir_dist_kernel, R, stream, a);
 }

@@ -5,7 +5,9 @@
 //   (b) dist_probe_min():     lane = probe; the minimum of (signed distance - radius) over the record list with the closest point and
 //       the normal of the winner in its geom's frame.  The record address and the geom type are wave-uniform, every distance is a
 //       closed form (see the header of mir_dist.hip).
-// Both are called by whole waves (they hold a ballot each).  Included after mir_dev.h and mir_query.h, inside no namespace.
+// Both are called by whole waves (they hold a ballot each).  What surrounds them in those kernels -- the row's env, the body poses in
+// LDS, the probe centres, the wave reductions, the pointers into the table (DistTabPtrs) -- is in mir_sphere_front.h, which includes
+// this file.  Needs mir_dev.h and mir_query.h in front of it, inside no namespace.
 #pragma once
 
 namespace {

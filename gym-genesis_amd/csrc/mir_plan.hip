@@ -7,9 +7,11 @@
 // streams a caller's trajectory through the same configuration check and reports the lowest clearance per segment.
 //
 // Mapping: one workgroup of one wave64 per row, as mir_dist.hip.  WSYNC() only; nothing travels from lane to lane through global memory.
-//   Row set-up.  The row's full start configuration (nq floats) goes to LDS; forward kinematics with lane = body (joint_local, composed
-//   parent before child); the geom records are built ONCE (dist_build_records): the host guarantees that every geom that is tested rides
-//   on a body without a planned dof above it.
+//   The row's env, the forward kinematics, the probe centres, the sphere-list entries, the wave reductions and the host's row checks and
+//   argument filling are the front end shared with mir_dist.hip and mir_self.hip: mir_sphere_front.h.
+//   Row set-up.  The row's full start configuration (nq floats) goes to LDS; forward kinematics with lane = body (sphere_poses_fk); the
+//   geom records are built ONCE (dist_build_records): the host guarantees that every geom that is tested rides on a body without a
+//   planned dof above it.
 //   clear(q).  Lane j < D writes planned dof j into the LDS row; the bodies below a planned dof (bit 15 of their word) are recomputed,
 //   every other body keeps its pose; the probes in chunks of 64 through dist_probe_min; the wave minimum of (distance - radius).
 //   A configuration is a float per lane: lane j holds dof j, lanes >= D hold 0.
@@ -48,8 +50,7 @@
 #include "mir_dev.h"
 
 #include "mir_query.h"
-
-#include "mir_dist_body.h"
+#include "mir_sphere_front.h"  // (brings mir_dist_body.h)
 
 #include "mir_self_body.h"
 
@@ -60,21 +61,17 @@ constexpr int PLAN_MAX_SUB = 4096;  // samples of one edge
 constexpr int PLAN_NO_PARENT = 0xffff;
 
 struct PlanArgs {
-  const DistTab* tab;
-  const float *planes, *tris;
-  const float* qpos;    // the scene's state (rows of qst floats, addressed like the public layout)
-  const float* qpos_o;  // (R, nq) public layout, nullable
-  int qst, B, n_rows, N, nbody, nq, depth_max, D;
+  SphereRowArgs r;  // (r.qpos_o: the start rows; body words with bit 15: a planned dof on the body's path to the world)
+  DistTabPtrs t;
+  const float* qpos;  // the scene's state (rows of qst floats, addressed like the public layout)
+  int qst, N, D;
   int NS;  // N + E: the probes of the self test (the first N are those of the scene test)
   int W, max_nodes, max_iter, smooth, ignore, K;
   uint32_t seed;
   float resolution, step, margin, max_distance;
   float self_margin, self_max;
   unsigned long long skip;
-  const float* probes;
-  const long long* env_idx;
   const float* goal;  // mir_plan_path: (R, D); mir_path_clearance: paths (R, K, D)
-  JointPtrs m;
   float* path;
   int32_t* status;
   float* poly;
@@ -84,8 +81,6 @@ struct PlanArgs {
   int32_t* first_blocked;
   float lo[PLAN_MAX_DOF], hi[PLAN_MAX_DOF];
   int32_t qadr[PLAN_MAX_DOF];
-  uint32_t body[MIR_MAX_BODY];    // parent | jtype << 8 | depth << 10 | (a planned dof on its path to the world) << 15
-  uint8_t link[DIST_MAX_PROBES];  // all zero when every probe stands in the world
   uint32_t link_mask[MIR_MAX_BODY];  // SELF: bit b of word a: the spheres on body a are tested against those on body b
   // CARRY: the carried body, the link it follows, the grasp rows (R, 7) (nullable: from the start row), the grasp each row used (nullable)
   int carry_body, carry_link;
@@ -121,17 +116,6 @@ __device__ __forceinline__ float div_refined(float x, float y) {
   return fmaf(fmaf(-t, y, x), r, t);
 }
 
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v = fmaxf(v, __shfl_xor(v, off));
-  return v;
-}
-
 // what a row carries through its launch (wave-uniform but for `lane`)
 enum { SELF_LIST = 0, SELF_IGNORED = 1, SELF_BLOCKED = 2 };  // what the last clearance() left for self_clearance()
 template <bool SELF, bool CARRY>
@@ -146,29 +130,9 @@ struct PlanRow {
   V3 gp;  // CARRY: the grasp transform, the carried body in the attach link's frame (wave-uniform)
   Q4 gq;
 
-  // forward kinematics, lane = body: every body (all) or the bodies below a planned dof; the arithmetic of mir_dist_kernel
+  // forward kinematics, lane = body: every body (all) or the bodies below a planned dof
   __device__ __forceinline__ void fk(bool all) {
-    const bool isb = lane < a.nbody;
-    const int b = isb ? lane : 0;
-    const uint32_t bw = a.body[b];
-    const int par = bw & 0xff, jt = (bw >> 8) & 3, depth = (bw >> 10) & 31;
-    const bool mine = isb && (all || ((bw >> 15) & 1u));
-    const JointLocal jl = joint_local(mine && b > 0, b, jt, L.qrow, a.m);
-    V3 P = jl.P;
-    Q4 Qx = jl.Qx;
-    for (int lvl = 0; lvl <= a.depth_max; lvl++) {
-      if (mine && depth == lvl) {
-        if (lvl > 0) {
-          const V3 pp = ld3(L.xp[par]);
-          const Q4 pq = ld4(L.xq[par]);
-          P = pp + qrot(pq, P);
-          Qx = qmul(pq, Qx);
-        }
-        st3(L.xp[b], P);
-        st4(L.xq[b], Qx);
-      }
-      WSYNC();
-    }
+    sphere_poses_fk(a.r, L.qrow, all, lane, L.xp, L.xq);
     if constexpr (CARRY)
       if (!all) {  // the carried body follows its link: link o grasp (its qpos entry is never read again, never written)
         if (lane == 0) {
@@ -190,35 +154,17 @@ struct PlanRow {
     for (int base = 0; base < a.N; base += 64) {
       const bool valid = base + lane < a.N;
       const int probe = valid ? base + lane : a.N - 1;
-      const float* const pr = a.probes + (size_t)probe * 4;
-      const float radius = pr[3];
-      const int lk = a.link[probe];
-      const V3 pw = ld3(L.xp[lk]) + qrot(ld4(L.xq[lk]), ld3(pr));
-      const DistBest w = dist_probe_min(L.rec, count, a.planes, a.tris, pw, radius, a.max_distance);
+      const ProbeWorld p = probe_world(a.r, probe, L.xp, L.xq);
+      const DistBest w = dist_probe_min(L.rec, count, a.t.planes, a.t.tris, p.c, p.radius, a.max_distance);
       const bool hit = w.bestk >= 0 && w.best <= a.max_distance;
       const float dist = hit ? w.best : a.max_distance;
-      nan |= __ballot(valid && (nonfinite(pw.x) || nonfinite(pw.y) || nonfinite(pw.z)));
+      nan |= probe_nonfinite(valid, p.c);
       if (valid) mn = fminf(mn, dist);
       if constexpr (SELF)
-        if (valid) {
-          st3(sph + 4 * probe, pw);
-          sph[4 * probe + 3] = radius;
-        }
+        if (valid) sphere_store(sph, probe, p.c, &p.radius);
     }
     if constexpr (SELF) {
-      unsigned long long nan_x = 0ull;
-      for (int base = a.N; base < a.NS; base += 64) {  // the extra probes: a centre for the list, no scene test
-        const bool valid = base + lane < a.NS;
-        const int probe = valid ? base + lane : a.NS - 1;
-        const float* const pr = a.probes + (size_t)probe * 4;
-        const int lk = a.link[probe];
-        const V3 pw = ld3(L.xp[lk]) + qrot(ld4(L.xq[lk]), ld3(pr));
-        nan_x |= __ballot(valid && (nonfinite(pw.x) || nonfinite(pw.y) || nonfinite(pw.z)));
-        if (valid) {
-          st3(sph + 4 * probe, pw);
-          sph[4 * probe + 3] = pr[3];
-        }
-      }
+      const unsigned long long nan_x = sphere_list_fill(a.r, a.N, a.NS, lane, L.xp, L.xq, sph);  // the extra probes: no scene test
       self_state = (nan | nan_x) != 0ull || (CARRY && bad) ? SELF_BLOCKED : SELF_LIST;
     }
     mn = wave_min(mn);
@@ -235,7 +181,7 @@ struct PlanRow {
     for (int base = 0; base < a.NS; base += 64) {
       const bool valid = base + lane < a.NS;
       const int i = valid ? base + lane : a.NS - 1;
-      const SelfBest w = self_probe_min<false>(sph, a.link, a.NS, base, i, valid ? a.link_mask[a.link[i]] : 0u, lane);
+      const SelfBest w = self_probe_min<false>(sph, a.r.link, a.NS, base, i, valid ? a.link_mask[a.r.link[i]] : 0u, lane);
       mn = fminf(mn, w.best);
     }
     mn = wave_min(mn);
@@ -305,11 +251,11 @@ struct PlanRow {
 template <class Row>
 __device__ __forceinline__ void plan_setup(Row& r, int row, int env) {
   const PlanArgs& a = r.a;
-  const float* const src = a.qpos_o ? a.qpos_o + (size_t)row * a.nq : a.qpos + (size_t)env * a.qst;
-  for (int i = r.lane; i < a.nq; i += 64) r.L.qrow[i] = src[i];
+  const float* const src = a.r.qpos_o ? a.r.qpos_o + (size_t)row * a.r.nq : a.qpos + (size_t)env * a.qst;
+  for (int i = r.lane; i < a.r.nq; i += 64) r.L.qrow[i] = src[i];
   WSYNC();
   r.fk(true);
-  r.count = a.ignore ? 0 : __builtin_amdgcn_readfirstlane(dist_build_records(a.tab, a.skip, r.lane, r.L.xp, r.L.xq, r.L.rec));
+  r.count = a.ignore ? 0 : __builtin_amdgcn_readfirstlane(dist_build_records(a.t.tab, a.skip, r.lane, r.L.xp, r.L.xq, r.L.rec));
   bool badrec = false;
   if (r.lane < r.count)
     for (int k = 5; k <= 16; k++) badrec = badrec || nonfinite(r.L.rec[r.lane * DIST_REC + k]);  // the geom's centre and axes
@@ -343,18 +289,13 @@ __device__ __forceinline__ void plan_setup(Row& r, int row, int env) {
   }
 }
 
-__device__ __forceinline__ int plan_env(const PlanArgs& a, int row) {
-  const int env = a.env_idx ? (int)a.env_idx[row] : row;
-  return env < 0 ? 0 : (env >= a.B ? a.B - 1 : env);  // (an index outside the batch is clamped, as in mir_link_kinematics)
-}
-
 extern __shared__ float plan_dyn[];
 
 template <bool SELF, bool CARRY>
 __global__ __launch_bounds__(64) void mir_plan_kernel(PlanArgs a) {
   __shared__ PlanLds L;
   const int lane = threadIdx.x, row = blockIdx.x, D = a.D, MN = a.max_nodes;
-  const int env = plan_env(a, row);
+  const int env = sphere_row_env(a.r, row);
   float* const tree = plan_dyn;                                                        // [2][D][MN]
   uint16_t* const parent = reinterpret_cast<uint16_t*>(plan_dyn + (size_t)2 * D * MN);  // [2][MN]
   PlanRow<SELF, CARRY> r{a, L, lane, 0, 0, false, plan_dyn + (size_t)(2 * D + 1) * MN, SELF_LIST};  // (2 MN 16-bit parents are MN floats)
@@ -386,15 +327,10 @@ __global__ __launch_bounds__(64) void mir_plan_kernel(PlanArgs a) {
       }
       if (acc < bd) { bd = acc; bi = n; }  // (nodes ascend: the lower index keeps a tie)
     }
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) {
-      const float om = __shfl_xor(bd, off);
-      const int oi = __shfl_xor(bi, off);
-      if (om < bd || (om == bd && oi < bi)) { bd = om; bi = oi; }
-    }
+    const ArgMin m = wave_argmin(bd, bi);
     WSYNC();
-    d2 = bd;
-    bi = __builtin_amdgcn_readfirstlane(bi);
+    d2 = m.v;
+    bi = __builtin_amdgcn_readfirstlane(m.i);
     return bi < cnt ? bi : 0;
   };
 
@@ -536,7 +472,7 @@ __global__ __launch_bounds__(64) void mir_path_clear_kernel(PlanArgs a) {
   __shared__ PlanLds L;
   const int lane = threadIdx.x, row = blockIdx.x, D = a.D;
   PlanRow<SELF, CARRY> r{a, L, lane, 0, 0, false, plan_dyn, SELF_LIST};
-  plan_setup(r, row, plan_env(a, row));
+  plan_setup(r, row, sphere_row_env(a.r, row));
   const bool isd = lane < D;
   const float* const p = a.goal + (size_t)row * a.K * D;
   float rmin = INFINITY, rself = INFINITY;
@@ -573,18 +509,33 @@ __global__ __launch_bounds__(64) void mir_path_clear_kernel(PlanArgs a) {
   }
 }
 
-// ---- host: what the two entry points share.  Fills `a` but for the outputs; every refusal launches nothing.
-// `self`: the call has a self test and `sq` is its MirSelfQuery (checked here); else sq is not read.  `carry`: the call is one of the two
-// *_carry entry points and `cq` is its MirCarryQuery (checked here, behind the refusals of the entry point it extends); else cq is not read.
-int plan_front(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, bool carry, const MirCarryQuery* cq, const char* who, bool planner,
-               const float* probes,
-               const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start, PlanArgs& a,
-               long long& R) {
-  if (!h || !q || !probes || !dof_qadr || (carry && !cq)) return query_error(MIR_E_INVALID, who, "null argument");
-  if (self) {
-    const int rc = self_query_check(h, sq, who);
-    if (rc != MIR_OK) return rc;
-  }
+// ---- host.  A call as its entry point hands it over, by name
+struct PlanCall {
+  const char* who;
+  MirHandle h;
+  const MirPlanQuery* q;
+  const MirSelfQuery* sq;   // read where `self` is set: the two *_self entry points always (a null sq is their refusal), the two
+  bool self;                // *_carry where sq is not null (a null sq is "no self test")
+  const MirCarryQuery* cq;  // read where `carry` is set: the two *_carry entry points
+  bool carry;
+  const float *probes, *qpos_start, *grasp;  // (grasp, grasp_used: carry only, nullable)
+  const int32_t *probe_link, *dof_qadr;
+  const int64_t* env_idx;
+  int32_t n_rows;
+  float* grasp_used;
+  void* stream;
+};
+
+// what the two kinds of entry point share.  Fills `a` but for the outputs and the table; every refusal launches nothing.  The self
+// query is checked here, the carry query too (behind the refusals of the entry point it extends).
+int plan_front(const PlanCall& c, bool planner, PlanArgs& a, long long& R) {
+  const MirHandle h = c.h;
+  const MirPlanQuery* const q = c.q;
+  const char* const who = c.who;
+  const bool self = c.self, carry = c.carry;
+  int rc;
+  if (!h || !q || !c.probes || !c.dof_qadr || (carry && !c.cq)) return query_error(MIR_E_INVALID, who, "null argument");
+  if (self && (rc = self_query_check(h, c.sq, who)) != MIR_OK) return rc;
   if (q->struct_size != (int32_t)sizeof(MirPlanQuery)) return query_error(MIR_E_INVALID, who, "struct_size is not sizeof(MirPlanQuery)");
   if (q->n_probes < 1) return query_error(MIR_E_INVALID, who, "n_probes < 1");
   if (q->n_dofs < 1 || q->n_dofs > PLAN_MAX_DOF) return query_error(MIR_E_INVALID, who, "n_dofs outside 1 .. 16");
@@ -599,26 +550,21 @@ int plan_front(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery
     if (q->max_iterations < 0 || q->smooth_passes < 0) return query_error(MIR_E_INVALID, who, "negative max_iterations or smooth_passes");
     if (!std::isfinite(q->step) || !(q->step > 0.0f)) return query_error(MIR_E_INVALID, who, "step must be finite and > 0");
   }
-  if (h->pending) return query_error(MIR_E_INVALID, who, "a step is pending (mir_step_end first)");
-  if (env_idx && n_rows < 0) return query_error(MIR_E_INVALID, who, "negative n_rows");
-  R = env_idx ? n_rows : h->B;
+  if ((rc = check_rows(h, c.env_idx, c.n_rows, who, R)) != MIR_OK) return rc;
   const int N = q->n_probes, D = q->n_dofs;
-  const long long NS = (long long)N + (self ? sq->n_extra : 0);
-  if (NS > DIST_MAX_PROBES) return query_error(MIR_E_CAPACITY, who, "more than 1024 probes in one call");
+  const long long NS = (long long)N + (self ? c.sq->n_extra : 0);
+  if ((rc = check_probe_count(NS, R, false, who)) != MIR_OK) return rc;
   memset(&a, 0, sizeof a);
-  if (probe_link)
-    for (int i = 0; i < (int)NS; i++) {
-      if (probe_link[i] < 0 || probe_link[i] >= h->nbody) return query_error(MIR_E_INVALID, who, "probe_link outside 0 .. nbody - 1");
-      a.link[i] = (uint8_t)probe_link[i];
-    }
+  const auto refuse = [&](int code, const char* what) { return query_error(code, who, what); };
+  if ((rc = pack_probe_links(c.probe_link, (int)NS, h->nbody, a.r.link, refuse)) != MIR_OK) return rc;
   const ModelView mv(h);
   // the planned dofs: the scalar joint behind each qpos address, its limits
-  bool planned[MIR_MAX_BODY] = {false}, moves[MIR_MAX_BODY] = {false};
+  bool planned[MIR_MAX_BODY] = {false};
   for (int j = 0; j < D; j++) {
     int body = -1;
     for (int b = 1; b < h->nbody; b++) {
       const int jt = mv.jtype(b);
-      if ((jt == MIR_JNT_REVOLUTE || jt == MIR_JNT_PRISMATIC) && mv.qadr(b) == dof_qadr[j]) body = b;
+      if ((jt == MIR_JNT_REVOLUTE || jt == MIR_JNT_PRISMATIC) && mv.qadr(b) == c.dof_qadr[j]) body = b;
     }
     if (body < 0) return query_error(MIR_E_INVALID, who, "dof_qadr is not the qpos address of a revolute or prismatic joint");
     if (planned[body]) return query_error(MIR_E_INVALID, who, "dof_qadr names a joint twice");
@@ -628,29 +574,20 @@ int plan_front(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery
     mv.limits(body, lo, hi, limited);
     if (!limited || !(hi > lo)) return query_error(MIR_E_INVALID, who, "a planned dof has no limits");
     if ((hi - lo) / (double)q->resolution > (double)PLAN_MAX_SUB) return query_error(MIR_E_INVALID, who, "a planned dof's range exceeds 4096 x resolution");
-    a.lo[j] = (float)lo; a.hi[j] = (float)hi; a.qadr[j] = dof_qadr[j];
+    a.lo[j] = (float)lo; a.hi[j] = (float)hi; a.qadr[j] = c.dof_qadr[j];
   }
-  int depth_max = 0;
-  for (int b = 1; b < h->nbody; b++) {  // (body order: a parent comes before its children)
-    const int par = mv.parent(b), jt = mv.jtype(b);
-    const bool chained = par > 0 && jt != MIR_JNT_FREE;
-    const int depth = chained ? (int)((a.body[par] >> 10) & 31) + 1 : 0;
-    if (depth >= G) return query_error(MIR_E_CAPACITY, who, "path longer than 16 bodies");
-    moves[b] = planned[b] || (chained && moves[par]);
-    a.body[b] = (uint32_t)par | (uint32_t)jt << 8 | (uint32_t)depth << 10 | (uint32_t)(moves[b] ? 1 : 0) << 15;
-    if (depth > depth_max) depth_max = depth;
-  }
+  if ((rc = build_body_words(mv, h->nbody, true, planned, a.r.body, a.r.depth_max, refuse)) != MIR_OK) return rc;
   a.ignore = (q->flags & MIR_PLAN_IGNORE_COLLISION) ? 1 : 0;
   if (!a.ignore)
     for (int g = 0; g < h->ngeom; g++) {
       const int b = h->kernel == 16 ? h->hm.g_body[g] : h->hm64.g_body[g];
-      if (!((q->skip_geoms >> g) & 1ull) && b >= 0 && b < h->nbody && moves[b])
+      if (!((q->skip_geoms >> g) & 1ull) && b >= 0 && b < h->nbody && ((a.r.body[b] >> 15) & 1u))
         return query_error(MIR_E_INVALID, who, "a geom that is not skipped rides on a planned joint (a moving obstacle is out of scope: skip it)");
     }
   if (carry) {
-    if (cq->struct_size != (int32_t)sizeof(MirCarryQuery)) return query_error(MIR_E_INVALID, who, "struct_size is not sizeof(MirCarryQuery)");
-    if (cq->flags) return query_error(MIR_E_INVALID, who, "unknown flag bit in MirCarryQuery");
-    const int cb = cq->body, cl = cq->link;
+    if (c.cq->struct_size != (int32_t)sizeof(MirCarryQuery)) return query_error(MIR_E_INVALID, who, "struct_size is not sizeof(MirCarryQuery)");
+    if (c.cq->flags) return query_error(MIR_E_INVALID, who, "unknown flag bit in MirCarryQuery");
+    const int cb = c.cq->body, cl = c.cq->link;
     if (cb < 1 || cb >= h->nbody || mv.jtype(cb) != MIR_JNT_FREE) return query_error(MIR_E_INVALID, who, "the carried body is not a free-joint body");
     for (int b = 1; b < h->nbody; b++)
       if (mv.parent(b) == cb) return query_error(MIR_E_INVALID, who, "the carried body has a child body");
@@ -672,65 +609,55 @@ int plan_front(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery
   }
   a.NS = (int)NS;
   if (self) {
-    a.self_margin = sq->self_margin; a.self_max = sq->max_distance;
-    memcpy(a.link_mask, sq->link_mask, sizeof a.link_mask);
+    a.self_margin = c.sq->self_margin; a.self_max = c.sq->max_distance;
+    memcpy(a.link_mask, c.sq->link_mask, sizeof a.link_mask);
   }
-  a.qpos = h->qpos; a.qpos_o = qpos_start; a.qst = h->pt.qst; a.B = h->B; a.n_rows = (int)R; a.N = N; a.nbody = h->nbody; a.nq = h->nq;
-  a.depth_max = depth_max; a.D = D;
+  fill_sphere_rows(mv, c.env_idx, R, c.qpos_start, c.probes, a.r);
+  a.qpos = h->qpos; a.qst = h->pt.qst; a.N = N; a.D = D;
   a.resolution = q->resolution; a.margin = q->margin; a.max_distance = q->max_distance; a.skip = q->skip_geoms;
-  a.probes = probes; a.env_idx = reinterpret_cast<const long long*>(env_idx);
-  a.m = mv.joint_pointers();
+  a.grasp = c.grasp; a.grasp_used = c.grasp_used;
   return MIR_OK;
 }
 
-int plan_launch(MirHandle h, const char* who, void (*kernel)(PlanArgs), PlanArgs& a, long long R, size_t dyn, void* stream) {
-  DeviceGuard guard(h->device);  // (the table's allocation, too)
-  const int rc = mir_dist_table(h, who);
-  if (rc != MIR_OK) return rc;
-  const char* const tab = static_cast<const char*>(h->dist_tab);
-  a.tab = reinterpret_cast<const DistTab*>(tab);
-  a.planes = reinterpret_cast<const float*>(tab + sizeof(DistTab));
-  a.tris = a.planes + 4 * (size_t)h->dist_nplane;
-  hipLaunchKernelGGL(kernel, dim3((unsigned)R), dim3(64), dyn, (hipStream_t)stream, a);
-  const hipError_t e = hipGetLastError();
-  return e == hipSuccess ? MIR_OK : mir_set_error(MIR_E_HIP, hipGetErrorString(e));
+// the instantiation of either kernel that serves a call
+using PlanKernel = void (*)(PlanArgs);
+PlanKernel plan_kernel(bool self, bool carry) {
+  if (carry) return self ? mir_plan_kernel<true, true> : mir_plan_kernel<false, true>;
+  return self ? mir_plan_kernel<true, false> : mir_plan_kernel<false, false>;
+}
+PlanKernel path_clear_kernel(bool self, bool carry) {
+  if (carry) return self ? mir_path_clear_kernel<true, true> : mir_path_clear_kernel<false, true>;
+  return self ? mir_path_clear_kernel<true, false> : mir_path_clear_kernel<false, false>;
 }
 
-int plan_entry(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, bool carry, const MirCarryQuery* cq, const char* who,
-               const float* probes, const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
-               const float* grasp, const float* qpos_goal, float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, float* grasp_used,
-               void* stream) {
-  if (!qpos_goal || !path || !status) return query_error(MIR_E_INVALID, who, "null argument");
+int plan_entry(const PlanCall& c, const float* qpos_goal, float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats) {
+  if (!qpos_goal || !path || !status) return query_error(MIR_E_INVALID, c.who, "null argument");
   PlanArgs a;
   long long R = 0;
-  const int rc = plan_front(h, q, self, sq, carry, cq, who, true, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
+  int rc = plan_front(c, true, a, R);
   if (rc != MIR_OK || R == 0) return rc;
-  a.grasp = grasp; a.grasp_used = grasp_used;
-  a.W = q->num_waypoints; a.max_nodes = q->max_nodes; a.max_iter = q->max_iterations; a.smooth = q->smooth_passes; a.seed = q->seed; a.step = q->step;
-  a.goal = qpos_goal; a.path = path; a.status = status; a.poly = poly; a.n_poly = n_poly; a.stats = stats;
+  a.W = c.q->num_waypoints; a.max_nodes = c.q->max_nodes; a.max_iter = c.q->max_iterations; a.smooth = c.q->smooth_passes; a.seed = c.q->seed;
+  a.step = c.q->step; a.goal = qpos_goal; a.path = path; a.status = status; a.poly = poly; a.n_poly = n_poly; a.stats = stats;
   const size_t trees = (size_t)2 * (size_t)a.max_nodes * (4 * (size_t)a.D + 2);
-  const size_t dyn = trees + (self ? 16 * (size_t)a.NS : 0);
-  if (carry) return plan_launch(h, who, self ? mir_plan_kernel<true, true> : mir_plan_kernel<false, true>, a, R, dyn, stream);
-  return plan_launch(h, who, self ? mir_plan_kernel<true, false> : mir_plan_kernel<false, false>, a, R, dyn, stream);
+  DeviceGuard guard(c.h->device);  // (the table's allocation, too)
+  if ((rc = fill_dist_tab(c.h, c.who, a.t)) != MIR_OK) return rc;
+  return launch_rows<64>(c.h, plan_kernel(c.self, c.carry), R, c.stream, a, trees + (c.self ? 16 * (size_t)a.NS : 0));
 }
 
-int path_clear_entry(MirHandle h, const MirPlanQuery* q, bool self, const MirSelfQuery* sq, bool carry, const MirCarryQuery* cq, const char* who,
-                     const float* probes, const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows,
-                     const float* qpos_start, const float* grasp, const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min,
-                     float* row_self_min, int32_t* row_first_blocked, float* grasp_used, void* stream) {
-  if (!paths) return query_error(MIR_E_INVALID, who, "null argument");
-  if (K < 2) return query_error(MIR_E_INVALID, who, "K < 2");
-  if (!self && (seg_self_min || row_self_min)) return query_error(MIR_E_INVALID, who, "seg_self_min / row_self_min without a MirSelfQuery");
+int path_clear_entry(const PlanCall& c, const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min, float* row_self_min,
+                     int32_t* row_first_blocked) {
+  if (!paths) return query_error(MIR_E_INVALID, c.who, "null argument");
+  if (K < 2) return query_error(MIR_E_INVALID, c.who, "K < 2");
+  if (!c.self && (seg_self_min || row_self_min)) return query_error(MIR_E_INVALID, c.who, "seg_self_min / row_self_min without a MirSelfQuery");
   PlanArgs a;
   long long R = 0;
-  const int rc = plan_front(h, q, self, sq, carry, cq, who, false, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, a, R);
-  if (rc != MIR_OK || R == 0 || (!seg_min && !seg_self_min && !row_min && !row_self_min && !row_first_blocked && !grasp_used)) return rc;
-  a.grasp = grasp; a.grasp_used = grasp_used;
+  int rc = plan_front(c, false, a, R);
+  if (rc != MIR_OK || R == 0 || (!seg_min && !seg_self_min && !row_min && !row_self_min && !row_first_blocked && !c.grasp_used)) return rc;
   a.K = K; a.goal = paths; a.seg_min = seg_min; a.row_min = row_min; a.first_blocked = row_first_blocked;
   a.seg_self_min = seg_self_min; a.row_self_min = row_self_min;
-  const size_t dyn = self ? 16 * (size_t)a.NS : 0;
-  if (carry) return plan_launch(h, who, self ? mir_path_clear_kernel<true, true> : mir_path_clear_kernel<false, true>, a, R, dyn, stream);
-  return plan_launch(h, who, self ? mir_path_clear_kernel<true, false> : mir_path_clear_kernel<false, false>, a, R, dyn, stream);
+  DeviceGuard guard(c.h->device);  // (the table's allocation, too)
+  if ((rc = fill_dist_tab(c.h, c.who, a.t)) != MIR_OK) return rc;
+  return launch_rows<64>(c.h, path_clear_kernel(c.self, c.carry), R, c.stream, a, c.self ? 16 * (size_t)a.NS : 0);
 }
 
 }  // namespace
@@ -741,30 +668,38 @@ extern "C" int mir_self_query_sizeof(void) { return (int)sizeof(MirSelfQuery); }
 extern "C" int mir_plan_path(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
                              const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal, float* path,
                              int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
-  return plan_entry(h, q, false, nullptr, false, nullptr, "mir_plan_path", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr, qpos_goal, path,
-                    status, poly, n_poly, stats, nullptr, stream);
+  PlanCall c{};
+  c.who = "mir_plan_path"; c.h = h; c.q = q; c.stream = stream;
+  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  return plan_entry(c, qpos_goal, path, status, poly, n_poly, stats);
 }
 
 extern "C" int mir_plan_path_self(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const float* probes, const int32_t* probe_link,
                                   const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal,
                                   float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
-  return plan_entry(h, q, true, sq, false, nullptr, "mir_plan_path_self", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr, qpos_goal, path,
-                    status, poly, n_poly, stats, nullptr, stream);
+  PlanCall c{};
+  c.who = "mir_plan_path_self"; c.h = h; c.q = q; c.sq = sq; c.self = true; c.stream = stream;
+  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  return plan_entry(c, qpos_goal, path, status, poly, n_poly, stats);
 }
 
 extern "C" int mir_path_clearance(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
                                   const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* paths, int32_t K,
                                   float* seg_min, float* row_min, int32_t* row_first_blocked, void* stream) {
-  return path_clear_entry(h, q, false, nullptr, false, nullptr, "mir_path_clearance", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr, paths,
-                          K, seg_min, nullptr, row_min, nullptr, row_first_blocked, nullptr, stream);
+  PlanCall c{};
+  c.who = "mir_path_clearance"; c.h = h; c.q = q; c.stream = stream;
+  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  return path_clear_entry(c, paths, K, seg_min, /*seg_self_min*/ nullptr, row_min, /*row_self_min*/ nullptr, row_first_blocked);
 }
 
 extern "C" int mir_path_clearance_self(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const float* probes, const int32_t* probe_link,
                                        const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
                                        const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min, float* row_self_min,
                                        int32_t* row_first_blocked, void* stream) {
-  return path_clear_entry(h, q, true, sq, false, nullptr, "mir_path_clearance_self", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr, paths,
-                          K, seg_min, seg_self_min, row_min, row_self_min, row_first_blocked, nullptr, stream);
+  PlanCall c{};
+  c.who = "mir_path_clearance_self"; c.h = h; c.q = q; c.sq = sq; c.self = true; c.stream = stream;
+  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  return path_clear_entry(c, paths, K, seg_min, seg_self_min, row_min, row_self_min, row_first_blocked);
 }
 
 extern "C" int mir_carry_query_sizeof(void) { return (int)sizeof(MirCarryQuery); }
@@ -773,14 +708,20 @@ extern "C" int mir_plan_path_carry(MirHandle h, const MirPlanQuery* q, const Mir
                                    const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
                                    const float* grasp, const float* qpos_goal, float* path, int32_t* status, float* poly, int32_t* n_poly,
                                    int32_t* stats, float* grasp_used, void* stream) {
-  return plan_entry(h, q, sq != nullptr, sq, true, cq, "mir_plan_path_carry", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, grasp, qpos_goal,
-                    path, status, poly, n_poly, stats, grasp_used, stream);
+  PlanCall c{};
+  c.who = "mir_plan_path_carry"; c.h = h; c.q = q; c.sq = sq; c.self = sq != nullptr; c.cq = cq; c.carry = true; c.stream = stream;
+  c.grasp = grasp; c.grasp_used = grasp_used;
+  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  return plan_entry(c, qpos_goal, path, status, poly, n_poly, stats);
 }
 
 extern "C" int mir_path_clearance_carry(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const MirCarryQuery* cq, const float* probes,
                                         const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows,
                                         const float* qpos_start, const float* grasp, const float* paths, int32_t K, float* seg_min, float* seg_self_min,
                                         float* row_min, float* row_self_min, int32_t* row_first_blocked, float* grasp_used, void* stream) {
-  return path_clear_entry(h, q, sq != nullptr, sq, true, cq, "mir_path_clearance_carry", probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, grasp,
-                          paths, K, seg_min, seg_self_min, row_min, row_self_min, row_first_blocked, grasp_used, stream);
+  PlanCall c{};
+  c.who = "mir_path_clearance_carry"; c.h = h; c.q = q; c.sq = sq; c.self = sq != nullptr; c.cq = cq; c.carry = true; c.stream = stream;
+  c.grasp = grasp; c.grasp_used = grasp_used;
+  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  return path_clear_entry(c, paths, K, seg_min, seg_self_min, row_min, row_self_min, row_first_blocked);
 }

@@ -210,11 +210,11 @@ static int build_link_paths(MirHandle h, const int32_t* link_body, int n_links, 
   return MIR_OK;
 }
 
-// ---- host: one launch of n_groups workgroups of TPB threads on the scene's device
+// ---- host: one launch of n_groups workgroups of TPB threads (and dyn_lds bytes of dynamic LDS each) on the scene's device
 template <int TPB = 64, class Args>
-static int launch_rows(MirHandle h, void (*kernel)(Args), long long n_groups, void* stream, const Args& a) {
+static int launch_rows(MirHandle h, void (*kernel)(Args), long long n_groups, void* stream, const Args& a, size_t dyn_lds = 0) {
   DeviceGuard guard(h->device);
-  hipLaunchKernelGGL(kernel, dim3((unsigned)n_groups), dim3(TPB), 0, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(kernel, dim3((unsigned)n_groups), dim3(TPB), dyn_lds, (hipStream_t)stream, a);
   const hipError_t e = hipGetLastError();
   return e == hipSuccess ? MIR_OK : mir_set_error(MIR_E_HIP, hipGetErrorString(e));
 }

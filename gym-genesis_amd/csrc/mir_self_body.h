@@ -2,7 +2,8 @@
 // (mir_plan_path_self, mir_path_clearance_self); include/mirigid.h "self-collision", DESIGN.md "Self-collision".
 //   device: the signed distance of two spheres of the world-frame sphere list, and the lowest one of a probe over the list;
 //   host:   the checks of a MirSelfQuery.
-// The sphere list is (centre xyz, radius) per probe in LDS, written by the wave that reads it.  Included after mir_dev.h and mir_query.h.
+// The sphere list is (centre xyz, radius) per probe in LDS, written by the wave that reads it (sphere_list_fill / sphere_store of
+// mir_sphere_front.h, where the rest of what the two files share lives).  Included after mir_dev.h and mir_query.h.
 #pragma once
 
 namespace {

@@ -903,6 +903,33 @@ class MirScene(StepHelpers):
         self.raycast_launches = self.__dict__.get("raycast_launches", 0) + 1
         return out
 
+    def _sphere_probes(self, probes, links, n_extra=None):
+        """the sphere model of signed_distance, self_distance, plan_path and path_clearance -> (probes on the device, links as host int32
+        or None).  n_extra: the call is self_distance(), whose probes are (N + n_extra, 4).  (Each call builds its query struct behind
+        this and before _sphere_qrows(): the order of their ValueErrors.)"""
+        if not isinstance(probes, torch.Tensor):
+            probes = torch.as_tensor(np.ascontiguousarray(probes, dtype=np.float32))
+        p = probes.to(device=self.device, dtype=torch.float32).contiguous()
+        if p.dim() != 2 or p.shape[1] != 4 or p.shape[0] - int(n_extra or 0) < 1:
+            raise ValueError(f"probes must be (N, 4) with N >= 1, got {tuple(p.shape)}" if n_extra is None else
+                             f"probes must be (N + n_extra, 4) with N >= 1, got {tuple(p.shape)} with n_extra = {n_extra}")
+        lk = None
+        if links is not None:
+            lk = np.ascontiguousarray(links.cpu().numpy() if isinstance(links, torch.Tensor) else links, dtype=np.int32).reshape(-1)
+            if lk.shape[0] != p.shape[0]:
+                raise ValueError(f"links must be ({p.shape[0]},), got {lk.shape}")
+        return p, lk
+
+    def _sphere_qrows(self, env_idx, qpos, qpos_name: str = "qpos"):
+        """... and their rows -> (the row list on the device or None, R, the qpos rows (R, nq) on the device or None)"""
+        idx = None if env_idx is None else torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
+        R = self.num_envs if idx is None else int(idx.numel())
+        if qpos is not None:
+            qpos = torch.as_tensor(qpos, device=self.device).to(torch.float32).contiguous()
+            if tuple(qpos.shape) != (R, self.nq):
+                raise ValueError(f"{qpos_name} must be ({R}, {self.nq}), got {tuple(qpos.shape)}")
+        return idx, R, qpos
+
     def signed_distance(self, probes, links=None, env_idx=None, qpos=None, max_distance: float = 1.0, skip_geoms=0, geom: bool = False,
                         closest: bool = False, normal: bool = False, row_min: bool = False) -> dict:
         """mir_signed_distance: the signed distance from the N probe spheres `probes` ((N,4) float32: centre in the frame of the probe's
@@ -915,26 +942,10 @@ class MirScene(StepHelpers):
         outward gradient, 0 on a miss; row_min: adds row_min (R,) and row_argmin (R,) int32, the lowest distance of a row and its probe.
         distance and what was asked for are returned: fresh device tensors on the current stream.  The call changes nothing a later
         call can see."""
-        if not isinstance(probes, torch.Tensor):
-            probes = torch.as_tensor(np.ascontiguousarray(probes, dtype=np.float32))
-        p = probes.to(device=self.device, dtype=torch.float32).contiguous()
-        if p.dim() != 2 or p.shape[1] != 4 or p.shape[0] < 1:
-            raise ValueError(f"probes must be (N, 4) with N >= 1, got {tuple(p.shape)}")
+        p, lk = self._sphere_probes(probes, links)
         N = int(p.shape[0])
-        lk = None
-        if links is not None:
-            lk = np.ascontiguousarray(links.cpu().numpy() if isinstance(links, torch.Tensor) else links, dtype=np.int32).reshape(-1)
-            if lk.shape[0] != N:
-                raise ValueError(f"links must be ({N},), got {lk.shape}")
         q = make_dist_query(N, max_distance, skip_geoms)
-        idx = None
-        if env_idx is not None:
-            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
-        R = self.num_envs if idx is None else int(idx.numel())
-        if qpos is not None:
-            qpos = torch.as_tensor(qpos, device=self.device).to(torch.float32).contiguous()
-            if tuple(qpos.shape) != (R, self.nq):
-                raise ValueError(f"qpos must be ({R}, {self.nq}), got {tuple(qpos.shape)}")
+        idx, R, qpos = self._sphere_qrows(env_idx, qpos)
         new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
         out = {"distance": new(N)}
         if geom:
@@ -961,26 +972,10 @@ class MirScene(StepHelpers):
         when none is that near; other (R, N + E) int32 = that sphere, -1: none; row_min: adds row_min (R,) and row_pair (R, 2) int32,
         the lowest distance of the row and its pair (i < j; (-1, -1): none).  `qpos` (R, nq) is evaluated instead of the rows' current
         state.  Fresh device tensors on the current stream; the call changes nothing a later call can see."""
-        if not isinstance(probes, torch.Tensor):
-            probes = torch.as_tensor(np.ascontiguousarray(probes, dtype=np.float32))
-        p = probes.to(device=self.device, dtype=torch.float32).contiguous()
-        if p.dim() != 2 or p.shape[1] != 4 or p.shape[0] - int(n_extra) < 1:
-            raise ValueError(f"probes must be (N + n_extra, 4) with N >= 1, got {tuple(p.shape)} with n_extra = {n_extra}")
+        p, lk = self._sphere_probes(probes, links, n_extra=n_extra)
         NS = int(p.shape[0])
-        lk = None
-        if links is not None:
-            lk = np.ascontiguousarray(links.cpu().numpy() if isinstance(links, torch.Tensor) else links, dtype=np.int32).reshape(-1)
-            if lk.shape[0] != NS:
-                raise ValueError(f"links must be ({NS},), got {lk.shape}")
         sq = make_self_query(link_mask, n_extra, 0.0, max_distance)
-        idx = None
-        if env_idx is not None:
-            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
-        R = self.num_envs if idx is None else int(idx.numel())
-        if qpos is not None:
-            qpos = torch.as_tensor(qpos, device=self.device).to(torch.float32).contiguous()
-            if tuple(qpos.shape) != (R, self.nq):
-                raise ValueError(f"qpos must be ({R}, {self.nq}), got {tuple(qpos.shape)}")
+        idx, R, qpos = self._sphere_qrows(env_idx, qpos)
         new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
         out = {"distance": new(NS)}
         if other:
@@ -1002,26 +997,9 @@ class MirScene(StepHelpers):
 
     def _plan_front(self, probes, links, dof_qadr, env_idx, qpos_start):
         """the arguments mir_plan_path and mir_path_clearance share -> (probes on the device, links, dof addresses, row list, R, start rows)"""
-        if not isinstance(probes, torch.Tensor):
-            probes = torch.as_tensor(np.ascontiguousarray(probes, dtype=np.float32))
-        p = probes.to(device=self.device, dtype=torch.float32).contiguous()
-        if p.dim() != 2 or p.shape[1] != 4 or p.shape[0] < 1:
-            raise ValueError(f"probes must be (N, 4) with N >= 1, got {tuple(p.shape)}")
-        lk = None
-        if links is not None:
-            lk = np.ascontiguousarray(links.cpu().numpy() if isinstance(links, torch.Tensor) else links, dtype=np.int32).reshape(-1)
-            if lk.shape[0] != p.shape[0]:
-                raise ValueError(f"links must be ({p.shape[0]},), got {lk.shape}")
+        p, lk = self._sphere_probes(probes, links)
         qa = np.ascontiguousarray(dof_qadr, dtype=np.int32).reshape(-1)
-        idx = None
-        if env_idx is not None:
-            idx = torch.as_tensor(env_idx, device=self.device).long().reshape(-1).contiguous()
-        R = self.num_envs if idx is None else int(idx.numel())
-        if qpos_start is not None:
-            qpos_start = torch.as_tensor(qpos_start, device=self.device).to(torch.float32).contiguous()
-            if tuple(qpos_start.shape) != (R, self.nq):
-                raise ValueError(f"qpos_start must be ({R}, {self.nq}), got {tuple(qpos_start.shape)}")
-        return p, lk, qa, idx, R, qpos_start
+        return (p, lk, qa, *self._sphere_qrows(env_idx, qpos_start, "qpos_start"))
 
     def _carry_query(self, carry, R):
         """carry = dict(body, link, grasp=None) -> (MirCarryQuery, the grasp rows (R, 7) on the device or None, grasp_used (R, 7))"""
@@ -1097,12 +1075,12 @@ class MirScene(StepHelpers):
         out = {"seg_min": torch.empty((R, K - 1), dtype=torch.float32, device=self.device),
                "row_min": torch.empty((R,), dtype=torch.float32, device=self.device),
                "row_first_blocked": torch.empty((R,), dtype=torch.int32, device=self.device)}
+        if sq is not None:
+            out["seg_self_min"] = torch.empty((R, K - 1), dtype=torch.float32, device=self.device)
+            out["row_self_min"] = torch.empty((R,), dtype=torch.float32, device=self.device)
         lkp = None if lk is None else lk.ctypes.data_as(C.c_void_p)
         if carry is not None:
             cq, grasp, out["grasp"] = self._carry_query(carry, R)
-            if sq is not None:
-                out["seg_self_min"] = torch.empty((R, K - 1), dtype=torch.float32, device=self.device)
-                out["row_self_min"] = torch.empty((R,), dtype=torch.float32, device=self.device)
             self._check(self.lib.mir_path_clearance_carry(self.h, C.byref(q), None if sq is None else C.byref(sq), C.byref(cq), _ptr(p), lkp,
                                                           qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(grasp), _ptr(paths), K,
                                                           _ptr(out["seg_min"]), _ptr(out.get("seg_self_min")), _ptr(out["row_min"]),
@@ -1113,8 +1091,6 @@ class MirScene(StepHelpers):
                                                     _ptr(paths), K, _ptr(out["seg_min"]), _ptr(out["row_min"]), _ptr(out["row_first_blocked"]),
                                                     self._stream()))
         else:
-            out["seg_self_min"] = torch.empty((R, K - 1), dtype=torch.float32, device=self.device)
-            out["row_self_min"] = torch.empty((R,), dtype=torch.float32, device=self.device)
             self._check(self.lib.mir_path_clearance_self(self.h, C.byref(q), C.byref(sq), _ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
                                                          _ptr(qpos_start), _ptr(paths), K, _ptr(out["seg_min"]), _ptr(out["seg_self_min"]),
                                                          _ptr(out["row_min"]), _ptr(out["row_self_min"]), _ptr(out["row_first_blocked"]),

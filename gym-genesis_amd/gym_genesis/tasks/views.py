@@ -382,6 +382,12 @@ class EntityView:
             kw["qvel"] = full
         return kw
 
+    def _state_rows(self, envs_idx, who: str, qpos=None, qvel=None):
+        """-> (the row list or None, R, _full_state_rows() of the overrides): how every query at candidate rows starts"""
+        idx = _env_index(self._mir, envs_idx)
+        R = self._mir.num_envs if idx is None else int(idx.numel())
+        return idx, R, self._full_state_rows(idx, R, qpos=qpos, qvel=qvel, who=who)
+
     def _task_dynamics(self, idx, **kw) -> dict:
         fn = getattr(self._mir, "task_dynamics", None)
         if fn is None:
@@ -423,10 +429,7 @@ class EntityView:
         inverse_dynamics.  TWO launches: mir_dynamics for the bias force c, then mir_task_dynamics for the solve.  At `qpos` / `qvel`
         (B, n) over this entity's dofs when given, else at the current state; passive damping, PD torques and contact forces are not
         included (they belong in tau)."""
-        mir = self._mir
-        idx = _env_index(mir, envs_idx)
-        R = mir.num_envs if idx is None else int(idx.numel())
-        kw = self._full_state_rows(idx, R, qpos=qpos, qvel=qvel, who="forward_dynamics")
+        idx, R, kw = self._state_rows(envs_idx, "forward_dynamics", qpos=qpos, qvel=qvel)
         bias = self._dynamics(idx, None, "bias", **kw)
         x = self._entity_rows(tau, R, "tau") - bias
         return self.mass_mat_solve(x, qpos=qpos, envs_idx=idx)
@@ -437,10 +440,7 @@ class EntityView:
         jbar (B, n, 6) = M^-1 J^T lambda over this entity's dofs, with J = get_jacobian(link, local_point) (linear rows first, then
         angular).  Where the task space is singular to float32 -- a link with fewer than six dofs above it, an arm at a singularity --
         lambda and jbar of that env are NaN; damping > 0 is the remedy.  lambda_inv is always finite."""
-        mir = self._mir
-        idx = _env_index(mir, envs_idx)
-        R = mir.num_envs if idx is None else int(idx.numel())
-        kw = self._full_state_rows(idx, R, qpos=qpos, who="operational_space")
+        idx, R, kw = self._state_rows(envs_idx, "operational_space", qpos=qpos)
         lp = None if local_point is None else [float(v) for v in np.asarray(local_point).reshape(3)]
         out = self._task_dynamics(idx, links=[self._link_body(link)], local_points=lp, damping=float(damping), **kw)
         return {"lambda_inv": out["lambda_inv"][:, 0].contiguous(), "lambda": out["lambda"][:, 0].contiguous(), "jbar": out["jbar"][:, 0].contiguous()}
@@ -563,6 +563,13 @@ class EntityView:
                 mask |= 1 << g
         return mask
 
+    def _skip_mask(self, with_entity=None, ignore_entities=()) -> int:
+        """bit mask of the geoms a clearance query leaves out besides the entity's own: all but `with_entity`'s, and `ignore_entities`'"""
+        skip = 0 if with_entity is None else ((1 << len(self._b.geoms)) - 1) & ~with_entity._own_geoms()
+        for e in ignore_entities:
+            skip |= e._own_geoms()
+        return skip
+
     def _clearance_model(self):
         """(probes, links, probes on the device, own geom mask): derived once -- the model on the host, its probes on the device"""
         mir = self._mir
@@ -598,14 +605,9 @@ class EntityView:
             if len(sel) == 0:
                 raise ValueError("no collision sphere rides on the links asked for")
             dev_probes, lk = torch.as_tensor(probes[sel], device=mir.device), np.ascontiguousarray(lk[sel])
-        skip = own
-        if with_entity is not None:
-            skip |= ((1 << len(self._b.geoms)) - 1) & ~with_entity._own_geoms()
-        idx = _env_index(mir, envs_idx)
-        R = mir.num_envs if idx is None else int(idx.numel())
-        kw = self._full_state_rows(idx, R, qpos=qpos, who="get_clearance")
-        r = fn(dev_probes, links=lk, env_idx=idx, max_distance=float(max_distance), skip_geoms=skip, geom=return_detail, closest=return_detail,
-               normal=return_detail, row_min=True, **kw)
+        idx, R, kw = self._state_rows(envs_idx, "get_clearance", qpos=qpos)
+        r = fn(dev_probes, links=lk, env_idx=idx, max_distance=float(max_distance), skip_geoms=own | self._skip_mask(with_entity), geom=return_detail,
+               closest=return_detail, normal=return_detail, row_min=True, **kw)
         if not return_detail:
             return r["row_min"]
         arg = r["row_argmin"].long()
@@ -751,9 +753,7 @@ class EntityView:
         if fn is None:
             raise NotImplementedError("this scene has no self-collision queries (MirScene.self_distance / mir_self_distance)")
         dev, lk, sm = self._self_args(0.0, max_distance)
-        idx = _env_index(mir, envs_idx)
-        R = mir.num_envs if idx is None else int(idx.numel())
-        kw = self._full_state_rows(idx, R, qpos=qpos, who="get_self_clearance")
+        idx, R, kw = self._state_rows(envs_idx, "get_self_clearance", qpos=qpos)
         r = fn(dev, links=lk, link_mask=sm["link_mask"], env_idx=idx, max_distance=float(max_distance), n_extra=sm["n_extra"], row_min=True, **kw)
         if not return_detail:
             return r["row_min"]
@@ -861,15 +861,9 @@ class EntityView:
             if getattr(mir, "self_distance", None) is None:
                 raise NotImplementedError("this scene has no self-collision queries (MirScene.self_distance / mir_self_distance)")
             dev_probes, lk, extra["self_model"] = self._self_args(self_margin)
-        skip = own
-        if with_entity is not None:
-            skip |= ((1 << len(self._b.geoms)) - 1) & ~with_entity._own_geoms()
-        for e in ignore_entities:
-            skip |= e._own_geoms()
-        idx = _env_index(mir, envs_idx)
-        R = mir.num_envs if idx is None else int(idx.numel())
-        kw = self._full_state_rows(idx, R, qpos=qpos_start, who=who)
-        args = dict(probes=dev_probes, links=lk, dof_qadr=self._qcols, env_idx=idx, qpos_start=kw.get("qpos"), skip_geoms=skip, **extra)
+        idx, R, kw = self._state_rows(envs_idx, who, qpos=qpos_start)
+        args = dict(probes=dev_probes, links=lk, dof_qadr=self._qcols, env_idx=idx, qpos_start=kw.get("qpos"),
+                    skip_geoms=own | self._skip_mask(with_entity, ignore_entities), **extra)
         if attached_entity is not None:
             if not (np.isfinite(self_margin) and self_margin >= 0.0):
                 raise ValueError(f"self_margin must be finite and >= 0, got {self_margin}")
