@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirCarryQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_carry_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_self_query, make_task_query  # noqa: F401
+from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirCarryQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_carry_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -165,6 +165,9 @@ def load_library() -> C.CDLL:
                                              i32, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_path_clearance_carry.restype = C.c_int
     lib.mir_path_clearance_self.restype = C.c_int
+    lib.mir_retime_query_sizeof.restype = C.c_int
+    lib.mir_retime_path.argtypes = [vp, C.POINTER(MirRetimeQuery), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_retime_path.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
@@ -189,6 +192,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirSelfQuery (rebuild the library)")
     if lib.mir_carry_query_sizeof() != C.sizeof(MirCarryQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCarryQuery (rebuild the library)")
+    if lib.mir_retime_query_sizeof() != C.sizeof(MirRetimeQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRetimeQuery (rebuild the library)")
     if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
     _lib = lib
@@ -1097,6 +1102,44 @@ class MirScene(StepHelpers):
                                                          self._stream()))
         if R > 0:
             self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
+        return out
+
+    def retime_path(self, paths, vmax, amax, dt, num_samples: int = 0, max_path_speed=None, extra=None, velocity: bool = False) -> dict:
+        """mir_retime_path: the joint paths `paths` (R, K, D) -- K waypoints of D <= 16 dofs per row, as plan_path()["path"] holds them --
+        as time-optimal trajectories within `vmax` and `amax` (a scalar or D values, shared by the rows), in ONE launch (include/mirigid.h
+        has the algorithm: TOPP-RA on the caller's waypoints, repeated waypoints dropped).  `dt`: the sample period; `num_samples` = T:
+        the samples written per row (0: none); `max_path_speed` in waypoints per second (None: 1 / dt, at most one waypoint per
+        sample); `extra` = (ea, eb, elo, ehi), each (R, K, E): E more rows elo <= ea u + eb x <= ehi per waypoint (torque limits).
+        -> dict of fresh device tensors on the current stream: x, t (R, K) squared path speed and time at the caller's waypoints,
+        duration (R,), status (R,) int32 (spec.RETIME_STATUS), n_samples (R,) int32 = ceil(duration / dt) + 1, and with T > 0 samples
+        (R, T, D) -- targets at n dt, the end configuration from the duration on -- and, with `velocity`, sample_vel (R, T, D).  A row
+        with n_samples > T is TRUNCATED (x, t, duration valid); a row that fails otherwise holds its start T times.  The call reads no
+        state and changes nothing a later call can see."""
+        paths = torch.as_tensor(paths, device=self.device).to(torch.float32).contiguous()
+        if paths.dim() != 3:
+            raise ValueError(f"paths must be (R, K, D), got {tuple(paths.shape)}")
+        R, K, D = (int(v) for v in paths.shape)
+        ex, E = [None] * 4, 0
+        if extra is not None:
+            ex = [torch.as_tensor(e, device=self.device).to(torch.float32).contiguous() for e in extra]
+            if len(ex) != 4 or any(e.dim() != 3 or tuple(e.shape) != (R, K, int(ex[0].shape[-1])) for e in ex):
+                raise ValueError(f"extra must be four ({R}, {K}, E) tensors (ea, eb, elo, ehi), got {[tuple(e.shape) for e in ex]}")
+            E = int(ex[0].shape[2])
+            if E == 0:
+                ex = [None] * 4
+        T = int(num_samples)
+        q = make_retime_query(D, K, vmax, amax, dt, T, max_path_speed, E)
+        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        out = {"x": new(K), "t": new(K), "duration": new(), "status": new(dtype=torch.int32), "n_samples": new(dtype=torch.int32)}
+        if T > 0:
+            out["samples"] = new(T, D)
+            if velocity:
+                out["sample_vel"] = new(T, D)
+        if R > 0:   # (without rows there is nothing to point at)
+            self._check(self.lib.mir_retime_path(self.h, C.byref(q), R, _ptr(paths), *(_ptr(e) for e in ex), _ptr(out["x"]), _ptr(out["t"]),
+                                                 _ptr(out["duration"]), _ptr(out["status"]), _ptr(out["n_samples"]), _ptr(out.get("samples")),
+                                                 _ptr(out.get("sample_vel")), self._stream()))
+            self.retime_launches = self.__dict__.get("retime_launches", 0) + 1
         return out
 
     def render(self, cam: MirCameraSpec, vis: MirVisualSpec, mode: int = 0, env_offset: Optional[torch.Tensor] = None,

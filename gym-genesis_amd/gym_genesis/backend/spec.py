@@ -555,6 +555,45 @@ def make_carry_query(body: int, link: int) -> MirCarryQuery:
     return q
 
 
+RETIME_MAX_WAYPOINTS = 2048  # MIR_RETIME_MAX_WAYPOINTS (include/mirigid.h)
+RETIME_MAX_DOF = 16
+RETIME_STATUS = ("OK", "NO_MOTION", "TOO_FEW_WAYPOINTS", "NOT_FINITE", "INFEASIBLE", "TRUNCATED")
+RETIME_OK, RETIME_NO_MOTION, RETIME_TOO_FEW_WAYPOINTS, RETIME_NOT_FINITE, RETIME_INFEASIBLE, RETIME_TRUNCATED = range(6)
+
+
+class MirRetimeQuery(C.Structure):
+    """include/mirigid.h: MirRetimeQuery (mir_retime_path)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("n_dofs", C.c_int32),
+        ("n_extra", C.c_int32),
+        ("num_waypoints", C.c_int32),
+        ("num_samples", C.c_int32),
+        ("flags", C.c_uint32),
+        ("dt", C.c_float),
+        ("max_path_speed", C.c_float),
+        ("vmax", C.c_float * RETIME_MAX_DOF),
+        ("amax", C.c_float * RETIME_MAX_DOF),
+    ]
+
+
+def make_retime_query(n_dofs: int, num_waypoints: int, vmax, amax, dt: float, num_samples: int = 0, max_path_speed=None,
+                      n_extra: int = 0) -> MirRetimeQuery:
+    """vmax, amax: a scalar or n_dofs values; max_path_speed None: 1 / dt, at most one waypoint per sample."""
+    q = MirRetimeQuery()
+    q.struct_size = C.sizeof(MirRetimeQuery)
+    q.n_dofs, q.n_extra, q.num_waypoints, q.num_samples, q.flags = int(n_dofs), int(n_extra), int(num_waypoints), int(num_samples), 0
+    q.dt = float(dt)
+    q.max_path_speed = (1.0 / q.dt if q.dt != 0.0 else math.inf) if max_path_speed is None else float(max_path_speed)   # (q.dt: the float32 the kernel reads)
+    n = max(0, min(int(n_dofs), RETIME_MAX_DOF))
+    for name, lim in (("vmax", vmax), ("amax", amax)):
+        v = [float(x) for x in lim] if hasattr(lim, "__len__") else [float(lim)] * n
+        if len(v) != n:
+            raise ValueError(f"{name} must be a scalar or {n} values, got {len(v)}")
+        getattr(q, name)[:n] = v
+    return q
+
+
 IK_DEFAULTS = dict(max_iters=20, respect_joint_limit=1, damping=0.05, pos_tol=5e-4, rot_tol=5e-3, max_step=0.5)
 
 RENDER_PER_ENV, RENDER_GLOBAL = 0, 1

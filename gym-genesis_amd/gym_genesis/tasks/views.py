@@ -968,6 +968,139 @@ class EntityView:
                                        self_margin=self_margin, attached_entity=attached_entity, ee_link_name=ee_link_name, grasp_pose=grasp_pose,
                                        attached_links=attached_links) < float(margin)
 
+    # ---- time parameterisation (MirScene.retime_path / mir_retime_path): what stands between plan_path and control_dofs_position.
+    # get_dofs_force_range is a Genesis name (RigidEntity); retime_path is this package's own: parity with Genesis is unpinned.
+    def get_dofs_force_range(self, dofs_idx_local=None):
+        """``entity.get_dofs_force_range()`` (a Genesis name) -> (lower (n,), upper (n,)): the force range of this entity's dofs in its
+        dof order, as the scene was built (frc_range).  A host-side getter: nothing is launched."""
+        cols = self._jac_dofs()
+        if dofs_idx_local is not None:
+            cols = [cols[int(i)] for i in np.asarray(dofs_idx_local).ravel()]
+        fr = np.asarray([self._b.dofs[d]["frc_range"] for d in cols], np.float32).reshape(-1, 2)
+        return tuple(torch.as_tensor(np.ascontiguousarray(fr[:, k]), device=self._mir.device) for k in (0, 1))
+
+    def _torque_rows(self, rows, idx, R: int, torque_limits):
+        """the extra rows of retime_path(torque_limits=...): one per dof and waypoint of `rows` (R, K, n), lo <= alpha u + beta x <= hi
+        with alpha = ID(q, 0, m) - g, beta = ID(q, m, c) - g, g = ID(q, 0, 0) and (lo, hi) = the limits - g, from three
+        inverse_dynamics calls on R x K rows (evaluated at a scaled m, below).  m and c are the differences of mir_retime_path's step 2
+        over the KEPT waypoints (a waypoint that repeats the one in front of it is dropped there, and its rows here are never read),
+        found without a host read."""
+        mir, (_, K, n) = self._mir, rows.shape
+        if torque_limits is True:
+            lo_lim, hi_lim = self.get_dofs_force_range()
+        else:
+            hi_lim = torch.as_tensor(torque_limits, device=mir.device).to(torch.float32).reshape(-1)
+            if hi_lim.numel() != n:
+                raise ValueError(f"torque_limits must be True or ({n},) over this entity's dofs, got {tuple(hi_lim.shape)}")
+            lo_lim = -hi_lim
+        ar = torch.arange(K, device=mir.device)
+        kept = torch.cat([torch.ones((R, 1), dtype=torch.bool, device=mir.device), (rows[:, 1:] != rows[:, :-1]).any(-1)], 1)
+        cand = torch.where(kept, ar[None, :], torch.full_like(ar, K)[None, :])
+        upto = torch.flip(torch.cummin(torch.flip(cand, (1,)), 1).values, (1,))          # the first kept waypoint at or behind k
+        nxt = torch.cat([upto[:, 1:], torch.full((R, 1), K, dtype=upto.dtype, device=mir.device)], 1)   # ... behind k (K: none)
+        has_next = (nxt < K)[..., None]
+        qn = torch.gather(rows, 1, nxt.clamp(max=K - 1)[..., None].expand(R, K, n))
+        dn = torch.where(has_next, qn - rows, torch.zeros_like(rows))
+        # (the waypoint in front of a kept one compares equal to the one kept before it)
+        dp = torch.cat([torch.zeros_like(rows[:, :1]), rows[:, 1:] - rows[:, :-1]], 1)
+        inner = has_next & (ar > 0)[None, :, None]
+        m = torch.where(inner, (dn + dp) * 0.5, dn + dp)
+        c = torch.where(inner, dn - dp, torch.zeros_like(rows))
+        envs = (torch.arange(R, device=mir.device) if idx is None else idx).repeat_interleave(K)
+        q, flat = rows.reshape(R * K, n), lambda t: t.reshape(R * K, n)  # noqa: E731
+        zero = torch.zeros_like(q)
+        # m is a few hundredths of a radian per waypoint: M m would be lost beside g in the float32 sum ID(q, 0, m).  The inverse dynamics
+        # are linear in the acceleration and quadratic in the velocity, so a power of two s per waypoint gives
+        # alpha = (ID(q, 0, s m) - g) / s and beta = (ID(q, s m, s^2 c) - g) / s^2 with the three terms at comparable sizes: s puts the
+        # larger of |m| and |c| between 8 and 16 (c counts for a waypoint where the path turns round on itself, m = 0)
+        size = torch.maximum(m.abs().amax(-1, keepdim=True), c.abs().amax(-1, keepdim=True)).clamp_min(2.0 ** -20)
+        s = flat(torch.exp2(4.0 - torch.ceil(torch.log2(size))).expand(R, K, n))
+        g = self.inverse_dynamics(zero, qpos=q, qvel=zero, envs_idx=envs)
+        al = (self.inverse_dynamics(s * flat(m), qpos=q, qvel=zero, envs_idx=envs) - g) / s
+        be = (self.inverse_dynamics(s * s * flat(c), qpos=q, qvel=s * flat(m), envs_idx=envs) - g) / (s * s)
+        return tuple(t.reshape(R, K, n).contiguous() for t in (al, be, lo_lim[None, :] - g, hi_lim[None, :] - g))
+
+    def retime_path(self, path, max_velocity, max_acceleration, dt=None, num_samples=None, torque_limits=None, refine: int = 1, envs_idx=None,
+                    return_detail: bool = False):
+        """``robot.retime_path(path, max_velocity, max_acceleration)`` -> (T, R, n): the joint path `path` ((K, R, n) as plan_path
+        returns it, in this entity's dof order) as position targets every `dt` seconds (None: the scene's step) that
+        control_dofs_position takes one per step: the fastest traversal of the polyline from rest to rest that keeps each dof's
+        |velocity| <= `max_velocity` and |acceleration| <= `max_acceleration` (scalars or (n,)), from ONE launch for all rows
+        (MirScene.retime_path / mir_retime_path, where the algorithm is written down: TOPP-RA on the waypoints).  A waypoint that
+        repeats the one in front of it is dropped; a row whose waypoints are all equal (a failed plan) comes back as its start,
+        status NO_MOTION, which is no error.  From a row's duration on its targets are its last waypoint.
+        `refine` = r splits every segment into r equal parts first (the points stay on the polyline): the limits are collocated at the
+        waypoints, so finer waypoints bound the motion more tightly.  Two distinct waypoints cannot be timed (rest to rest over one
+        interval of constant path acceleration): a two-waypoint path with refine=1 raises ValueError.
+        `num_samples` None: one launch without samples, ONE host read of the longest n_samples (the only synchronisation of this
+        call), and a second launch with T sized to it.  An explicit `num_samples` = T is one launch without a host read; a row that
+        needs more comes back TRUNCATED with its first T targets.
+        `torque_limits` True (the dofs' force range, get_dofs_force_range()) or (n,): the torque of the rigid-body dynamics along the
+        path stays within them, collocated at the waypoints, by one extra row per dof and waypoint from three inverse_dynamics calls
+        on R x K rows (the other entities stay in their current state and at rest, as inverse_dynamics documents; no contact forces).
+        return_detail=True -> a dict: samples (T, R, n), velocity (T, R, n), valid (R,) bool (OK or NO_MOTION), status (R,) int32
+        (spec.RETIME_STATUS), duration (R,), n_samples (R,), and t, x (R, K'): time and squared path speed (waypoints^2 / s^2) at the
+        waypoints of the refined path, K' = (K - 1) r + 1.  On an unbatched task (num_envs = 0) every result comes without its env axis.
+        Not done: corners are not blended (a dof's velocity changes at a kink within one sample), no jerk limit, rest at both ends."""
+        mir = self._mir
+        if getattr(mir, "retime_path", None) is None:
+            raise NotImplementedError("this scene has no time parameterisation (MirScene.retime_path / mir_retime_path)")
+        n = len(self._qcols)
+        if not n:
+            raise NotImplementedError("retime_path: an entity without scalar joints")
+        one = bool(self.__dict__.get("unbatched"))
+        idx = _env_index(mir, envs_idx)
+        R = mir.num_envs if idx is None else int(idx.numel())
+        p = torch.as_tensor(path, device=mir.device).to(torch.float32)
+        if one and p.dim() == 2:
+            p = p[:, None]
+        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != n or p.shape[0] < 2:
+            raise ValueError(f"path must be (K >= 2, {R}, {n}), got {tuple(p.shape)}")
+        r = int(refine)
+        if r < 1:
+            raise ValueError(f"refine must be >= 1, got {refine}")
+        if p.shape[0] == 2 and r == 1:
+            raise ValueError("a path of two waypoints cannot be timed (rest to rest needs three): pass refine >= 2 to split its segment")
+
+        def limit(v, name):
+            a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32).reshape(-1)
+            a = np.full(n, a[0], np.float32) if a.size == 1 else a
+            if a.size != n or not (np.isfinite(a).all() and (a > 0).all()):
+                raise ValueError(f"{name} must be a scalar or ({n},), finite and > 0, got {v!r}")
+            return [float(x) for x in a]
+
+        vmax, amax = limit(max_velocity, "max_velocity"), limit(max_acceleration, "max_acceleration")
+        dt = float(self._b.opt["dt"] if dt is None else dt)
+        if not (np.isfinite(dt) and dt > 0.0):
+            raise ValueError(f"dt must be finite and > 0, got {dt}")
+        rows = p.permute(1, 0, 2).contiguous()   # (R, K, n)
+        if r > 1:
+            f = (torch.arange(r, dtype=torch.float32, device=mir.device) / float(r))[None, None, :, None]
+            a, b = rows[:, :-1, None, :], rows[:, 1:, None, :]
+            rows = torch.cat([(a + f * (b - a)).reshape(R, -1, n), rows[:, -1:]], 1).contiguous()
+        kw = dict(vmax=vmax, amax=amax, dt=dt)
+        if torque_limits is not None and torque_limits is not False:
+            kw["extra"] = self._torque_rows(rows, idx, R, torque_limits)
+        if num_samples is None:
+            first = mir.retime_path(rows, num_samples=0, **kw)
+            T = max(int(first["n_samples"].max().item()), 1) if R > 0 else 1   # (the one host read: it waits for the launch above)
+            if R * T * n > 0x7fffffff:   # (mir_retime_path's MIR_E_CAPACITY, met before anything of that size is allocated)
+                raise ValueError(f"the longest row takes {T} samples at dt = {dt}: {R} x {T} x {n} targets are beyond 2^31 - 1 "
+                                 "(raise the limits or dt, or pass num_samples and read the rows that come back TRUNCATED)")
+        else:
+            T = int(num_samples)
+            if T < 1:
+                raise ValueError(f"num_samples must be >= 1 or None, got {num_samples}")
+        res = mir.retime_path(rows, num_samples=T, velocity=bool(return_detail), **kw)
+        samples = res["samples"].permute(1, 0, 2).contiguous()
+        if not return_detail:
+            return samples[:, 0] if one else samples
+        detail = {"samples": samples, "velocity": res["sample_vel"].permute(1, 0, 2).contiguous(), "valid": res["status"] <= 1,
+                  "status": res["status"], "duration": res["duration"], "n_samples": res["n_samples"], "t": res["t"], "x": res["x"]}
+        if one:
+            detail = {k: (v[:, 0] if k in ("samples", "velocity") else v[0]) for k, v in detail.items()}
+        return detail
+
     def get_carried_clearance(self, qpos=None, attached_entity=None, ee_link_name=None, grasp_pose=None, attached_links=None, envs_idx=None,
                               with_entity=None, ignore_entities=(), max_distance: float = 1.0, self_collision=None) -> dict:
         """{clearance (R,), self_clearance (R,)} of ONE configuration with the carried object of plan_path() attached: `qpos` (R, n) in
@@ -1394,6 +1527,11 @@ class SceneView:
 
     def step(self) -> None:
         self._mir.step(1)
+
+    @property
+    def dt(self) -> float:
+        """``scene.dt`` (a Genesis name): the step of the simulation in seconds, as the scene was built"""
+        return float(self._mir.spec.opt.dt)
 
     def add_sensor(self, options):
         """``scene.add_sensor(gs.sensors.Lidar(...))``: a ray-cast range sensor (tasks/sensors.py: Raycaster / Lidar / DepthCamera options)

@@ -942,6 +942,79 @@ int mir_path_clearance_carry(MirHandle h, const MirPlanQuery* q, const MirSelfQu
                              float* row_self_min /* (R), NULL without sq */, int32_t* row_first_blocked /* (R) */,
                              float* grasp_used /* (R,7) nullable */, void* stream);
 
+/* ---- time parameterisation: a joint path as targets at a chosen sample period, within velocity, acceleration and torque limits ----
+ * mir_plan_path ends at geometry: W waypoints at equal arc length.  mir_retime_path says how long such a path takes and turns it into
+ * targets: time-optimal path parameterisation by reachability analysis (TOPP-RA; Pham & Pham 2018) with the interpolation collocation
+ * scheme on the caller's waypoints, R rows in one launch, one wave64 per row (mir_retime.hip).  Per row:
+ * Inputs.  A path P (K, D), K >= 2, D <= 16; vmax[D], amax[D] (the query: shared by the rows); max_path_speed in waypoints per second;
+ *   E >= 0 extra rows per waypoint ea, eb, elo, ehi (R, K, E) on the device, 2 (D + E) <= 64; a sample period dt and a capacity T.
+ * 1. Compaction.  Waypoint k is dropped when all D values compare equal to the last kept waypoint (a failed mir_plan_path row holds
+ *   its start W times); the kept ones are Q_0 .. Q_{M-1}, and extra rows of dropped waypoints are ignored.  In this order: a value of
+ *   the row's path (anywhere) or of its extra rows at a kept waypoint that is not finite: NOT_FINITE.  M = 1: NO_MOTION (duration 0,
+ *   one sample; no error).  M = 2: TOO_FEW_WAYPOINTS (a constant path acceleration per interval cannot go rest to rest over one
+ *   interval).  An extra row at a kept waypoint without lo < 0 < hi: INFEASIBLE (rest must be strictly feasible).
+ * 2. Geometry, path parameter s = waypoint index.  d_i = Q_{i+1} - Q_i; c_0 = c_{M-1} = 0, m_0 = d_0, m_{M-1} = d_{M-2}; inside,
+ *   c_i = d_i - d_{i-1} and m_i = (d_i + d_{i-1}) / 2.
+ * 3. Speed cap, x = (ds/dt)^2.  cap_i = min(max_path_speed^2, (vmax_j / |d_ej|)^2) over the adjacent intervals e in {i-1, i} and the
+ *   dofs j with d_ej != 0.  Positions are piecewise linear in s (9.) and x is linear in s within an interval, so the velocity limit
+ *   holds at every instant, not only at the waypoints.
+ * 4. Rows at gridpoint i, lo <= alpha u + beta x <= hi with u = d2s/dt2: D acceleration rows (m_ij, c_ij, -amax_j, amax_j), then the
+ *   E extra rows as given.
+ * 5. Interval i: (x, u) satisfies the rows of gridpoint i at (x, u), those of gridpoint i+1 at (x + 2u, u) -- the row
+ *   (alpha' + 2 beta', beta', lo', hi') in (u, x) -- and 0 <= x + 2u <= Kmax_{i+1}.
+ * 6. Backward.  Kmax_{M-1} = 0; for i = M-2 .. 1, Kmax_i = the largest x in [0, cap_i] for which a u exists under 5.; Kmax_0 = 0.
+ * 7. Forward.  x_0 = 0; u_i = the largest u the rows of 5. allow at x_i with x_i + 2u <= Kmax_{i+1}, raised to -x_i / 2 if rounding
+ *   put it below; x_{i+1} = max(x_i + 2 u_i, 0), x_{M-1} = 0.
+ * 8. Times.  t_0 = 0, t_{i+1} = t_i + 2 / (sqrt x_i + sqrt x_{i+1}); a zero denominator: INFEASIBLE.  duration = t_{M-1}.
+ * 9. Samples.  n_samples = ceil(duration / dt) + 1 (at most 2 000 000 001); sample n at tau = n dt.  Sample 0 carries the bits of P_0;
+ *   a sample with tau >= duration the bits of P_{K-1} and velocity 0; else, in the interval t_i <= tau < t_{i+1}, with
+ *   delta = tau - t_i and u_i = (x_{i+1} - x_i) / 2: f = clamp(sqrt(x_i) delta + u_i delta^2 / 2, 0, 1), q = Q_i + f d_i,
+ *   velocity = d_i (sqrt(x_i) + u_i delta).  All T samples of a row are written.  With a sample array given and n_samples > T the row is
+ *   TRUNCATED: x, t and duration stay valid and the first T samples are written.  A row with another failure status writes P_0 to
+ *   every sample, zeros to x and t, duration 0 and n_samples 1: following it keeps the arm where it is.
+ * The LPs of 6. and 7. have two variables and at most 66 constraints: a lane holds one row (the lower D + E lanes the left collocation,
+ *   the upper D + E the right one) as bounds on u that are linear in x; 6. is a bisection on x with 32 halvings (a wave minimum and a
+ *   wave maximum each), 7. one wave minimum.  A row with alpha == 0 bounds x alone.  Every loop is bounded by K, T or a constant.
+ * Outputs use the caller's indexing: x, t (R, K), a dropped waypoint repeats the values of the waypoint kept before it; duration (R);
+ *   status (R): MIR_RETIME_*; n_samples (R); samples, sample_vel (R, T, D), each nullable.  K <= MIR_RETIME_MAX_WAYPOINTS: the row's
+ *   Kmax, x and t live in LDS.  The call reads no state and changes nothing a later call can see; n_rows = 0 returns MIR_OK.
+ * MIR_E_INVALID: a NULL handle, query, paths or x / t / duration / status / n_samples; struct_size != sizeof(MirRetimeQuery); K < 2,
+ *   D outside 1 .. 16, E < 0, E > 0 with a NULL extra array, n_rows < 0, num_samples < 0; an unknown flag bit; a vmax, amax, dt or
+ *   max_path_speed that is not finite and > 0; samples or sample_vel with num_samples < 1; a call while a mir_step_begin is open.
+ *   MIR_E_CAPACITY: 2 (D + E) > 64; K > MIR_RETIME_MAX_WAYPOINTS; R x T x D beyond 2^31 - 1.  None of them launches anything, and
+ *   mir_last_error() names the entry point.
+ * What it does not do.  The acceleration and torque limits are collocated: they bound the path acceleration averaged over each
+ *   waypoint-to-waypoint traversal, as in TOPP-RA and MoveIt's parameterisers.  The samples stay exactly on the polyline that was
+ *   collision-checked, so a dof's velocity changes at a kink within one sample: the finite difference of the samples keeps vmax, their
+ *   second difference can exceed amax many times over at a kink (finer waypoints shrink that).  No blending of corners, no jerk limit,
+ *   no start or end speed other than rest, no contact forces in the torque rows (those are the caller's extra rows).
+ * (Added struct and entry point: MIR_VERSION and every other struct and entry point stay as they are.) */
+#define MIR_RETIME_MAX_WAYPOINTS 2048
+#define MIR_RETIME_OK 0
+#define MIR_RETIME_NO_MOTION 1
+#define MIR_RETIME_TOO_FEW_WAYPOINTS 2
+#define MIR_RETIME_NOT_FINITE 3
+#define MIR_RETIME_INFEASIBLE 4
+#define MIR_RETIME_TRUNCATED 5
+typedef struct MirRetimeQuery {
+  int32_t  struct_size;    /* = sizeof(MirRetimeQuery) */
+  int32_t  n_dofs;         /* D: 1 .. 16 */
+  int32_t  n_extra;        /* E >= 0 extra rows per waypoint, 2 (D + E) <= 64 */
+  int32_t  num_waypoints;  /* K: 2 .. MIR_RETIME_MAX_WAYPOINTS */
+  int32_t  num_samples;    /* T >= 0: the capacity of samples / sample_vel per row */
+  uint32_t flags;          /* 0; unknown bits are MIR_E_INVALID */
+  float    dt;             /* the sample period, s */
+  float    max_path_speed; /* waypoints per second */
+  float    vmax[16];       /* per dof, finite and > 0 (the first D are read) */
+  float    amax[16];
+} MirRetimeQuery;
+int mir_retime_query_sizeof(void);
+int mir_retime_path(MirHandle h, const MirRetimeQuery* q, int n_rows, const float* paths /* (R,K,D) device */,
+                    const float* ea, const float* eb, const float* elo, const float* ehi /* (R,K,E) device, NULL when E == 0 */,
+                    float* x /* (R,K) */, float* t /* (R,K) */, float* duration /* (R) */, int32_t* status /* (R) */,
+                    int32_t* n_samples /* (R) */, float* samples /* (R,T,D) nullable */, float* sample_vel /* (R,T,D) nullable */,
+                    void* stream);
+
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
