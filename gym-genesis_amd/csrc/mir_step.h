@@ -100,6 +100,11 @@ constexpr int step_cpl(int k) { return (k == STEP_LIST48 || k == STEP_HEAVY48 ||
 constexpr bool step_big(int k) { return step_cpl(k) > 1; }
 // ... then the outputs, then the action-independent half of the next step
 constexpr bool step_fused_next_pre(int k) { return k == STEP_LIST48; }
+// the kinds that run only in contact-rich steps (an env above 16 points in the batch): their arithmetic is dominated by the contact
+// rows, where packed fp32 pairs pay (STEP_POST48 57.5 us packed / 60.8 us not, STEP_HEAVY48 93.9 / 97.2, STEP_ROTATED_LIST 49.8 / 51.0 on
+// the reference's expert and the scripted grasp), so they are compiled with the SLP vectoriser on; every other kind without it
+// (STEP_ROTATED on the headline 21.1 / 20.8 us).  Build flags only: the bits are the same either way.
+constexpr bool step_packed(int k) { return step_big(k) || k == STEP_ROTATED_LIST; }
 // two passes of the body's loop: the second half of this step, then the first half of the next one ...
 constexpr bool step_rotated(int k) { return k == STEP_ROTATED || k == STEP_POST48 || k == STEP_ROTATED_LIST; }
 // ... of which only the first is taken

@@ -294,7 +294,7 @@ __attribute__((amdgpu_waves_per_eu(step_wpe_min(VARIANT), step_wpe_max(VARIANT))
 
 }  // namespace
 
-#ifdef MIR_STEP_CONVEX_TU
+#if defined(MIR_STEP_CONVEX_TU) && !defined(MIR_STEP_PACKED_TU)
 // debug aid: the lane-private convex narrowphase on n pairs given directly, one thread per pair.
 //   in  (n, 22): type1, size1[3], pos1[3], quat1[4] (wxyz), type2, size2[3], pos2[3], quat2[4]
 //   out (n, 8):  hit (0/1), pos[3], dist, normal[3]
@@ -324,10 +324,22 @@ extern "C" int mir_launch_debug_convex(const float* in, float* out, int n, hipSt
 // (mir_step_convex.hip = this file compiled with MIR_STEP_CONVEX_TU and WITHOUT -fno-signed-zeros: together with
 // -ffp-contract=on that flag miscompiles the support-mapping selects of mir_convex.h -- box pairs lose contacts -- while the
 // planes-and-boxes kernels gain 1 % from it).
+// Each of the two sources is compiled twice, and every kind is instantiated in ONE of the two objects: the kinds of the contact-rich
+// steps (step_packed, mir_step.h) in the MIR_STEP_PACKED_TU object, which is built with the SLP vectoriser on, all others in the
+// object built with -fno-slp-vectorize (Makefile: STEP16FLAGS / STEP16PACKED).  The entry points below hand a kind to its object.
+#ifdef MIR_STEP_PACKED_TU
+constexpr bool kPackedTU = true;
+#else
+constexpr bool kPackedTU = false;
+#endif
 template <int KIND, int FEAT>
 static int launch_kind(const StepArgs& a, int blocks, hipStream_t stream) {
-  hipLaunchKernelGGL((mir_step_kernel<KIND, FEAT, step_cpl(KIND)>), dim3(blocks), dim3(step_block(KIND)), 0, stream, a);
-  return (int)hipGetLastError();
+  if constexpr (step_packed(KIND) == kPackedTU) {
+    hipLaunchKernelGGL((mir_step_kernel<KIND, FEAT, step_cpl(KIND)>), dim3(blocks), dim3(step_block(KIND)), 0, stream, a);
+    return (int)hipGetLastError();
+  } else {
+    return (int)hipErrorInvalidValue;  // (not instantiated in this object: the entry points never send it here)
+  }
 }
 // THE dispatch: kind -> instantiation, for the FEAT mask of the caller's translation unit.  A kind that a mask does not carry is an
 // error.  (STEP_POST has no collision code in it: one instantiation, FEAT_PLAIN, serves every scene; STEP_FULL stays generic.)
@@ -352,16 +364,28 @@ static int launch_feat(const StepArgs& a, int kind, int blocks, hipStream_t stre
   return (int)hipErrorInvalidValue;
 }
 #ifdef MIR_STEP_CONVEX_TU
+#ifdef MIR_STEP_PACKED_TU
+extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_convex_packed(const StepArgs* args, int kind, hipStream_t stream) {
+  const StepArgs& a = *args;
+#else
+extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_convex_packed(const StepArgs* args, int kind, hipStream_t stream);
 extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_convex(const StepArgs* args, int kind, hipStream_t stream) {
   const StepArgs& a = *args;
+  if (step_packed(kind)) return mir_launch_step_convex_packed(args, kind, stream);
+#endif
   const int blocks = (a.B + EPB - 1) / EPB;
   // the headline scene's instantiation (FEAT_SPEC: mir_create found SpecPick::matches); the everything-variant stays generic
   if ((a.features & FEAT_SPEC) && kind != STEP_FULL && kind != STEP_SENSE48) return launch_feat<FEAT_CONVEX | FEAT_SPEC>(a, kind, blocks, stream);
   if (a.features & FEAT_SAP) return launch_feat<FEAT_CONVEX | FEAT_SAP>(a, kind, blocks, stream);  // sweep-and-prune scenes carry the convex code too
   return launch_feat<FEAT_CONVEX>(a, kind, blocks, stream);
 }
+#elif defined(MIR_STEP_PACKED_TU)
+extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_plain_packed(const StepArgs* args, int kind, hipStream_t stream) {
+  return launch_feat<FEAT_PLAIN>(*args, kind, (args->B + EPB - 1) / EPB, stream);
+}
 #else
 extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_convex(const StepArgs* args, int kind, hipStream_t stream);
+extern "C" __attribute__((visibility("hidden"))) int mir_launch_step_plain_packed(const StepArgs* args, int kind, hipStream_t stream);
 extern "C" int mir_launch_step(const StepArgs* args, hipStream_t stream) {
   const StepArgs& a = *args;
   const int blocks = (a.B + EPB - 1) / EPB;
@@ -380,6 +404,7 @@ extern "C" int mir_launch_step(const StepArgs* args, hipStream_t stream) {
     kind = single ? STEP_SINGLE : (plain_loop ? STEP_LOOP : STEP_FULL);
   }
   if (a.features && !step_post_only(kind)) return mir_launch_step_convex(&a, kind, stream);
+  if (step_packed(kind)) return mir_launch_step_plain_packed(&a, kind, stream);
   return launch_feat<FEAT_PLAIN>(a, kind, blocks, stream);
 }
 #endif
