@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirCarryQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_carry_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
+from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirCartQuery, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirCarryQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_carry_query, make_cart_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -168,6 +168,10 @@ def load_library() -> C.CDLL:
     lib.mir_retime_query_sizeof.restype = C.c_int
     lib.mir_retime_path.argtypes = [vp, C.POINTER(MirRetimeQuery), i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_retime_path.restype = C.c_int
+    lib.mir_cart_query_sizeof.restype = C.c_int
+    lib.mir_cartesian_path.argtypes = [vp, C.POINTER(MirCartQuery), C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp,
+                                       vp, i32, vp, vp, vp, C.POINTER(MirIkOptions), vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_cartesian_path.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
@@ -194,6 +198,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCarryQuery (rebuild the library)")
     if lib.mir_retime_query_sizeof() != C.sizeof(MirRetimeQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRetimeQuery (rebuild the library)")
+    if lib.mir_cart_query_sizeof() != C.sizeof(MirCartQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCartQuery (rebuild the library)")
     if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
     _lib = lib
@@ -1102,6 +1108,52 @@ class MirScene(StepHelpers):
                                                          self._stream()))
         if R > 0:
             self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
+        return out
+
+    def cartesian_path(self, probes, links, dof_qadr, link_body: int, target_pos, target_quat=None, env_idx=None, qpos_start=None,
+                       max_pos_step: float = 0.01, max_rot_step: float = 0.05, jump_threshold: float = 0.5, max_points: int = 256,
+                       num_waypoints: int = 0, ignore_collision: bool = False, resolution: float = 0.05, margin: float = 0.0,
+                       max_distance: float = 1.0, skip_geoms=0, self_model=None, carry=None, **ik_options) -> dict:
+        """mir_cartesian_path: for the envs `env_idx` (None: all), ONE launch takes the body `link_body` from where it is at
+        `qpos_start` ((R, nq) full rows; None: the current state) along the straight segments to `target_pos` (R, K, 3) -- with
+        `target_quat` (R, K, 4) wxyz the orientation is interpolated along the shorter arc, without it it is free -- by inverse
+        kinematics at samples at most `max_pos_step` m and `max_rot_step` rad apart, each seeded with the one before; a sample whose IK
+        does not converge, that moves a planned dof by more than `jump_threshold`, or whose edge from the sample before is not clear
+        (the sphere model, `resolution`, `margin`, `skip_geoms`, `self_model` and `carry` = dict(body, link) exactly as in
+        path_clearance(); the grasp is taken from the start row) ends the row, which keeps what it achieved (include/mirigid.h has the
+        rule).  Only the planned dofs `dof_qadr` on the chain to the link move.  `ik_options`: those of inverse_kinematics().
+        -> dict of fresh device tensors: points (R, P, D) with P = max_points (the start, the accepted samples, then the last one
+        repeated), n_points (R,) int32, fraction (R,) = accepted samples / all samples, status (R,) int32 (spec.CART_STATUS), stats
+        (R, 4) int32: IK iterations, configurations checked, samples S, the segment that failed or -1; with num_waypoints = W >= 2 also
+        path (R, W, D): the points resampled at equal steps of their index.  The call changes nothing a later call can see."""
+        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
+        D = int(qa.shape[0])
+        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
+        tp = torch.as_tensor(target_pos, device=self.device).to(torch.float32).contiguous()
+        if tp.dim() != 3 or tp.shape[0] != R or tp.shape[2] != 3 or tp.shape[1] < 1:
+            raise ValueError(f"target_pos must be ({R}, K >= 1, 3), got {tuple(tp.shape)}")
+        K = int(tp.shape[1])
+        tq = None
+        if target_quat is not None:
+            tq = torch.as_tensor(target_quat, device=self.device).to(torch.float32).contiguous()
+            if tuple(tq.shape) != (R, K, 4):
+                raise ValueError(f"target_quat must be ({R}, {K}, 4), got {tuple(tq.shape)}")
+        P, W = int(max_points), int(num_waypoints)
+        q = make_cart_query(link_body, K, P, W, max_pos_step, max_rot_step, jump_threshold)
+        pq = make_plan_query(N, D, ignore_collision=ignore_collision, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
+        cq = None if carry is None else make_carry_query(carry["body"], carry["link"])
+        o = self._ik_options(ik_options)
+        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        out = {"points": new(max(P, 0), D), "n_points": new(dtype=torch.int32), "fraction": new(), "status": new(dtype=torch.int32),
+               "stats": new(4, dtype=torch.int32)}
+        if W > 0:
+            out["path"] = new(W, D)
+        if R > 0:   # (without rows there is nothing to point at)
+            self._check(self.lib.mir_cartesian_path(self.h, C.byref(q), C.byref(pq), None if sq is None else C.byref(sq), None if cq is None else C.byref(cq),
+                                                    _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p), qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
+                                                    _ptr(qpos_start), _ptr(tp), _ptr(tq), C.byref(o), _ptr(out["points"]), _ptr(out["n_points"]),
+                                                    _ptr(out["fraction"]), _ptr(out["status"]), _ptr(out.get("path")), _ptr(out["stats"]), self._stream()))
+            self.cart_launches = self.__dict__.get("cart_launches", 0) + 1
         return out
 
     def retime_path(self, paths, vmax, amax, dt, num_samples: int = 0, max_path_speed=None, extra=None, velocity: bool = False) -> dict:

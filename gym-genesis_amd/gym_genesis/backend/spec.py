@@ -594,6 +594,36 @@ def make_retime_query(n_dofs: int, num_waypoints: int, vmax, amax, dt: float, nu
     return q
 
 
+CART_STATUS = {0: "OK", 2: "START_IN_COLLISION", 7: "START_IN_SELF_COLLISION", 16: "TOO_MANY_POINTS", 17: "NOT_FINITE", 18: "IK_FAILED",
+               19: "JOINT_JUMP", 20: "BLOCKED", 21: "BLOCKED_SELF"}   # mir_cartesian_path: MIR_PLAN_* for the start, MIR_CART_* (include/mirigid.h)
+CART_TOO_MANY_POINTS, CART_NOT_FINITE, CART_IK_FAILED, CART_JOINT_JUMP, CART_BLOCKED, CART_BLOCKED_SELF = range(16, 22)
+
+
+class MirCartQuery(C.Structure):
+    """include/mirigid.h: MirCartQuery (mir_cartesian_path)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("link_body", C.c_int32),
+        ("num_targets", C.c_int32),
+        ("max_points", C.c_int32),
+        ("num_waypoints", C.c_int32),
+        ("flags", C.c_uint32),
+        ("max_pos_step", C.c_float),
+        ("max_rot_step", C.c_float),
+        ("jump_threshold", C.c_float),
+    ]
+
+
+def make_cart_query(link_body: int, num_targets: int, max_points: int = 256, num_waypoints: int = 0, max_pos_step: float = 0.01,
+                    max_rot_step: float = 0.05, jump_threshold: float = 0.5) -> MirCartQuery:
+    """link_body: the body that follows the line; steps in metres / radians between two samples; jump_threshold per sample and joint."""
+    q = MirCartQuery()
+    q.struct_size = C.sizeof(MirCartQuery)
+    q.link_body, q.num_targets, q.max_points, q.num_waypoints, q.flags = int(link_body), int(num_targets), int(max_points), int(num_waypoints), 0
+    q.max_pos_step, q.max_rot_step, q.jump_threshold = float(max_pos_step), float(max_rot_step), float(jump_threshold)
+    return q
+
+
 IK_DEFAULTS = dict(max_iters=20, respect_joint_limit=1, damping=0.05, pos_tol=5e-4, rot_tol=5e-3, max_step=0.5)
 
 RENDER_PER_ENV, RENDER_GLOBAL = 0, 1

@@ -968,6 +968,64 @@ class EntityView:
                                        self_margin=self_margin, attached_entity=attached_entity, ee_link_name=ee_link_name, grasp_pose=grasp_pose,
                                        attached_links=attached_links) < float(margin)
 
+    # ---- straight-line end-effector paths (MirScene.cartesian_path / mir_cartesian_path): the approach, the lift and the place of a
+    # grasp.  The name and the arguments are this package's own (MoveIt: computeCartesianPath): parity with Genesis is unpinned.
+    def plan_cartesian_path(self, link, pos, quat=None, qpos_start=None, envs_idx=None, max_step=0.01, max_rot_step=0.05, jump_threshold=0.5,
+                            max_points=256, num_waypoints=None, margin=0.0, ignore_collision=False, with_entity=None, ignore_entities=(),
+                            self_collision=None, self_margin=0.0, attached_entity=None, ee_link_name=None, grasp_pose=None, attached_links=None,
+                            return_fraction=False, return_detail=False, **ik_options):
+        """``robot.plan_cartesian_path(hand, pos=(R, 3), quat=(R, 4))`` -> (W, R, n): waypoints in this entity's dof order, in the layout
+        plan_path() returns (so they go into retime_path, get_path_clearance and control_dofs_position unchanged), along which `link` (a
+        LinkView or a local link index) moves on a STRAIGHT LINE from where it is at `qpos_start` ((R, n); None: the current state) to
+        `pos` -- (R, 3), or (R, K, 3) for a polyline of K segments -- turning along the shorter arc to `quat` ((R, 4) / (R, K, 4) wxyz, or
+        one quaternion for all; None: the orientation is free).  ONE launch for all rows (MirScene.cartesian_path / mir_cartesian_path,
+        where the rule is written down): inverse kinematics at samples at most `max_step` m and `max_rot_step` rad apart, each seeded
+        with the one before; a sample whose IK does not converge (`ik_options`: those of inverse_kinematics), that moves a joint by more
+        than `jump_threshold`, or whose edge from the sample before is in collision ends the row, which keeps the samples it achieved.
+        `num_waypoints` = W: the accepted samples resampled at equal steps of their index; None: the dense samples themselves, W =
+        `max_points` (the capacity: more samples than that and the row does not move), the last accepted one repeated behind the row's
+        own count -- retime_path drops the repeats.  The collision keywords (`margin`, `ignore_collision`, `with_entity`,
+        `ignore_entities`, `self_collision`, `self_margin`, `attached_entity`, `ee_link_name`, `attached_links`) mean what they mean in
+        plan_path(); the carried object's grasp is where the object is at the start (`grasp_pose` must be None).
+        return_fraction=True -> (path, fraction (R,)): the share of the line each row achieved, 1 = all of it.  return_detail=True -> a
+        dict with path, fraction, valid (R,) = fraction is 1, status (R,) int32 (spec.CART_STATUS), points (R, P, n), n_points (R,)
+        and stats (R, 4).  On an unbatched task every result comes without its env axis.
+        What it does not do: no escape from a blocked line (that is plan_path's job), no null-space objective, one link, no axis
+        masks; clearance between two samples is as coarse as the planner's edge rule."""
+        if grasp_pose is not None:
+            raise NotImplementedError("plan_cartesian_path: the grasp is taken from where the attached entity is at the start (mir_cartesian_path "
+                                      "has no grasp rows); grasp_pose must be None")
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "plan_cartesian_path", self_collision, self_margin,
+                                  attached_entity, ee_link_name, None, attached_links)
+        if getattr(self._mir, "cartesian_path", None) is None:
+            raise NotImplementedError("this scene has no Cartesian paths (MirScene.cartesian_path / mir_cartesian_path)")
+        dev = self._mir.device
+        p = torch.as_tensor(pos, device=dev).to(torch.float32)
+        if p.dim() <= 2:
+            p = p.reshape(R, 1, 3)
+        if p.dim() != 3 or p.shape[0] != R or p.shape[2] != 3:
+            raise ValueError(f"pos must be ({R}, 3) or ({R}, K, 3), got {tuple(p.shape)}")
+        K = int(p.shape[1])
+        q = None
+        if quat is not None:
+            q = torch.as_tensor(quat, device=dev).to(torch.float32)
+            q = q.reshape(1, 1, 4).expand(R, K, 4) if q.numel() == 4 else q.reshape(R, K, 4)
+        if "carry" in args:
+            args["carry"] = dict(body=args["carry"]["body"], link=args["carry"]["link"])
+        W = None if num_waypoints is None else int(num_waypoints)
+        r = self._mir.cartesian_path(link_body=self._link_body(link), target_pos=p.contiguous(), target_quat=None if q is None else q.contiguous(),
+                                     max_pos_step=float(max_step), max_rot_step=float(max_rot_step), jump_threshold=float(jump_threshold),
+                                     max_points=int(max_points), num_waypoints=0 if W is None else W, ignore_collision=bool(ignore_collision),
+                                     margin=float(margin), max_distance=max(1.0, 2.0 * float(margin)), **args, **ik_options)
+        path = (r["points"] if W is None else r["path"]).permute(1, 0, 2).contiguous()
+        detail = {"path": path, "fraction": r["fraction"], "valid": r["status"] == 0, "status": r["status"], "points": r["points"],
+                  "n_points": r["n_points"], "stats": r["stats"]}
+        if self.__dict__.get("unbatched"):   # (an unbatched task: no env axis anywhere)
+            detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
+        if return_detail:
+            return detail
+        return (detail["path"], detail["fraction"]) if return_fraction else detail["path"]
+
     # ---- time parameterisation (MirScene.retime_path / mir_retime_path): what stands between plan_path and control_dofs_position.
     # get_dofs_force_range is a Genesis name (RigidEntity); retime_path is this package's own: parity with Genesis is unpinned.
     def get_dofs_force_range(self, dofs_idx_local=None):

@@ -1015,6 +1015,87 @@ int mir_retime_path(MirHandle h, const MirRetimeQuery* q, int n_rows, const floa
                     int32_t* n_samples /* (R) */, float* samples /* (R,T,D) nullable */, float* sample_vel /* (R,T,D) nullable */,
                     void* stream);
 
+/* ---- Cartesian paths: a link follows a straight-line polyline, collision-checked, in one launch -------------
+ * `robot.plan_cartesian_path(link, pos, quat)`: the approach, the lift and the place of a grasp, where the hand itself must follow a
+ * line (MoveIt: computeCartesianPath(eef_step, jump_threshold) -> fraction).  For R rows ONE launch (mir_cart.hip, one wave64 per row)
+ * takes each row's link along K straight segments: inverse kinematics at every sample, seeded with the sample before, a joint-jump
+ * test and the planner's edge check between consecutive samples.  It reads the state (or the start rows) and the compiled model and
+ * writes only its outputs.  Parity with Genesis and MoveIt is unpinned: the rule is this library's own, fixed here to the operand.
+ * Arguments.  pq supplies the clearance side exactly as for mir_path_clearance (n_probes, n_dofs, resolution, margin, max_distance,
+ *   flags, skip_geoms; its planner fields are ignored); sq and cq, both nullable, mean what they mean in mir_plan_path_self and
+ *   mir_plan_path_carry (the grasp transform is taken from the start row).  probes, probe_link, dof_qadr (D <= 16), env_idx, n_rows,
+ *   clamping and qpos_start are those of mir_plan_path.  opt: the options of mir_inverse_kinematics (NULL: its defaults; pos_tol and
+ *   rot_tol must be > 0).  target_pos (R, K, 3); target_quat (R, K, 4) wxyz or NULL: the link keeps no orientation target and the
+ *   rotation part of the IK error is dropped.
+ * Per row:
+ * 1. Set-up.  a0 = the planned dofs of the start row.  The chain world -> link_body is that of mir_inverse_kinematics (fixed bodies
+ *   folded, <= 16 elements).  A joint MOVES when it is a scalar joint on the chain and a planned dof; every other entry keeps its
+ *   start bits.  X_0 = (p_0, q_0), the link's pose at a0 by the chain's forward kinematics.  p_k = target_pos[k - 1]; q_k =
+ *   target_quat[k - 1] normalised by the routine used for free-joint quaternions (k = 1 .. K).
+ * 2. NOT_FINITE: a NaN or an infinity in any target of the row, or a target quaternion whose four squares sum to less than 1e-30 or
+ *   to no finite float32.
+ * 3. Sample counts.  dp_k = sqrt(dx^2 + dy^2 + dz^2) of p_k - p_{k-1}.  d_k = conj(q_{k-1}) q_k, negated when d_k.w < 0 (the shorter
+ *   arc; the antipodal case d_k.w == 0 is NOT negated: the half turn about +d_k.xyz); sn_k = |d_k.xyz|, ang_k = 2 atan2(sn_k, d_k.w)
+ *   (0 without target_quat).  n_k = max(1, ceil(max(dp_k / max_pos_step, ang_k / max_rot_step))), at most 2^30 (a quotient that is
+ *   not finite counts as 2^30).  Every quotient here and below is the planner's: a float32 division refined by one Newton step.
+ *   S = sum n_k.  S + 1 > max_points: TOO_MANY_POINTS.
+ * 4. Start.  clear(a0) of mir_plan_path: its scene test fails: MIR_PLAN_START_IN_COLLISION; with sq, its self test fails:
+ *   MIR_PLAN_START_IN_SELF_COLLISION.  In 2. - 4. nothing moves: n_points = 1, fraction = 0.
+ * 5. Samples, in order: segment k = 1 .. K, i = 1 .. n_k, from the last accepted configuration c (a0 at first).
+ *   Target.  i == n_k: (p_k, q_k) themselves.  Else t = i / n_k, p = p_{k-1} + t (p_k - p_{k-1}), q = q_{k-1} (cos h, sin h d_k.xyz /
+ *     sn_k) with h = t ang_k / 2; sn_k <= 1e-9 (the zero-angle case): q = q_{k-1}.
+ *   IK.  The iteration of mir_inverse_kinematics (below) word for word -- accept / reject / stall, the lambda^2 schedule (from
+ *     damping^2 at every sample), the max_step scaling, the limit clamp, max_iters -- on the moving joints, seeded with c.  Its result
+ *     q_acc gives the candidate c' (the moving joints from q_acc, the other planned dofs from a0).  |e_pos| < pos_tol and |e_rot| <
+ *     rot_tol do not both hold at q_acc: IK_FAILED.
+ *   Jump.  max_j |c'_j - c_j| > jump_threshold over the planned dofs: JOINT_JUMP.
+ *   Collision.  edge(c, c') of mir_plan_path: its samples in order, each by the scene test and then, with sq and only when the scene
+ *     test holds, the self test.  The first test that fails decides: the scene test: BLOCKED; the self test: BLOCKED_SELF (the tie
+ *     rule: within one configuration the scene test is asked first, so a configuration that fails both is BLOCKED).
+ *   The first failure ends the row, which keeps what it achieved; otherwise c' is accepted: point a = the count of accepted samples.
+ * 6. Outputs.  points (R, P, D): points[0] = a0's bits, points[a] = accepted sample a, and every point behind n_points = a + 1 repeats
+ *   the last accepted one (what mir_retime_path compacts and mir_path_clearance accepts).  fraction = a / S (float32, refined).
+ *   status (R): MIR_PLAN_OK, the two start statuses or MIR_CART_*.  path (R, W, D), with num_waypoints = W >= 2: waypoint 0 = the bits
+ *   of points[0], waypoint W - 1 those of points[n_points - 1]; else u = (w / (W - 1)) (n_points - 1), i0 = min(floor(u), n_points -
+ *   2), t = u - i0, waypoint = points[i0] + t (points[i0 + 1] - points[i0]); n_points == 1: the start W times.  stats (R, 4): IK
+ *   iterations summed over the samples, configurations checked for clearance, S (saturated at 2^31 - 1), the segment (0-based) whose
+ *   sample failed or -1.
+ * Every loop is bounded by K, P, W, max_iters or the 4096 samples of the edge rule; no input can keep a wave running.
+ * MIR_E_INVALID: a NULL handle, q, pq, probes, dof_qadr, target_pos, points, n_points, fraction or status; struct_size != sizeof of
+ *   any query given; K < 1, P < 2, W < 0 or W == 1, W >= 2 without path or path with W == 0; an unknown flag bit; a step or the
+ *   threshold not finite or <= 0; bad IK options; a link out of range or that hangs off a free body; no moving joint; everything
+ *   mir_path_clearance (and the _self / _carry forms, when sq / cq are given) refuses.  MIR_E_CAPACITY: R x max(P, W) x D beyond
+ *   2^31 - 1; a chain of more than 16 elements.  None of them launches anything; n_rows == 0 returns MIR_OK without a launch.
+ * What it does not do.  No escape from a blocked line (that is mir_plan_path's job); no null-space objective or redundancy resolution
+ *   beyond the damped least-squares step; one link, no axis masks; clearance between two samples is as coarse as the edge rule.
+ * (Added struct and entry point: MIR_VERSION and every other struct and entry point stay as they are.) */
+#define MIR_CART_TOO_MANY_POINTS 16
+#define MIR_CART_NOT_FINITE 17
+#define MIR_CART_IK_FAILED 18
+#define MIR_CART_JOINT_JUMP 19
+#define MIR_CART_BLOCKED 20
+#define MIR_CART_BLOCKED_SELF 21
+typedef struct MirCartQuery {
+  int32_t  struct_size;    /* = sizeof(MirCartQuery) */
+  int32_t  link_body;      /* the link that follows the line */
+  int32_t  num_targets;    /* K >= 1 */
+  int32_t  max_points;     /* P >= 2: the capacity of points per row */
+  int32_t  num_waypoints;  /* W: 0, or >= 2 with path */
+  uint32_t flags;          /* 0; unknown bits are MIR_E_INVALID */
+  float    max_pos_step;   /* > 0, metres between two samples */
+  float    max_rot_step;   /* > 0, radians between two samples */
+  float    jump_threshold; /* > 0, radians or metres per sample and joint */
+} MirCartQuery;
+int mir_cart_query_sizeof(void);
+struct MirIkOptions; /* (defined below, "batched inverse kinematics") */
+int mir_cartesian_path(MirHandle h, const MirCartQuery* q, const MirPlanQuery* pq, const MirSelfQuery* sq /* nullable */,
+                       const MirCarryQuery* cq /* nullable */, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+                       const int64_t* env_idx, int32_t n_rows, const float* qpos_start /* (R,nq) nullable */,
+                       const float* target_pos /* (R,K,3) */, const float* target_quat /* (R,K,4) wxyz, nullable */,
+                       const struct MirIkOptions* opt /* nullable: the IK defaults */, float* points /* (R,P,D) */, int32_t* n_points /* (R) */,
+                       float* fraction /* (R) */, int32_t* status /* (R) */, float* path /* (R,W,D) nullable */,
+                       int32_t* stats /* (R,4) nullable */, void* stream);
+
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
