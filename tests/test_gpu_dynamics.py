@@ -25,6 +25,7 @@ import torch
 import dyn_ref
 import kin_ref
 import orc
+import tree_metrics
 from gym_genesis.backend import models
 from gym_genesis.backend.spec import MirDynQuery, make_dyn_query
 
@@ -83,6 +84,13 @@ def test_parity_with_the_float64_reference(name):
     print(f"\n[dynamics, {name}] max |x - x64| over {B} envs:  " + "   ".join(f"{k}: GPU {e[k]:.3e} port {s['yard'][k]:.3e} allowed {4 * s['yard'][k]:.3e}" for k in OUTS))
     for k in OUTS:
         assert e[k] <= 4.0 * s["yard"][k], (name, k, e[k], s["yard"][k])
+    # ... and per kinematic tree and dof kind (tests/tree_metrics.py): pooled, the arm's yardstick (mass 2e-6, tau 3e-5) is as large as
+    # a cube's whole rotational inertia (3.4e-6) or torque (6.6e-6), so the cube's rotational rows could be wrong by half their size
+    model = s["model"]
+    bad = tree_metrics.report(f"dynamics, {name}, mass", tree_metrics.matrix_blocks(model, got["mass"], s["port"]["mass"], s["ref"]["mass"]))
+    for k in OUTS[1:]:
+        bad += tree_metrics.report(f"dynamics, {name}, {k}", tree_metrics.vector_blocks(model, got[k], s["port"][k], s["ref"][k]))
+    assert not bad, bad
 
 
 @pytest.mark.parametrize("name", ["pick", "stack"])
@@ -221,7 +229,7 @@ def test_through_genesis_env_against_the_reference_on_the_state_read_back():
     worst, yard = dict.fromkeys(keys, 0.0), dict.fromkeys(keys, 0.0)
     m = float(np.float32(spec.body[cube.root].mass))
     frc_lo, frc_hi = (np.array([spec.dof[i].frc_range[j] for i in range(9)]) for j in (0, 1))
-    skipped = 0
+    skipped, worst_rot = 0, 0.0
     for t in range(20):
         env.step(A[20 * t % acts.shape[0]])
         got = dict(mass=robot.get_mass_mat(), bias=robot.get_dofs_bias_force(), tau=robot.inverse_dynamics(qacc), ctrl_force=robot.get_dofs_control_force())
@@ -243,9 +251,16 @@ def test_through_genesis_env_against_the_reference_on_the_state_read_back():
         Mc = cube.get_mass_mat().cpu().numpy()
         assert Mc.shape == (n, 6, 6) and (Mc[:, 0:3, 0:3] == np.float32(m) * np.eye(3, dtype=np.float32)).all(), "the cube's mass block is diag(m, m, m, .)"
         assert (Mc[:, 0:3, 3:6] == 0).all() and (Mc[:, 3:6, 0:3] == 0).all()
+        # the cube's rotational 3 x 3 block against the reference, by its own yardstick (the arm's is as large as the block itself)
+        rot = slice(12, 15)
+        e_rot, y_rot = float(np.abs(Mc[:, 3:6, 3:6] - ref["mass"][:, rot, rot]).max()), float(np.abs(prt["mass"][:, rot, rot] - ref["mass"][:, rot, rot]).max())
+        a_rot = tree_metrics.allowed(y_rot, ref["mass"][:, rot, rot])
+        worst_rot = max(worst_rot, e_rot / a_rot)
+        assert e_rot <= a_rot, (t, e_rot, y_rot, a_rot)
     print("\n[dynamics, GenesisEnv, 20 steps x 8 envs] " + "   ".join(f"{k}: GPU {worst[k]:.3e} port {yard[k]:.3e} allowed {4 * yard[k]:.3e}" for k in keys))
     # a near-limit band is 2e-3 of the force range wide per limit: a stepped state lands in one about once in 250 dof evaluations,
     # and only some of those flip; more than 1 % of the 2 x 20 x 8 x 9 comparisons would be a broken clamp, not rounding
+    print(f"[dynamics, GenesisEnv] the cube's rotational block of mass: worst error / allowed over the steps {worst_rot:.3f}")
     print(f"[dynamics, GenesisEnv] ctrl_force comparisons left out (near a clamp limit AND clamp state differs): {skipped} of {2 * 20 * n * 9}")
     assert skipped <= 0.01 * 2 * 20 * n * 9
     for k in keys:

@@ -31,6 +31,7 @@ import dyn_ref
 import kin_ref
 import orc
 import task_ref
+import tree_metrics
 from gym_genesis.backend import models
 from gym_genesis.backend.spec import MIR_MAX_BODY, MirTaskQuery, make_task_query
 
@@ -126,6 +127,11 @@ def test_parity_with_the_float64_reference(name):
             print(f"[task dynamics, {name}, damping {d}] {key[0]:>10} {str(key[1]):>5}: GPU {e[key]:.3e} port {yard[key]:.3e} allowed {4 * yard[key]:.3e}")
             if not e[key] <= 4.0 * yard[key]:
                 bad.append((name, d, key, e[key], yard[key]))
+        # minv and solve per kinematic tree and dof kind as well (tests/tree_metrics.py): pooled, a cube's rotational block of M^-1 (~3e5)
+        # sets a yardstick of 0.07 .. 0.25 for the arm, whose entries are ~10 and whose own port error is ~1e-5
+        t = f"task dynamics, {name}, damping {d}"
+        bad += tree_metrics.report(f"{t}, minv", tree_metrics.matrix_blocks(s["model"], got["minv"], s["port"][d]["minv"], s["ref"][d]["minv"]))
+        bad += tree_metrics.report(f"{t}, solve", tree_metrics.vector_blocks(s["model"], got["solve"], s["port"][d]["solve"], s["ref"][d]["solve"]))
     assert not bad, bad
 
 

@@ -5,6 +5,7 @@
   * the views (get_jacobian, get_links_pos / quat / vel / ang, link.get_vel / get_ang) on a test double that serves
     `link_kinematics` from the reference;
   * the ctypes mirror of MirKinQuery has the layout a C compiler gives the header's struct.
+The first two also on the synthetic trees of tests/tree_cases.py, every moving body of each.
 """
 import ctypes as C
 import os
@@ -16,6 +17,7 @@ import torch
 
 import kin_ref
 import orc
+import tree_cases
 from fake_scene import OracleScene
 from gym_genesis.backend import models
 from gym_genesis.backend.spec import MIR_MAX_BODY, MirKinQuery, make_kin_query
@@ -24,12 +26,19 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _scene(name):
+    if name in tree_cases.CASES:
+        return tree_cases.build(name)
     sb = models.franka_cube_pick_scene() if name == "pick" else models.franka_cube_stack_scene()
     return sb, sb.build()
 
 
 def _links(sb, name):
-    """hand, one finger, first and last cube"""
+    """hand, one finger, first and last cube; every body of a synthetic tree that has a joint on its path (the tests ask for a link that moves)"""
+    if name in tree_cases.CASES:
+        moves = [False] * len(sb.bodies)
+        for b in range(1, len(sb.bodies)):
+            moves[b] = moves[sb.bodies[b]["parent"]] or sb.bodies[b]["jtype"] != kin_ref.FIXED
+        return [b for b in range(1, len(sb.bodies)) if moves[b]]
     cubes = ["cube"] if name == "pick" else [models.STACK_CUBES[0], models.STACK_CUBES[-1]]
     return [sb.body_index(n) for n in ["hand", "left_finger"] + cubes]
 
@@ -76,7 +85,7 @@ def _pose(o, model, q, link, lp):
     return xp[link] + kin_ref.quat_to_mat(ql) @ np.asarray(lp), ql
 
 
-@pytest.mark.parametrize("scene", ["pick", "stack"])
+@pytest.mark.parametrize("scene", ["pick", "stack", *tree_cases.CASES])
 def test_the_reference_jacobian_equals_central_differences_of_the_oracles_fk(scene):
     """eps = 1e-5 and the bound 1e-8 + a model term, from the errors of a central difference in float64.  Truncation: eps^2 / 6 x the
     third derivative of a pose along one dof, at most the lever arm (< 2 m with the local point) for positions and 1 for orientations:
@@ -117,7 +126,7 @@ def test_the_reference_jacobian_equals_central_differences_of_the_oracles_fk(sce
     print(f"\n[kin, {scene}] analytic Jacobian against central differences (eps {eps:g}): max |J - FD| over the links {worst:.3e}")
 
 
-@pytest.mark.parametrize("scene", ["pick", "stack"])
+@pytest.mark.parametrize("scene", ["pick", "stack", *tree_cases.CASES])
 def test_the_reference_velocity_equals_the_displacement_of_one_oracle_step(scene):
     """One step of the oracle with dt = 1e-6 from a state in free space: the oracle updates qvel, then moves qpos with the NEW qvel (a
     free body: position += dt v, quaternion <- exp(w dt) (x) q).  So (p(q1) - p(q0)) / dt = J(q0) qvel1 + dt / 2 x the second derivative
@@ -132,6 +141,7 @@ def test_the_reference_velocity_equals_the_displacement_of_one_oracle_step(scene
     o = orc.Oracle(spec, 1)
     q0, v0 = kin_ref.random_state(spec, model, 1, seed=4)
     q0, v0 = q0[0].astype(np.float64), v0[0].astype(np.float64)
+    moved = []
     for link in _links(sb, scene):
         lp = (0.03, -0.02, 0.05)
         o.write(orc.F_QPOS, q0)
@@ -152,7 +162,11 @@ def test_the_reference_velocity_equals_the_displacement_of_one_oracle_step(scene
         err = float(np.abs(vel - fd).max())
         print(f"\n[kin, {scene}] link {link}: |J qvel - dp / dt| {err:.3e}, bound {bound:.3e}")
         assert err < bound, (scene, link, err, bound)
-        assert np.abs(vel).max() > 0.05
+        moved.append(float(np.abs(vel).max()))
+        if scene not in tree_cases.CASES:
+            assert np.abs(vel).max() > 0.05
+    # (a synthetic tree is asked link by link, a link under one joint included, whose speed is one random number: the scene must move)
+    assert max(moved) > 0.05 and np.median(moved) > 0.05
 
 
 # ---- the views on a test double -------------------------------------------------------------------------------------------------

@@ -10,6 +10,7 @@ The float64 reference of tests/task_ref.py (the oracle's M and J, combined) is p
   * make_task_query validation and the struct's layout;
   * the EntityView methods on a test double that serves `task_dynamics` from the reference; forward_dynamics / inverse_dynamics
     round trip.
+M minv = I, the consistency of J-bar (or the NaN rule) and the float32 port also on the synthetic trees of tests/tree_cases.py.
 """
 import ctypes as C
 import os
@@ -23,6 +24,7 @@ import dyn_ref
 import kin_ref
 import orc
 import task_ref
+import tree_cases
 from gym_genesis.backend import models
 from gym_genesis.backend.spec import MIR_MAX_BODY, MIR_MAX_DOF, MirTaskQuery, make_task_query
 from test_dyn_cpu import DynScene
@@ -126,6 +128,92 @@ def test_float32_port_agrees_with_the_reference_to_float32_accuracy(pick):
         else:
             for l in range(2):
                 assert np.abs(port[k][:, l] - ref[k][:, l]).max() < 2e-2 * np.abs(ref[k][:, l]).max(), (k, l)
+    assert not np.array_equal(port["minv"], ref["minv"])
+
+
+# ---- the same pins on the synthetic trees of tests/tree_cases.py --------------------------------------------------------------------------
+LP_TREE = (0.03, -0.02, 0.05)
+_trees = {}
+
+
+def _tree(name):
+    """state at seed 3, x, and per case the two deepest links with >= 6 dofs on their path (bushy has none: its deepest two)"""
+    if name not in _trees:
+        sb, spec = tree_cases.build(name)
+        model = kin_ref.Model(spec)
+        q, v = kin_ref.random_state(spec, model, B, seed=3)
+        x = np.random.default_rng(12).uniform(-2, 2, (B, model.nv))
+        links = tree_cases.links_on_long_paths(model)[:2] or [model.nbody - 1, model.nbody - 2]
+        M, J = task_ref.oracle_mass_and_jacobian(spec, model, q, links, LP_TREE)
+        _trees[name] = dict(spec=spec, model=model, q=q, x=x, links=links, M=M, J=J, ref=task_ref.combine(M, J, x, 0.0))   # computed once, left unchanged
+    return _trees[name]
+
+
+@pytest.mark.parametrize("name", tree_cases.CASES)
+def test_trees_minv_is_the_inverse_and_respects_the_trees(name):
+    """The pick bar is the absolute 1e-9 for cond(M) < 1e5 and entries of M^-1 up to 3e5.  Here it is relative to the float64 magnitudes:
+    |M minv - I| <= cond(M) x 2^-52 x a few, so 16 cond(M) 2^-52 (`many` holds a 4 cm cube beside 3 kg bodies: cond(M) ~ 3e6)."""
+    t = _tree(name)
+    M, ref, model = t["M"], t["ref"], t["model"]
+    nv = model.nv
+    bar = 16.0 * np.linalg.cond(M).max() * 2.0 ** -52
+    err = np.abs(M @ ref["minv"] - np.eye(nv)).max()
+    print(f"\n[task, {name}] max |M minv - I| {err:.3e}, bar {bar:.3e} (cond {np.linalg.cond(M).max():.3g})")
+    assert err < bar, (err, bar)
+    root = [0] * model.nbody
+    for b in range(1, model.nbody):
+        root[b] = b if model.parent[b] == 0 else root[model.parent[b]]
+    tree = np.array([root[max(b for b in range(model.nbody) if model.dofadr[b] <= d and model.jtype[b] != kin_ref.FIXED)] for d in range(nv)])
+    cross = tree[:, None] != tree[None, :]
+    assert cross.any() == (name == "many") and (ref["minv"][:, cross] == 0).all()
+    assert np.array_equal(ref["minv"], ref["minv"].transpose(0, 2, 1))
+    scale = np.abs(ref["solve"]).max()
+    assert np.abs(np.einsum("bij,bj->bi", M, ref["solve"]) - t["x"]).max() < bar * max(1.0, scale)
+
+
+@pytest.mark.parametrize("name", tree_cases.CASES)
+def test_trees_jbar_is_a_dynamically_consistent_inverse_or_nan(name):
+    t = _tree(name)
+    M, J, ref = t["M"], t["J"], t["ref"]
+    minv = ref["minv"]
+    assert np.isfinite(ref["lambda_inv"]).all()
+    for l in range(2):
+        Jl, jb = J[:, l], ref["jbar"][:, l]
+        assert np.allclose(ref["lambda_inv"][:, l], Jl @ minv @ Jl.transpose(0, 2, 1), rtol=1e-10, atol=1e-12)
+        if name == "bushy":   # four dofs on every path: the rule of the header, on links other than the Panda's link3
+            assert np.isnan(jb).all() and np.isnan(ref["lambda"][:, l]).all() and (ref["relpivot"][:, l] < 1e-6).all()
+            continue
+        assert np.isfinite(jb).all() and (ref["relpivot"][:, l] > 1e-4).all(), ref["relpivot"][:, l]
+        scale = np.abs(Jl).max() * np.abs(jb).max()
+        assert np.abs(Jl @ jb - np.eye(6)).max() < 1e-8 * max(1.0, scale), l
+        N = np.eye(M.shape[1]) - jb @ Jl
+        cons = Jl @ minv @ N.transpose(0, 2, 1)
+        assert np.abs(cons).max() < 1e-8 * np.abs(Jl @ minv).max() * max(1.0, np.abs(N).max()), (l, np.abs(cons).max())
+    damped = task_ref.combine(M, J, None, 0.05)
+    assert np.isfinite(damped["lambda"]).all() and np.isfinite(damped["jbar"]).all() and (damped["relpivot"] > 1e-4).all()
+
+
+@pytest.mark.parametrize("name", tree_cases.CASES)
+def test_trees_float32_port_agrees_with_the_reference_to_float32_accuracy(name):
+    """The bar of the pick test, 2e-2 of the largest entry; minv and solve per tree (tests/tree_metrics.py), never pooled: in `many`
+    the cube's rotational block of M^-1 is 3e5, the chain's a few."""
+    import tree_metrics
+
+    t = _tree(name)
+    f32 = "big" if name == "many" else True
+    port = task_ref.oracle_task_dynamics(t["spec"], t["model"], t["q"], t["links"], LP_TREE, x=t["x"], damping=0.05, f32=f32)
+    ref = task_ref.oracle_task_dynamics(t["spec"], t["model"], t["q"], t["links"], LP_TREE, x=t["x"], damping=0.05)
+    for label, idx in tree_metrics.dof_groups(t["model"]):
+        for lb, jdx in tree_metrics.dof_groups(t["model"]):
+            if label[0] == lb[0]:
+                blk = lambda a: a[:, idx[:, None], jdx[None, :]]  # noqa: E731
+                assert np.abs(blk(port["minv"]) - blk(ref["minv"])).max() <= 2e-2 * np.abs(blk(ref["minv"])).max(), (label, lb)
+        assert np.abs(port["solve"][:, idx] - ref["solve"][:, idx]).max() < 2e-2 * np.abs(ref["solve"][:, idx]).max(), label
+    for k in ("lambda_inv", "lambda", "jbar"):
+        if name == "bushy" and k != "lambda_inv":
+            continue   # (damping 0.05 leaves that 6 x 6 at a relative pivot of ~1e-4: conditioning, not the formulas)
+        for l in range(2):
+            assert np.abs(port[k][:, l] - ref[k][:, l]).max() < 2e-2 * np.abs(ref[k][:, l]).max(), (k, l)
     assert not np.array_equal(port["minv"], ref["minv"])
 
 
