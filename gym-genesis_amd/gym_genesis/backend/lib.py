@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirCartQuery, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirCarryQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_carry_query, make_cart_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
+from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirCartQuery, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirBlendQuery, MirCarryQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_blend_query, make_carry_query, make_cart_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -172,6 +172,10 @@ def load_library() -> C.CDLL:
     lib.mir_cartesian_path.argtypes = [vp, C.POINTER(MirCartQuery), C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp,
                                        vp, i32, vp, vp, vp, C.POINTER(MirIkOptions), vp, vp, vp, vp, vp, vp, vp]
     lib.mir_cartesian_path.restype = C.c_int
+    lib.mir_blend_query_sizeof.restype = C.c_int
+    lib.mir_blend_path.argtypes = [vp, C.POINTER(MirBlendQuery), C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp,
+                                   vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_blend_path.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
@@ -200,6 +204,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRetimeQuery (rebuild the library)")
     if lib.mir_cart_query_sizeof() != C.sizeof(MirCartQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCartQuery (rebuild the library)")
+    if lib.mir_blend_query_sizeof() != C.sizeof(MirBlendQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirBlendQuery (rebuild the library)")
     if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
     _lib = lib
@@ -1154,6 +1160,50 @@ class MirScene(StepHelpers):
                                                     _ptr(qpos_start), _ptr(tp), _ptr(tq), C.byref(o), _ptr(out["points"]), _ptr(out["n_points"]),
                                                     _ptr(out["fraction"]), _ptr(out["status"]), _ptr(out.get("path")), _ptr(out["stats"]), self._stream()))
             self.cart_launches = self.__dict__.get("cart_launches", 0) + 1
+        return out
+
+    def blend_path(self, probes, links, dof_qadr, poly, n_poly=None, env_idx=None, qpos_start=None, max_deviation: float = 0.05,
+                   blend_points: int = 8, max_shrinks: int = 4, max_points=None, num_waypoints: int = 0, ignore_collision: bool = False,
+                   resolution: float = 0.05, margin: float = 0.0, max_distance: float = 1.0, skip_geoms=0, self_model=None, carry=None) -> dict:
+        """mir_blend_path: for the envs `env_idx` (None: all), ONE launch rounds the interior corners of the joint-space polylines `poly`
+        (R, K, D) -- K <= 128 nodes over the planned dofs `dof_qadr`, as plan_path()["poly"] holds them, `n_poly` (R,) the count of valid
+        leading nodes (None: K); repeated nodes are dropped -- by quadratic Bezier blends that stay within `max_deviation` (L2 over the
+        dofs) of their corner, `blend_points` chords each.  Every blend is checked like an edge of plan_path() (the sphere model,
+        `resolution`, `margin`, `skip_geoms`, `self_model` and `carry` = dict(body, link) exactly as in path_clearance(); the grasp is
+        taken from the start row, `qpos_start` (R, nq) or the current state); a blocked blend is halved up to `max_shrinks` times and
+        then left sharp (include/mirigid.h has the rule).  The straight remainders of the input's segments are not checked again.
+        -> dict of fresh device tensors: points (R, P, D) with P = `max_points` (None: the worst case 2 + (K - 2)(blend_points + 1); the
+        smoothed path, then its last point repeated), n_points (R,) int32, status (R,) int32 (spec.BLEND_STATUS), blend_len (R, 128): the
+        accepted half-length at each input node, stats (R, 4) int32: nodes kept, corners blended, corners left sharp, configurations
+        checked; with num_waypoints = W >= 2 also path (R, W, D): the points resampled at equal arc length.  A row that fails holds its
+        first node everywhere.  The call changes nothing a later call can see."""
+        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
+        D = int(qa.shape[0])
+        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
+        poly = torch.as_tensor(poly, device=self.device).to(torch.float32).contiguous()
+        if poly.dim() != 3 or poly.shape[0] != R or poly.shape[2] != D:
+            raise ValueError(f"poly must be ({R}, K, {D}), got {tuple(poly.shape)}")
+        K = int(poly.shape[1])
+        if n_poly is not None:
+            n_poly = torch.as_tensor(n_poly, device=self.device).to(torch.int32).contiguous()
+            if tuple(n_poly.shape) != (R,):
+                raise ValueError(f"n_poly must be ({R},), got {tuple(n_poly.shape)}")
+        W = int(num_waypoints)
+        q = make_blend_query(K, max_deviation, blend_points, max_shrinks, max_points, W)
+        P = int(q.max_points)
+        pq = make_plan_query(N, D, ignore_collision=ignore_collision, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
+        cq = None if carry is None else make_carry_query(carry["body"], carry["link"])
+        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        out = {"points": new(max(P, 0), D), "n_points": new(dtype=torch.int32), "status": new(dtype=torch.int32), "blend_len": new(PLAN_MAX_POLY),
+               "stats": new(4, dtype=torch.int32)}
+        if W > 0:
+            out["path"] = new(W, D)
+        if R > 0:   # (without rows there is nothing to point at)
+            self._check(self.lib.mir_blend_path(self.h, C.byref(q), C.byref(pq), None if sq is None else C.byref(sq), None if cq is None else C.byref(cq),
+                                                _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p), qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
+                                                _ptr(qpos_start), _ptr(poly), _ptr(n_poly), _ptr(out["points"]), _ptr(out["n_points"]), _ptr(out["status"]),
+                                                _ptr(out.get("path")), _ptr(out["blend_len"]), _ptr(out["stats"]), self._stream()))
+            self.blend_launches = self.__dict__.get("blend_launches", 0) + 1
         return out
 
     def retime_path(self, paths, vmax, amax, dt, num_samples: int = 0, max_path_speed=None, extra=None, velocity: bool = False) -> dict:

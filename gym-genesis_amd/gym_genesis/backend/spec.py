@@ -624,6 +624,41 @@ def make_cart_query(link_body: int, num_targets: int, max_points: int = 256, num
     return q
 
 
+BLEND_STATUS = {0: "OK", 2: "START_IN_COLLISION", 7: "START_IN_SELF_COLLISION", 32: "NO_MOTION", 33: "NOT_FINITE",
+                34: "TOO_MANY_POINTS"}   # mir_blend_path: MIR_PLAN_* for the start, MIR_BLEND_* (include/mirigid.h)
+BLEND_NO_MOTION, BLEND_NOT_FINITE, BLEND_TOO_MANY_POINTS = range(32, 35)
+
+
+class MirBlendQuery(C.Structure):
+    """include/mirigid.h: MirBlendQuery (mir_blend_path)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("num_nodes", C.c_int32),
+        ("blend_points", C.c_int32),
+        ("max_shrinks", C.c_int32),
+        ("max_points", C.c_int32),
+        ("num_waypoints", C.c_int32),
+        ("flags", C.c_uint32),
+        ("max_deviation", C.c_float),
+    ]
+
+
+def blend_max_points(num_nodes: int, blend_points: int) -> int:
+    """the dense points a polyline of `num_nodes` nodes can need: 2 + (K - 2)(m + 1)"""
+    return 2 + max(int(num_nodes) - 2, 0) * (int(blend_points) + 1)
+
+
+def make_blend_query(num_nodes: int, max_deviation: float = 0.05, blend_points: int = 8, max_shrinks: int = 4, max_points=None,
+                     num_waypoints: int = 0) -> MirBlendQuery:
+    """max_deviation: the blend's largest L2 distance from its corner; blend_points chords per blend; max_points None: the worst case."""
+    q = MirBlendQuery()
+    q.struct_size = C.sizeof(MirBlendQuery)
+    q.num_nodes, q.blend_points, q.max_shrinks, q.num_waypoints, q.flags = int(num_nodes), int(blend_points), int(max_shrinks), int(num_waypoints), 0
+    q.max_points = blend_max_points(num_nodes, blend_points) if max_points is None else int(max_points)
+    q.max_deviation = float(max_deviation)
+    return q
+
+
 IK_DEFAULTS = dict(max_iters=20, respect_joint_limit=1, damping=0.05, pos_tol=5e-4, rot_tol=5e-3, max_step=0.5)
 
 RENDER_PER_ENV, RENDER_GLOBAL = 0, 1

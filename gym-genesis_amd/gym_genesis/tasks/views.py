@@ -1026,6 +1026,60 @@ class EntityView:
             return detail
         return (detail["path"], detail["fraction"]) if return_fraction else detail["path"]
 
+    # ---- corner blending (MirScene.blend_path / mir_blend_path): what stands between plan_path and retime_path.  The name and the
+    # arguments are this package's own: parity with Genesis is unpinned.
+    def blend_path(self, poly, n_poly=None, max_deviation=0.05, blend_points=8, max_shrinks=4, num_waypoints=None, max_points=None,
+                   envs_idx=None, qpos_start=None, return_detail=False, resolution=0.05, margin=0.0, ignore_collision=False, with_entity=None,
+                   ignore_entities=(), self_collision=None, self_margin=0.0, attached_entity=None, ee_link_name=None, grasp_pose=None,
+                   attached_links=None):
+        """``robot.blend_path(detail["poly"], detail["n_poly"])`` -> (W, R, n): the polyline `poly` ((R, K, n) in this entity's dof order,
+        K <= 128: what plan_path(return_detail=True) returns as poly, with `n_poly` (R,) its count of valid leading nodes; None: all K)
+        with every interior corner rounded by a quadratic Bezier blend that stays within `max_deviation` (L2 over the dofs) of the
+        corner, `blend_points` chords per blend, in the layout plan_path() returns -- so it goes into retime_path, get_path_clearance and
+        control_dofs_position unchanged.  ONE launch for all rows (MirScene.blend_path / mir_blend_path, where the rule is written
+        down).  A blend cuts inside its corner, towards what the planner went round, so each one is checked like an edge of plan_path()
+        (every `resolution` per joint; `margin`, `ignore_collision`, `with_entity`, `ignore_entities`, `self_collision`, `self_margin`,
+        `attached_entity`, `ee_link_name`, `attached_links` mean what they mean there; the carried object's grasp is where the object
+        is at the start: `grasp_pose` must be None); a blocked blend is halved up to `max_shrinks` times and then left sharp.
+        `num_waypoints` = W: the smoothed path resampled at equal arc length; None: its dense points themselves, W = `max_points` (None:
+        the worst case 2 + (K - 2)(blend_points + 1)), the last one repeated behind the row's own count -- retime_path drops the repeats.
+        (The 128-node polyline of plan_path makes that 1136 points per row: where memory matters, slice `poly` to the nodes in use,
+        poly[:, :int(n_poly.max())], or give `max_points`; a row that needs more comes back TOO_MANY_POINTS, as its start.)
+        A row without motion (a failed plan: its start K times) comes back as its start.  return_detail=True -> a dict with path, valid
+        (R,) = status is OK or NO_MOTION, status (R,) int32 (spec.BLEND_STATUS), points (R, P, n), n_points (R,), blend_len (R, 128): the
+        accepted half-length at each input node, and stats (R, 4): nodes kept, corners blended, corners left sharp, configurations
+        checked.  On an unbatched task every result comes without its env axis ((K, n) is accepted for poly).
+        What it does not do: a reversal is still a stop; no jerk limit; the straight remainders of the input's segments are not checked
+        again (the input was checked by whoever made it; get_path_clearance answers for the result)."""
+        if grasp_pose is not None:
+            raise NotImplementedError("blend_path: the grasp is taken from where the attached entity is at the start (mir_blend_path has no "
+                                      "grasp rows); grasp_pose must be None")
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "blend_path", self_collision, self_margin, attached_entity,
+                                  ee_link_name, None, attached_links)
+        if getattr(self._mir, "blend_path", None) is None:
+            raise NotImplementedError("this scene has no corner blending (MirScene.blend_path / mir_blend_path)")
+        one = bool(self.__dict__.get("unbatched"))
+        p = torch.as_tensor(poly, device=self._mir.device).to(torch.float32)
+        if one and p.dim() == 2:
+            p = p[None]
+        if p.dim() != 3 or p.shape[0] != R or p.shape[2] != len(self._qcols):
+            raise ValueError(f"poly must be ({R}, K, {len(self._qcols)}), got {tuple(p.shape)}")
+        if n_poly is not None:
+            n_poly = torch.as_tensor(n_poly, device=self._mir.device).to(torch.int32).reshape(-1)
+        if "carry" in args:
+            args["carry"] = dict(body=args["carry"]["body"], link=args["carry"]["link"])
+        W = None if num_waypoints is None else int(num_waypoints)
+        r = self._mir.blend_path(poly=p.contiguous(), n_poly=n_poly, max_deviation=float(max_deviation), blend_points=int(blend_points),
+                                 max_shrinks=int(max_shrinks), max_points=None if max_points is None else int(max_points),
+                                 num_waypoints=0 if W is None else W, ignore_collision=bool(ignore_collision), resolution=float(resolution),
+                                 margin=float(margin), max_distance=max(1.0, 2.0 * float(margin)), **args)
+        path = (r["points"] if W is None else r["path"]).permute(1, 0, 2).contiguous()
+        detail = {"path": path, "valid": (r["status"] == 0) | (r["status"] == 32), "status": r["status"], "points": r["points"],
+                  "n_points": r["n_points"], "blend_len": r["blend_len"], "stats": r["stats"]}
+        if one:   # (an unbatched task: no env axis anywhere)
+            detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
+        return detail if return_detail else detail["path"]
+
     # ---- time parameterisation (MirScene.retime_path / mir_retime_path): what stands between plan_path and control_dofs_position.
     # get_dofs_force_range is a Genesis name (RigidEntity); retime_path is this package's own: parity with Genesis is unpinned.
     def get_dofs_force_range(self, dofs_idx_local=None):

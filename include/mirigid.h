@@ -1096,6 +1096,86 @@ int mir_cartesian_path(MirHandle h, const MirCartQuery* q, const MirPlanQuery* p
                        float* fraction /* (R) */, int32_t* status /* (R) */, float* path /* (R,W,D) nullable */,
                        int32_t* stats /* (R,4) nullable */, void* stream);
 
+/* ---- corner blending: the corners of a joint-space polyline rounded, collision-checked, in one launch -------------
+ * `robot.blend_path(poly)`: mir_plan_path and mir_cartesian_path turn their corners at a point, and mir_retime_path keeps the
+ * acceleration limit only on average there (above, "What it does not do").  For R rows ONE launch (mir_blend.hip, one wave64 per row)
+ * replaces each interior corner of a row's polyline by a quadratic Bezier blend within a stated deviation from the corner, checks the
+ * blend with the planner's clear(q), halves a blocked blend and returns the smoothed path dense enough for mir_retime_path.  It reads
+ * the state (or the start rows) and the compiled model and writes only its outputs.  The rule is this library's own.
+ * Arguments.  pq supplies the clearance side exactly as for mir_path_clearance (n_probes, n_dofs, resolution, margin, max_distance,
+ *   flags, skip_geoms; its planner fields are ignored); sq, cq, probes, probe_link, dof_qadr (D <= 16), env_idx, n_rows and qpos_start
+ *   are those of mir_cartesian_path (the grasp transform is taken from the start row).  poly (R, K, D): row k's polyline (row k, not env
+ *   env_idx[k]), 2 <= K = num_nodes <= MIR_PLAN_MAX_POLY; n_poly (R), nullable: the count of valid leading nodes as mir_plan_path
+ *   writes it, clamped to 1 .. K (NULL: K); nodes behind it are not read.  delta = max_deviation, m = blend_points, s = max_shrinks,
+ *   P = max_points, W = num_waypoints.  Every quotient below is the planner's: a float32 division refined by one Newton step; every
+ *   sum over the dofs runs j ascending.
+ * Per row:
+ * 1. Compaction, as mir_retime_path: node k is dropped when all D values compare equal to the last kept node; the kept ones are
+ *   Q_0 .. Q_{M-1}.  In this order: a value of a valid node that is not finite: NOT_FINITE.  M = 1: NO_MOTION (no error: the start
+ *   repeated, what a failed mir_plan_path row holds).  2 + (M - 2)(m + 1) > P: TOO_MANY_POINTS -- decided from the worst case before
+ *   anything is evaluated, so it does not depend on collisions.
+ * 2. Start.  clear(Q_0) of mir_plan_path: its scene test fails: MIR_PLAN_START_IN_COLLISION; with sq, its self test fails:
+ *   MIR_PLAN_START_IN_SELF_COLLISION.
+ * 3. Segments.  d_i = Q_{i+1} - Q_i, L_i = sqrt(sum_j d_ij^2), u_ij = d_ij / L_i (u_i = 0 when L_i underflowed to 0).
+ * 4. Half-length of the blend at interior node i = 1 .. M - 2: h_i = min(L_{i-1}, L_i) / 2, so neighbouring blends never overlap; with
+ *   du = sqrt(sum_j (u_ij - u_{i-1,j})^2) > 0 also h_i <= 4 delta / du: the curve passes its corner at the distance h du / 4, at its
+ *   midpoint, and no point of it lies further than that from the input polyline.  du = 0 (collinear) keeps h_i = min / 2: the blend
+ *   lies on the segments.
+ * 5. Blend.  A = Q_i - h u_{i-1}, C = Q_i + h u_i, B(t) = (1 - t)^2 A + 2 t (1 - t) Q_i + t^2 C, evaluated by de Casteljau per dof:
+ *   p = A + t (Q_i - A), r = Q_i + t (C - Q_i), B = p + t (r - p); B(0) carries A's bits and B(1) C's.  A dof that does not move on
+ *   either segment keeps its bits through every step.
+ * 6. Check.  n_c = max(1, ceil(2 max_j max(|Q_ij - A_j|, |C_j - Q_ij|) / resolution)), at most 4096 (a quotient that is not finite
+ *   counts as 4096); clear(B(k / n_c)) for k = 0 .. n_c in order, the first blocked one ends the check.  |dB_j/dt| <= 2 max(|Q_ij -
+ *   A_j|, |C_j - Q_ij|), so consecutive samples differ by at most `resolution` per joint: the promise of the planner's edge rule.
+ *   clear is the planner's: the scene test, then (sq) the self test, both with the carried body (cq).
+ * 7. Shrinking.  A blocked blend halves h and is checked again, at most s times (s + 1 checks); still blocked, h = 0: the corner
+ *   stays sharp and is counted.  h = 0 from 4. (an L that underflowed) is sharp without a check.  MIR_PLAN_IGNORE_COLLISION skips 2.
+ *   and every check.  The straight remainders of the input's segments are the caller's and are NOT evaluated: the input polyline
+ *   was checked by whoever made it, and mir_path_clearance answers for the dense points.
+ * 8. Dense points, in order: Q_0; per interior node B(k / m) for k = 0 .. m of the accepted h (k = 0: A's bits, k = m: C's), or Q_i
+ *   itself at h = 0; Q_{M-1}.  A point whose D bit patterns equal the point before is not emitted (two full-length blends meet
+ *   mid-segment).  points (R, P, D) holds them, the last one repeated behind n_points (the layout of mir_cartesian_path: what
+ *   mir_retime_path compacts and mir_path_clearance accepts).  Every point is a convex combination of input nodes (up to rounding), so
+ *   the joint limits the input kept need no new check.
+ * 9. Waypoints, W >= 2: path (R, W, D) = the n_points dense points resampled at equal arc length by step 7 of mir_plan_path, the first
+ *   and the last carrying the bits of Q_0 and Q_{M-1}.
+ * Outputs.  status (R): MIR_PLAN_OK, the two start statuses or MIR_BLEND_*; n_points (R); blend_len (R, MIR_PLAN_MAX_POLY), nullable: the
+ *   accepted h at each INPUT node, 0 where there is none (the ends, a dropped node, a sharp corner); stats (R, 4), nullable: M, corners
+ *   blended, corners left sharp, configurations checked.  A row with another status than OK returns its first node everywhere
+ *   (n_points = 1, blend_len 0): following it keeps the arm still.
+ * Every loop is bounded by K, m, s, the 4096 samples of a check, P or W; no input can keep a wave running.
+ * MIR_E_INVALID: a NULL handle, q, pq, probes, dof_qadr, poly, points, n_points or status; struct_size != sizeof of any query given;
+ *   K < 2; m outside 2 .. 64; s < 0; P < 2; W < 0 or W == 1, W >= 2 without path or path with W == 0; an unknown flag bit; delta not
+ *   finite or <= 0; everything mir_path_clearance (and the _self / _carry forms, when sq / cq are given) refuses.  MIR_E_CAPACITY:
+ *   K > MIR_PLAN_MAX_POLY; R x max(P, W) x D beyond 2^31 - 1.  None of them launches anything, mir_last_error() names the entry point,
+ *   and n_rows == 0 returns MIR_OK without a launch.
+ * What it does not do.  A reversal (u_i = -u_{i-1}) is still a stop: its blend lies on the segment.  No jerk limit: the curvature
+ *   jumps where a blend meets a straight remainder.  Straight remainders are not re-checked (7.).  A blocked blend is only shrunk
+ *   about its corner, never moved to the other side.
+ * (Added struct and entry point: MIR_VERSION and every other struct and entry point stay as they are.) */
+#define MIR_BLEND_NO_MOTION 32
+#define MIR_BLEND_NOT_FINITE 33
+#define MIR_BLEND_TOO_MANY_POINTS 34
+#define MIR_BLEND_MAX_POINTS_PER_CORNER 64
+#define MIR_BLEND_MAX_CHECK 4096
+typedef struct MirBlendQuery {
+  int32_t  struct_size;    /* = sizeof(MirBlendQuery) */
+  int32_t  num_nodes;      /* K: 2 .. MIR_PLAN_MAX_POLY */
+  int32_t  blend_points;   /* m: 2 .. 64 chords per blend */
+  int32_t  max_shrinks;    /* s >= 0 halvings of a blocked blend */
+  int32_t  max_points;     /* P >= 2: the capacity of points per row */
+  int32_t  num_waypoints;  /* W: 0, or >= 2 with path */
+  uint32_t flags;          /* 0; unknown bits are MIR_E_INVALID */
+  float    max_deviation;  /* delta > 0: L2 over the planned dofs */
+} MirBlendQuery;
+int mir_blend_query_sizeof(void);
+int mir_blend_path(MirHandle h, const MirBlendQuery* q, const MirPlanQuery* pq, const MirSelfQuery* sq /* nullable */,
+                   const MirCarryQuery* cq /* nullable */, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+                   const int64_t* env_idx, int32_t n_rows, const float* qpos_start /* (R,nq) nullable */,
+                   const float* poly /* (R,K,D) */, const int32_t* n_poly /* (R) nullable */, float* points /* (R,P,D) */,
+                   int32_t* n_points /* (R) */, int32_t* status /* (R) */, float* path /* (R,W,D) nullable */,
+                   float* blend_len /* (R,MIR_PLAN_MAX_POLY) nullable */, int32_t* stats /* (R,4) nullable */, void* stream);
+
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
