@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirCartQuery, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirBlendQuery, MirCarryQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_blend_query, make_carry_query, make_cart_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
+from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirCartQuery, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirBlendQuery, MirCarryQuery, MirCertQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_blend_query, make_carry_query, make_cart_query, make_cert_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -176,6 +176,9 @@ def load_library() -> C.CDLL:
     lib.mir_blend_path.argtypes = [vp, C.POINTER(MirBlendQuery), C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp,
                                    vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_blend_path.restype = C.c_int
+    lib.mir_cert_query_sizeof.restype = C.c_int
+    lib.mir_certify_path.argtypes = [vp, C.POINTER(MirCertQuery), C.POINTER(MirPlanQuery), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_certify_path.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
@@ -206,6 +209,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCartQuery (rebuild the library)")
     if lib.mir_blend_query_sizeof() != C.sizeof(MirBlendQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirBlendQuery (rebuild the library)")
+    if lib.mir_cert_query_sizeof() != C.sizeof(MirCertQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCertQuery (rebuild the library)")
     if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
     _lib = lib
@@ -1114,6 +1119,44 @@ class MirScene(StepHelpers):
                                                          self._stream()))
         if R > 0:
             self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
+        return out
+
+    def certify_path(self, probes, links, dof_qadr, paths, env_idx=None, qpos_start=None, margin: float = 0.0, tol: float = 0.002,
+                     guard: float = 1e-5, max_depth: int = 12, max_evaluations: int = 4096, bracket: bool = False, max_leaves: int = 0,
+                     max_distance: float = 1.0, skip_geoms=0, ignore_collision: bool = False) -> dict:
+        """mir_certify_path: the CONTINUOUS minimum clearance of the trajectories `paths` (R, K, D) over the planned dofs `dof_qadr`,
+        bracketed per segment in ONE launch.  Where path_clearance() judges samples of a segment, this call judges all of it: the signed
+        distance is 1-Lipschitz in a sphere's centre and a centre moves no faster than the kinematic chain allows, so one evaluation
+        bounds the clearance on a whole interval, which is bisected where the bound does not decide (include/mirigid.h has the rule).
+        `tol`: the width a bracket is closed to; `guard`: subtracted from every bound for the float32 error of an evaluation; `max_depth`
+        (0 .. 20) and `max_evaluations` per row bound the work; `bracket`: close every bracket to `tol` instead of stopping at "clear of
+        `margin`"; `max_leaves`: the accepted leaves kept per row.  Everything else as path_clearance(); the self test and a carried
+        object are sampled only and have no place here.
+        -> dict of fresh device tensors: seg_lower, seg_upper (R, K-1), seg_status (R, K-1) int32 (spec.CERT_STATUS), row_lower,
+        row_upper (R,), row_status, row_first (R,) int32 (the first segment that is not CLEAR, -1: none), stats (R, 4) int32:
+        evaluations, leaves, deepest level, segments finished; with max_leaves > 0 also leaves (R, max_leaves, 3) int32: segment, level,
+        index, -1 behind the row's count.  The call changes nothing a later call can see."""
+        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
+        D = int(qa.shape[0])
+        paths = torch.as_tensor(paths, device=self.device).to(torch.float32).contiguous()
+        if paths.dim() != 3 or paths.shape[0] != R or paths.shape[2] != D or paths.shape[1] < 2:
+            raise ValueError(f"paths must be ({R}, K >= 2, {D}), got {tuple(paths.shape)}")
+        K = int(paths.shape[1])
+        q = make_cert_query(K, tol, guard, max_depth, max_evaluations, bracket, max_leaves)
+        pq = make_plan_query(int(p.shape[0]), D, ignore_collision=ignore_collision, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
+        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        i32 = torch.int32
+        out = {"seg_lower": new(K - 1), "seg_upper": new(K - 1), "seg_status": new(K - 1, dtype=i32), "row_lower": new(), "row_upper": new(),
+               "row_status": new(dtype=i32), "row_first": new(dtype=i32), "stats": new(4, dtype=i32)}
+        if int(max_leaves) > 0:
+            out["leaves"] = torch.full((R, int(max_leaves), 3), -1, dtype=i32, device=self.device)
+        if R > 0:   # (without rows there is nothing to point at)
+            self._check(self.lib.mir_certify_path(self.h, C.byref(q), C.byref(pq), _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p),
+                                                  qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(paths), _ptr(out["seg_lower"]),
+                                                  _ptr(out["seg_upper"]), _ptr(out["seg_status"]), _ptr(out["row_lower"]), _ptr(out["row_upper"]),
+                                                  _ptr(out["row_status"]), _ptr(out["row_first"]), _ptr(out.get("leaves")), _ptr(out["stats"]),
+                                                  self._stream()))
+            self.cert_launches = self.__dict__.get("cert_launches", 0) + 1
         return out
 
     def cartesian_path(self, probes, links, dof_qadr, link_body: int, target_pos, target_quat=None, env_idx=None, qpos_start=None,

@@ -659,6 +659,36 @@ def make_blend_query(num_nodes: int, max_deviation: float = 0.05, blend_points: 
     return q
 
 
+CERT_STATUS = {0: "CLEAR", 1: "UNDECIDED", 2: "DEPTH", 3: "BUDGET", 4: "BLOCKED", 5: "NOT_FINITE"}   # mir_certify_path, by severity
+CERT_CLEAR, CERT_UNDECIDED, CERT_DEPTH, CERT_BUDGET, CERT_BLOCKED, CERT_NOT_FINITE = range(6)
+CERT_BRACKET = 1
+
+
+class MirCertQuery(C.Structure):
+    """include/mirigid.h: MirCertQuery (mir_certify_path)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("num_points", C.c_int32),
+        ("max_depth", C.c_int32),
+        ("max_evaluations", C.c_int32),
+        ("max_leaves", C.c_int32),
+        ("flags", C.c_uint32),
+        ("tol", C.c_float),
+        ("guard", C.c_float),
+    ]
+
+
+def make_cert_query(num_points: int, tol: float = 0.002, guard: float = 1e-5, max_depth: int = 12, max_evaluations: int = 4096,
+                    bracket: bool = False, max_leaves: int = 0) -> MirCertQuery:
+    """tol: the width a bracket is closed to; guard: subtracted from every bound; bracket: close every bracket, not only decide the margin."""
+    q = MirCertQuery()
+    q.struct_size = C.sizeof(MirCertQuery)
+    q.num_points, q.max_depth, q.max_evaluations, q.max_leaves = int(num_points), int(max_depth), int(max_evaluations), int(max_leaves)
+    q.flags = CERT_BRACKET if bracket else 0
+    q.tol, q.guard = float(tol), float(guard)
+    return q
+
+
 IK_DEFAULTS = dict(max_iters=20, respect_joint_limit=1, damping=0.05, pos_tol=5e-4, rot_tol=5e-3, max_step=0.5)
 
 RENDER_PER_ENV, RENDER_GLOBAL = 0, 1

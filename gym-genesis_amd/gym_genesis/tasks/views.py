@@ -968,6 +968,50 @@ class EntityView:
                                        self_margin=self_margin, attached_entity=attached_entity, ee_link_name=ee_link_name, grasp_pose=grasp_pose,
                                        attached_links=attached_links) < float(margin)
 
+    # ---- certified clearance (MirScene.certify_path / mir_certify_path): the question get_path_clearance answers for samples, answered for
+    # the whole of every segment.  The names and the arguments are this package's own: parity with Genesis is unpinned.
+    def certify_path(self, path, margin=0.0, tol=0.002, guard=1e-5, max_depth=12, max_evaluations=4096, bracket=False, max_leaves=0,
+                     max_distance=1.0, envs_idx=None, qpos_start=None, with_entity=None, ignore_entities=(), return_detail=False,
+                     self_collision=False, attached_entity=None):
+        """``robot.certify_path(path)`` -> (R,) int32, spec.CERT_STATUS by severity: 0 CLEAR -- the entity's sphere model keeps `margin`
+        from every tested geom along the WHOLE trajectory `path` ((K, R, n) as plan_path returns it and get_path_clearance accepts it,
+        K >= 2), not only at samples of it -- 1 UNDECIDED (the minimum is bracketed within `tol` and the bracket straddles the margin),
+        2 DEPTH, 3 BUDGET (`max_depth`, `max_evaluations` per row ran out), 4 BLOCKED (a configuration below the margin was found),
+        5 NOT_FINITE.  ONE launch for all rows (MirScene.certify_path / mir_certify_path, where the rule and the argument are written
+        down).  `bracket`: close the bracket of every segment to `tol` instead of stopping at "clear of the margin".  `qpos_start`,
+        `envs_idx`, `with_entity`, `ignore_entities` as in get_path_clearance.  return_detail=True: a dict with status, first (R,) the
+        first segment that is not CLEAR (-1: none), lower, upper (R,), seg_lower, seg_upper, seg_status (R, K-1), stats (R, 4):
+        evaluations, leaves, deepest level, segments finished, and with max_leaves > 0 leaves (R, max_leaves, 3).
+        What it does not do: the arm against itself and a carried object need a bound on relative motion; they are sampled only
+        (get_path_clearance), so `self_collision=True` or an `attached_entity` is refused."""
+        if self_collision or attached_entity is not None:
+            raise ValueError("certify_path: the self and carried-object tests are sampled only (get_path_clearance); the certified rule "
+                             "covers the sphere model against the static scene")
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "certify_path", False)
+        if getattr(self._mir, "certify_path", None) is None:
+            raise NotImplementedError("this scene has no certified clearance (MirScene.certify_path / mir_certify_path)")
+        p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
+        if self.__dict__.get("unbatched") and p.dim() == 2:
+            p = p[:, None]
+        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != len(self._qcols) or p.shape[0] < 2:
+            raise ValueError(f"path must be (K >= 2, {R}, {len(self._qcols)}), got {tuple(p.shape)}")
+        r = self._mir.certify_path(paths=p.permute(1, 0, 2).contiguous(), margin=float(margin), tol=float(tol), guard=float(guard),
+                                   max_depth=int(max_depth), max_evaluations=int(max_evaluations), bracket=bool(bracket),
+                                   max_leaves=int(max_leaves), max_distance=max(float(max_distance), 2.0 * float(margin)), **args)
+        out = {"status": r["row_status"], "first": r["row_first"], "lower": r["row_lower"], "upper": r["row_upper"], "seg_lower": r["seg_lower"],
+               "seg_upper": r["seg_upper"], "seg_status": r["seg_status"], "stats": r["stats"]}
+        if "leaves" in r:
+            out["leaves"] = r["leaves"]
+        if self.__dict__.get("unbatched"):
+            out = {k: v[0] for k, v in out.items()}
+        return out if return_detail else out["status"]
+
+    def path_is_certified_clear(self, path, margin: float = 0.0, **kwargs) -> torch.Tensor:
+        """(R,) bool: certify_path(path, margin, ...) is CLEAR -- the sphere model keeps `margin` from every tested geom along the whole
+        trajectory.  False is "not proven": BLOCKED is a found collision, the other statuses say what ran out."""
+        kwargs.pop("return_detail", None)
+        return self.certify_path(path, margin=margin, **kwargs) == 0
+
     # ---- straight-line end-effector paths (MirScene.cartesian_path / mir_cartesian_path): the approach, the lift and the place of a
     # grasp.  The name and the arguments are this package's own (MoveIt: computeCartesianPath): parity with Genesis is unpinned.
     def plan_cartesian_path(self, link, pos, quat=None, qpos_start=None, envs_idx=None, max_step=0.01, max_rot_step=0.05, jump_threshold=0.5,

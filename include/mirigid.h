@@ -1176,6 +1176,94 @@ int mir_blend_path(MirHandle h, const MirBlendQuery* q, const MirPlanQuery* pq, 
                    int32_t* n_points /* (R) */, int32_t* status /* (R) */, float* path /* (R,W,D) nullable */,
                    float* blend_len /* (R,MIR_PLAN_MAX_POLY) nullable */, int32_t* stats /* (R,4) nullable */, void* stream);
 
+/* ---- certified clearance: the continuous minimum clearance of a joint path bracketed, in one launch ----------------
+ * `robot.certify_path(path)`: every collision answer above between two configurations is a sampled one (the edge rule evaluates
+ * configurations at most `resolution` apart per joint and leaves what lies between them unjudged).  For R rows ONE launch
+ * (mir_cert.hip, one wave64 per row) gives, per segment of a row's path, a lower and an upper bound of the minimum over the WHOLE
+ * segment of the sphere model's clearance against the tested geoms.  It reads the state (or the start rows) and the compiled model
+ * and writes only its outputs.  The rule is this library's own.
+ * Why it holds.  The signed distance to a static scene is 1-Lipschitz in a sphere's centre (the planner's front end refuses tested
+ *   geoms that ride on planned joints, so the scene is static).  Along q(t) = a + t dq, t in [0, 1], the centre of probe i moves no
+ *   faster than v_i = sum_j |dq_j| rho_ij, where for a revolute dof j rho_ij is a bound on the distance between joint j's anchor and
+ *   the centre -- the length of the kinematic chain between them, which does not depend on the configuration -- and for a prismatic
+ *   dof the length of its axis.  So d_i(t) >= d_i(tm) - |t - tm| v_i: ONE evaluation at the midpoint of an interval bounds the
+ *   clearance on all of it, and bisecting where that bound does not decide yields a guaranteed lower bound.
+ * Arguments.  pq supplies n_probes, n_dofs, margin, max_distance, flags and skip_geoms exactly as for mir_path_clearance (the rest is
+ *   checked as ever and not read); probes, probe_link, dof_qadr (D <= 16), env_idx, n_rows, qpos_start are those of
+ *   mir_path_clearance.  paths (R, K, D): row k's path (row k, not env env_idx[k]), K = num_points >= 2.  Segment s runs from a = P_s
+ *   to b = P_{s+1}, dq = b - a (float32).
+ * Per row and segment:
+ * 1. Chain lengths, rebuilt per segment, parent before child: S[0] = 0, S[b] = S[parent] + |pos_b| + pris_b, where pris_b = max(|a_k|,
+ *   |b_k|) |axis_b| for a planned prismatic joint (k its dof), |q_b| |axis_b| of the row for an unplanned one, 0 for a revolute or
+ *   fixed body.  A body whose parent is the world, and a free body, start a chain: S = 0.  The joint anchor is the body's origin
+ *   (MirBodySpec has no joint offset).
+ * 2. Speed bound of probe i on link L with local centre c_i: v_i = ((S[L] + |c_i|) A_L - B_L + P_L) 1.0001, never below 0, from
+ *   three sums over the planned dofs j on L's path to the world (up to the start of its chain), formed parent before child like S:
+ *   A = sum over the revolute ones of |dq_j|, B = sum over the revolute ones of |dq_j| S[body_j], P = sum over the prismatic ones of
+ *   |dq_j| |axis_j|.  That is sum_j |dq_j| rho_ij with rho_ij = S[L] - S[body_j] + |c_i| (revolute) or |axis_j| (prismatic); the
+ *   factor 1.0001 keeps float32 rounding from making it too low.  Probes on the world, or below no planned dof, have v_i = 0.  Every
+ *   product is rounded on its own (no fused multiply-add).
+ * 3. Endpoints.  P_0 for segment 0 only, and P_{s+1} for every segment, are evaluated like clear(q) of mir_plan_path: u = min_i d_i
+ *   with d_i the capped (distance - radius) of probe i; upper_s = min(upper_s, u).  Without MIR_CERT_BRACKET an endpoint with u <
+ *   margin ends the segment as BLOCKED, with lower_s = u - guard.
+ * 4. Bisection, stackless, depth first, left child first, from (l, k) = (0, 0).  Node (l, k) covers [k 2^-l, (k + 1) 2^-l]; its
+ *   midpoint tm = (2k + 1) 2^-(l+1) and half-width hw = 2^-(l+1) are exact in float32.  d_i at fmaf(tm, dq, a); u = min_i d_i; lo =
+ *   min_i (d_i - hw v_i) - guard; upper_s = min(upper_s, u).  Without BRACKET and u < margin: lower_s = min(lower_s, lo), BLOCKED, the
+ *   segment ends.  The node is a LEAF when (not BRACKET and lo >= margin) or lo >= upper_s - tol; at l == max_depth it is a leaf
+ *   regardless, and if neither test held it marks the segment DEPTH.  A leaf does lower_s = min(lower_s, lo); then, while k is odd,
+ *   k >>= 1 and l--; the segment is done at l == 0; otherwise k++.  A node that is no leaf does l++, k *= 2.
+ * 5. Budget (takes precedence over 3. and 4.): before EVERY evaluation the row's count is compared with max_evaluations; when it is
+ *   spent, this segment and every later one are BUDGET with lower = -INFINITY; upper keeps what was sampled (+INFINITY: nothing).
+ * 6. Not finite.  A segment one of whose waypoints (or whose dq) is not finite is NOT_FINITE with lower = -INFINITY and nothing is
+ *   evaluated for it; so is a segment at one of whose evaluations a probe centre is not finite, which ends there.  A row whose tested
+ *   geom poses are not finite has every segment NOT_FINITE.
+ * 7. Status, in this order: NOT_FINITE (6.); BUDGET (5.); BLOCKED: upper < margin (with BRACKET judged here, at the end); DEPTH;
+ *   CLEAR: lower >= margin; else UNDECIDED (the bracket is within tol).  row_status: the highest code of the row's segments;
+ *   row_first: the first segment that is not CLEAR, -1: none; row_lower, row_upper: the minima over the segments.
+ * 8. MIR_PLAN_IGNORE_COLLISION in pq: every segment is CLEAR with lower = upper = max_distance, nothing is evaluated.
+ * What the outputs mean.  For a segment that ends CLEAR or UNDECIDED, the continuous minimum over the segment of the sphere model's
+ *   clearance against the tested geoms (capped at max_distance) lies in [lower, upper], up to the float32 error of one clearance
+ *   evaluation, which `guard` is there to cover; and lower >= margin or upper - lower <= tol.  BLOCKED is a witness: one configuration
+ *   below the margin.  A DEPTH segment's lower is still a bound, only a wider one.
+ * Outputs, each nullable: seg_lower, seg_upper (R, K-1); seg_status (R, K-1); row_lower, row_upper, row_status, row_first (R); leaves
+ *   (R, max_leaves, 3): segment, level and index of the accepted leaves in the order they were accepted -- leaves beyond the capacity
+ *   are counted, not stored, and entries behind the count are not written; stats (R, 4): evaluations, leaves, deepest level, segments
+ *   whose bisection ran to its end.
+ * Every loop is bounded by K, the tree depth, max_depth or max_evaluations; no input can keep a wave running.
+ * MIR_E_INVALID: a NULL handle, q, pq, probes, dof_qadr or paths; struct_size != sizeof of a query; K < 2; max_depth outside 0 .. 20;
+ *   max_evaluations < 1; max_leaves < 0; leaves NULL while max_leaves > 0; an unknown flag bit; tol not finite; guard not finite or
+ *   negative; tol <= guard (the bracket could never close); a step is pending; everything mir_path_clearance refuses.  None of them
+ *   launches anything, mir_last_error() names the entry point; n_rows == 0, or every output NULL, returns MIR_OK without a launch.
+ * What it does not do.  The arm against itself and a carried object: both need a bound on RELATIVE motion, and stay sampled
+ *   (mir_path_clearance_self / _carry).  mir_plan_path does not use this rule for its own edges.  The chain bound is loose for
+ *   distal spheres when only proximal joints move (the chain is taken at full stretch).
+ * (Added struct and entry point: MIR_VERSION and every other struct and entry point stay as they are.) */
+#define MIR_CERT_BRACKET 1u /* MirCertQuery.flags: bracket the minimum to tol everywhere instead of stopping at "clear of the margin" */
+#define MIR_CERT_MAX_DEPTH 20
+#define MIR_CERT_CLEAR 0
+#define MIR_CERT_UNDECIDED 1
+#define MIR_CERT_DEPTH 2
+#define MIR_CERT_BUDGET 3
+#define MIR_CERT_BLOCKED 4
+#define MIR_CERT_NOT_FINITE 5
+typedef struct MirCertQuery {
+  int32_t  struct_size;      /* = sizeof(MirCertQuery) */
+  int32_t  num_points;       /* K >= 2 waypoints per row */
+  int32_t  max_depth;        /* 0 .. 20: the deepest level of the bisection */
+  int32_t  max_evaluations;  /* >= 1: clearance evaluations per row */
+  int32_t  max_leaves;       /* >= 0: the capacity of leaves per row */
+  uint32_t flags;            /* MIR_CERT_BRACKET; unknown bits are MIR_E_INVALID */
+  float    tol;              /* > guard: the width a bracket is closed to */
+  float    guard;            /* >= 0: subtracted from every bound, for the float32 error of an evaluation */
+} MirCertQuery;
+int mir_cert_query_sizeof(void);
+int mir_certify_path(MirHandle h, const MirCertQuery* q, const MirPlanQuery* pq, const float* probes, const int32_t* probe_link,
+                     const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start /* (R,nq) nullable */,
+                     const float* paths /* (R,K,D) */, float* seg_lower /* (R,K-1) */, float* seg_upper /* (R,K-1) */,
+                     int32_t* seg_status /* (R,K-1) */, float* row_lower /* (R) */, float* row_upper /* (R) */, int32_t* row_status /* (R) */,
+                     int32_t* row_first /* (R) */, int32_t* leaves /* (R,max_leaves,3) nullable */, int32_t* stats /* (R,4) nullable */,
+                     void* stream);
+
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
