@@ -8,7 +8,8 @@ Planning with a margin and certifying at margin 0 turns that into "no configurat
 is 1-Lipschitz in a sphere's centre and the kinematic chain bounds how fast a centre moves, so one evaluation bounds the clearance on a
 whole interval, which is bisected where the bound does not decide (include/mirigid.h: mir_certify_path).  Printed: per status how many
 envs, and the evaluations per env beside the samples the edge rule takes on the same paths.
-The certified rule covers the sphere model against the scene; the arm against itself is sampled only.
+This example certifies the sphere model against the scene; robot.certify_sweep(path, self_collision=True, attached_entity=...) also
+certifies the arm against itself and a carried object.
 """
 import argparse
 import os

@@ -179,6 +179,11 @@ def load_library() -> C.CDLL:
     lib.mir_cert_query_sizeof.restype = C.c_int
     lib.mir_certify_path.argtypes = [vp, C.POINTER(MirCertQuery), C.POINTER(MirPlanQuery), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_certify_path.restype = C.c_int
+    lib.mir_certify_path_self.argtypes = [vp, C.POINTER(MirCertQuery), C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), vp, vp, vp, vp, i32, vp, vp] + [vp] * 14
+    lib.mir_certify_path_self.restype = C.c_int
+    lib.mir_certify_path_carry.argtypes = [vp, C.POINTER(MirCertQuery), C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp,
+                                           vp, i32, vp, vp, vp] + [vp] * 15
+    lib.mir_certify_path_carry.restype = C.c_int
     for name in ("mir_create", "mir_destroy", "mir_get_dims", "mir_get_model_consts", "mir_reset", "mir_autoreset", "mir_set_pd_targets",
                  "mir_step", "mir_step_fused", "mir_get_obs", "mir_get_state", "mir_set_state", "mir_get_links",
                  "mir_get_diag", "mir_forward"):
@@ -1123,15 +1128,20 @@ class MirScene(StepHelpers):
 
     def certify_path(self, probes, links, dof_qadr, paths, env_idx=None, qpos_start=None, margin: float = 0.0, tol: float = 0.002,
                      guard: float = 1e-5, max_depth: int = 12, max_evaluations: int = 4096, bracket: bool = False, max_leaves: int = 0,
-                     max_distance: float = 1.0, skip_geoms=0, ignore_collision: bool = False) -> dict:
+                     max_distance: float = 1.0, skip_geoms=0, ignore_collision: bool = False, self_model=None, carry=None, grasp=None) -> dict:
         """mir_certify_path: the CONTINUOUS minimum clearance of the trajectories `paths` (R, K, D) over the planned dofs `dof_qadr`,
         bracketed per segment in ONE launch.  Where path_clearance() judges samples of a segment, this call judges all of it: the signed
         distance is 1-Lipschitz in a sphere's centre and a centre moves no faster than the kinematic chain allows, so one evaluation
         bounds the clearance on a whole interval, which is bisected where the bound does not decide (include/mirigid.h has the rule).
         `tol`: the width a bracket is closed to; `guard`: subtracted from every bound for the float32 error of an evaluation; `max_depth`
         (0 .. 20) and `max_evaluations` per row bound the work; `bracket`: close every bracket to `tol` instead of stopping at "clear of
-        `margin`"; `max_leaves`: the accepted leaves kept per row.  Everything else as path_clearance(); the self test and a carried
-        object are sampled only and have no place here.
+        `margin`"; `max_leaves`: the accepted leaves kept per row.  Everything else as path_clearance().
+        `self_model` and `carry` (the dicts of path_clearance(); `grasp` (R, 7) may also be given here in place of carry["grasp"]):
+        mir_certify_path_self / mir_certify_path_carry -- the self clearance (the lowest distance of an enabled pair of spheres, capped
+        at self_model["max_distance"]) is bracketed over the whole of every segment too, by a bound on the RELATIVE speed of two spheres
+        (only the joints below the lowest common ancestor of their links count), and the carried body's spheres ride along in both
+        tests.  The result gains seg_self_lower, seg_self_upper (R, K-1), row_self_lower, row_self_upper (R,) (+inf without a self
+        model) and grasp (R, 7) (NaN without a carried body); a status then speaks for both tests.
         -> dict of fresh device tensors: seg_lower, seg_upper (R, K-1), seg_status (R, K-1) int32 (spec.CERT_STATUS), row_lower,
         row_upper (R,), row_status, row_first (R,) int32 (the first segment that is not CLEAR, -1: none), stats (R, 4) int32:
         evaluations, leaves, deepest level, segments finished; with max_leaves > 0 also leaves (R, max_leaves, 3) int32: segment, level,
@@ -1143,13 +1153,43 @@ class MirScene(StepHelpers):
             raise ValueError(f"paths must be ({R}, K >= 2, {D}), got {tuple(paths.shape)}")
         K = int(paths.shape[1])
         q = make_cert_query(K, tol, guard, max_depth, max_evaluations, bracket, max_leaves)
-        pq = make_plan_query(int(p.shape[0]), D, ignore_collision=ignore_collision, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
+        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
+        pq = make_plan_query(N, D, ignore_collision=ignore_collision, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
         new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
         i32 = torch.int32
         out = {"seg_lower": new(K - 1), "seg_upper": new(K - 1), "seg_status": new(K - 1, dtype=i32), "row_lower": new(), "row_upper": new(),
                "row_status": new(dtype=i32), "row_first": new(dtype=i32), "stats": new(4, dtype=i32)}
         if int(max_leaves) > 0:
             out["leaves"] = torch.full((R, int(max_leaves), 3), -1, dtype=i32, device=self.device)
+        if self_model is not None or carry is not None or grasp is not None:
+            if grasp is not None:
+                if carry is None:
+                    raise ValueError("grasp belongs to carry, which is None")
+                carry = {**carry, "grasp": grasp}
+            if sq is not None:
+                out.update(seg_self_lower=new(K - 1), seg_self_upper=new(K - 1), row_self_lower=new(), row_self_upper=new())
+            else:
+                inf = lambda *shape: torch.full((R, *shape), float("inf"), dtype=torch.float32, device=self.device)  # noqa: E731
+                out.update(seg_self_lower=inf(K - 1), seg_self_upper=inf(K - 1), row_self_lower=inf(), row_self_upper=inf())
+            cq, g = None, None
+            if carry is not None:
+                cq, g, out["grasp"] = self._carry_query(carry, R)
+            else:
+                out["grasp"] = torch.full((R, 7), float("nan"), dtype=torch.float32, device=self.device)
+            if R > 0:
+                lkp = None if lk is None else lk.ctypes.data_as(C.c_void_p)
+                so = [_ptr(out[k]) if sq is not None else None for k in ("seg_self_lower", "seg_self_upper", "row_self_lower", "row_self_upper")]
+                head = (self.h, C.byref(q), C.byref(pq), None if sq is None else C.byref(sq))
+                front = (_ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start))
+                outs = (_ptr(out["seg_lower"]), _ptr(out["seg_upper"]), so[0], so[1], _ptr(out["seg_status"]), _ptr(out["row_lower"]),
+                        _ptr(out["row_upper"]), so[2], so[3], _ptr(out["row_status"]), _ptr(out["row_first"]))
+                tail = (_ptr(out.get("leaves")), _ptr(out["stats"]), self._stream())
+                if cq is None:
+                    self._check(self.lib.mir_certify_path_self(*head, *front, _ptr(paths), *outs, *tail))
+                else:
+                    self._check(self.lib.mir_certify_path_carry(*head, C.byref(cq), *front, _ptr(g), _ptr(paths), *outs, _ptr(out["grasp"]), *tail))
+                self.cert_launches = self.__dict__.get("cert_launches", 0) + 1
+            return out
         if R > 0:   # (without rows there is nothing to point at)
             self._check(self.lib.mir_certify_path(self.h, C.byref(q), C.byref(pq), _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p),
                                                   qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(paths), _ptr(out["seg_lower"]),

@@ -665,7 +665,7 @@ CERT_BRACKET = 1
 
 
 class MirCertQuery(C.Structure):
-    """include/mirigid.h: MirCertQuery (mir_certify_path)"""
+    """include/mirigid.h: MirCertQuery (mir_certify_path, mir_certify_path_self, mir_certify_path_carry)"""
     _fields_ = [
         ("struct_size", C.c_int32),
         ("num_points", C.c_int32),

@@ -982,11 +982,11 @@ class EntityView:
         `envs_idx`, `with_entity`, `ignore_entities` as in get_path_clearance.  return_detail=True: a dict with status, first (R,) the
         first segment that is not CLEAR (-1: none), lower, upper (R,), seg_lower, seg_upper, seg_status (R, K-1), stats (R, 4):
         evaluations, leaves, deepest level, segments finished, and with max_leaves > 0 leaves (R, max_leaves, 3).
-        What it does not do: the arm against itself and a carried object need a bound on relative motion; they are sampled only
-        (get_path_clearance), so `self_collision=True` or an `attached_entity` is refused."""
+        What it does not do: the arm against itself and a carried object need a bound on relative motion; this method keeps to the
+        scene test, so `self_collision=True` or an `attached_entity` is refused: certify_sweep() certifies all three."""
         if self_collision or attached_entity is not None:
             raise ValueError("certify_path: the self and carried-object tests are sampled only (get_path_clearance); the certified rule "
-                             "covers the sphere model against the static scene")
+                             "covers the sphere model against the static scene -- certify_sweep() certifies all three")
         args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "certify_path", False)
         if getattr(self._mir, "certify_path", None) is None:
             raise NotImplementedError("this scene has no certified clearance (MirScene.certify_path / mir_certify_path)")
@@ -1011,6 +1011,54 @@ class EntityView:
         trajectory.  False is "not proven": BLOCKED is a found collision, the other statuses say what ran out."""
         kwargs.pop("return_detail", None)
         return self.certify_path(path, margin=margin, **kwargs) == 0
+
+    # ---- certified clearance with the self test and a carried object (MirScene.certify_path(self_model=, carry=) / mir_certify_path_self,
+    # mir_certify_path_carry): what plan_path(self_collision=True, attached_entity=...) plans, certified for the whole of every segment.
+    def certify_sweep(self, path, margin=0.0, self_margin=0.0, tol=0.002, guard=1e-5, max_depth=12, max_evaluations=4096, bracket=False,
+                      max_leaves=0, max_distance=1.0, envs_idx=None, qpos_start=None, with_entity=None, ignore_entities=(), self_collision=None,
+                      attached_entity=None, ee_link_name=None, grasp_pose=None, attached_links=None, return_detail=False):
+        """``robot.certify_sweep(path, self_collision=True, attached_entity=cube, ee_link_name="hand")`` -> (R,) int32, spec.CERT_STATUS:
+        certify_path() with the tests it refuses.  0 CLEAR -- along the WHOLE trajectory `path` ((K, R, n)) the sphere model keeps `margin`
+        from every tested geom AND, with `self_collision` (None: the scene's enable_self_collision option), `self_margin` between the
+        spheres of the self model AND, with `attached_entity` / `ee_link_name` / `grasp_pose` / `attached_links` (the carried object of
+        plan_path()), the object's spheres keep `margin` from the scene and `self_margin` from the arm.  4 BLOCKED: a configuration
+        below either margin was found; the other statuses as certify_path().  ONE launch for all rows (mir_certify_path_self / _carry,
+        where the bound on the relative speed of two spheres is written down).  The arguments go through the same path as those of
+        get_path_clearance().  return_detail=True: the dict of certify_path() plus self_lower, self_upper (R,), seg_self_lower,
+        seg_self_upper (R, K-1) (+inf when neither a self model nor a carried object is in play) and grasp (R, 7) (NaN without a carried
+        object).  Without self test and carried object this is certify_path()."""
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "certify_sweep", self_collision, self_margin, attached_entity,
+                                  ee_link_name, grasp_pose, attached_links)
+        if getattr(self._mir, "certify_path", None) is None:
+            raise NotImplementedError("this scene has no certified clearance (MirScene.certify_path / mir_certify_path)")
+        p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
+        if self.__dict__.get("unbatched") and p.dim() == 2:
+            p = p[:, None]
+        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != len(self._qcols) or p.shape[0] < 2:
+            raise ValueError(f"path must be (K >= 2, {R}, {len(self._qcols)}), got {tuple(p.shape)}")
+        K = int(p.shape[0])
+        r = self._mir.certify_path(paths=p.permute(1, 0, 2).contiguous(), margin=float(margin), tol=float(tol), guard=float(guard),
+                                   max_depth=int(max_depth), max_evaluations=int(max_evaluations), bracket=bool(bracket),
+                                   max_leaves=int(max_leaves), max_distance=max(float(max_distance), 2.0 * float(margin)), **args)
+        dev = self._mir.device
+        inf = lambda *shape: torch.full((R, *shape), float("inf"), dtype=torch.float32, device=dev)  # noqa: E731
+        out = {"status": r["row_status"], "first": r["row_first"], "lower": r["row_lower"], "upper": r["row_upper"], "seg_lower": r["seg_lower"],
+               "seg_upper": r["seg_upper"], "seg_status": r["seg_status"], "stats": r["stats"],
+               "self_lower": r["row_self_lower"] if "row_self_lower" in r else inf(), "self_upper": r["row_self_upper"] if "row_self_upper" in r else inf(),
+               "seg_self_lower": r["seg_self_lower"] if "seg_self_lower" in r else inf(K - 1),
+               "seg_self_upper": r["seg_self_upper"] if "seg_self_upper" in r else inf(K - 1),
+               "grasp": r["grasp"] if "grasp" in r else torch.full((R, 7), float("nan"), dtype=torch.float32, device=dev)}
+        if "leaves" in r:
+            out["leaves"] = r["leaves"]
+        if self.__dict__.get("unbatched"):
+            out = {k: v[0] for k, v in out.items()}
+        return out if return_detail else out["status"]
+
+    def sweep_is_certified_clear(self, path, **kwargs) -> torch.Tensor:
+        """(R,) bool: certify_sweep(path, ...) is CLEAR -- proven clear of the scene, of itself and with what it carries along the
+        whole trajectory.  False is "not proven": BLOCKED is a found collision, the other statuses say what ran out."""
+        kwargs.pop("return_detail", None)
+        return self.certify_sweep(path, **kwargs) == 0
 
     # ---- straight-line end-effector paths (MirScene.cartesian_path / mir_cartesian_path): the approach, the lift and the place of a
     # grasp.  The name and the arguments are this package's own (MoveIt: computeCartesianPath): parity with Genesis is unpinned.

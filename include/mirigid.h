@@ -1234,8 +1234,8 @@ int mir_blend_path(MirHandle h, const MirBlendQuery* q, const MirPlanQuery* pq, 
  *   max_evaluations < 1; max_leaves < 0; leaves NULL while max_leaves > 0; an unknown flag bit; tol not finite; guard not finite or
  *   negative; tol <= guard (the bracket could never close); a step is pending; everything mir_path_clearance refuses.  None of them
  *   launches anything, mir_last_error() names the entry point; n_rows == 0, or every output NULL, returns MIR_OK without a launch.
- * What it does not do.  The arm against itself and a carried object: both need a bound on RELATIVE motion, and stay sampled
- *   (mir_path_clearance_self / _carry).  mir_plan_path does not use this rule for its own edges.  The chain bound is loose for
+ * What it does not do.  The arm against itself and a carried object need a bound on RELATIVE motion: that is mir_certify_path_self /
+ *   _carry below, not this entry point.  mir_plan_path does not use this rule for its own edges.  The chain bound is loose for
  *   distal spheres when only proximal joints move (the chain is taken at full stretch).
  * (Added struct and entry point: MIR_VERSION and every other struct and entry point stay as they are.) */
 #define MIR_CERT_BRACKET 1u /* MirCertQuery.flags: bracket the minimum to tol everywhere instead of stopping at "clear of the margin" */
@@ -1263,6 +1263,84 @@ int mir_certify_path(MirHandle h, const MirCertQuery* q, const MirPlanQuery* pq,
                      int32_t* seg_status /* (R,K-1) */, float* row_lower /* (R) */, float* row_upper /* (R) */, int32_t* row_status /* (R) */,
                      int32_t* row_first /* (R) */, int32_t* leaves /* (R,max_leaves,3) nullable */, int32_t* stats /* (R,4) nullable */,
                      void* stream);
+
+/* ---- certified clearance: self and carried object -----------------------------------------------------------------
+ * `robot.certify_sweep(path, self_collision=True, attached_entity=cube, ...)`: mir_certify_path with the two tests it left sampled.
+ * For R rows ONE launch (mir_certrel.hip, one wave64 per row) brackets, per segment, the continuous minimum of the scene clearance
+ * (exactly as mir_certify_path, the carried body's spheres included) AND of the self clearance of mir_path_clearance_self / _carry:
+ * the lowest s_ij = |x_i - x_j| - (r_i + r_j) over the enabled pairs of the N + E spheres, capped at self_max = sq->max_distance.
+ * Why it holds.  Take sphere i on link a (local centre c_i) and sphere j on link b, D = x_i - x_j.
+ *   1. s_ij = |D| - (r_i + r_j) and d|D|/dt = D^ . (x_i' - x_j').
+ *   2. Along q(t) = a + t dq a planned joint k on the path to the world of BOTH links adds nothing to d|D|/dt: a revolute one adds
+ *      dq_k w_k x D to the relative velocity, which is perpendicular to D; a prismatic one adds 0.
+ *   3. Only the joints strictly below c = lca(a, b), on either branch, count.
+ *   4. Hence |d s_ij / dt| <= v_ij = rel(i, c) + rel(j, c), with rel(i, c) the sum over the planned dofs k of the bodies from a up
+ *      to, not including, c of |dq_k| (S[a] - S[body_k] + |c_i|) for a revolute k and |dq_k| |axis_k| for a prismatic one: the rho_ik
+ *      of mir_certify_path, restricted to the branch.
+ *   5. Links in different chains (c = the world, or a chain start that is not common): nothing is restricted.  6. a == c: rel(i, c) = 0.
+ *   7. Capping at self_max keeps the Lipschitz property, so 8. min(s_ij(t), self_max) >= min(s_ij(tm), self_max) - |t - tm| v_ij, and
+ *   9. one evaluation at the midpoint of an interval bounds every enabled pair on all of it, as for the scene test.
+ *   A carried body C follows link Lk by the rigid grasp G = (p_G, q_G) of the row, so its spheres are spheres of Lk with local centre
+ *   p_G + R_G c_i, whose norm is at most cn_i = |p_G| + |c_i| (this bound is used: no rotation enters the rounding).  In the scene test
+ *   a probe on C gets cert_speed(S[Lk], cn_i, A[Lk], B[Lk], P[Lk]); in the pair test it counts as sitting on Lk for the LCA, while its
+ *   mask row stays link_mask[C].
+ * Arguments mean what they mean in mir_certify_path and mir_path_clearance_self / _carry: N = pq->n_probes probes take the scene test,
+ *   N + sq->n_extra the pair test under sq->link_mask at sq->self_margin; cq names C and Lk, C's geoms are in pq->skip_geoms; grasp
+ *   (R, 7) nullable: from the start row; grasp_used (R, 7) nullable.
+ * Rule per row and segment: that of mir_certify_path with two brackets.
+ *   1., 2. as there, with cn_i above for the probes on C, plus the branch sums: per body a and per count t = 0 .. depth(a) + 1 of
+ *     bodies walked from a upward (k = a, parent(a), ...: the order is part of the rule), three non-negative float32 sums dA = sum
+ *     |dq_k| over revolute k, dSB = sum |dq_k| (S[a] - S[body_k]) over revolute k, dP = sum |dq_k| |axis_k| over prismatic k; each
+ *     difference, product and sum is one rounding (no fused multiply-add).  They are NOT formed as differences of A, B, P: the
+ *     cancellation would make the error absolute, which the factor 1.0001 does not cover.  rel(i, c) = (cn_i dA + dSB) + dP at t =
+ *     the bodies from a up to, not including, c (all of the chain when there is no common ancestor; none for the world);
+ *     v_ij = (rel(i, c) + rel(j, c)) 1.0001, never below 0.
+ *   3., 4. Every evaluation (endpoints with hw = 0, nodes) yields u = min_i d_i and m = min_i (d_i - hw v_i) over the first N probes,
+ *     as mir_certify_path, and in the float32 arithmetic of mir_path_clearance_self u_s = min(self_max, lowest s_ij) and m_s = the
+ *     lowest min(s_ij, self_max) - hw v_ij over the enabled pairs (no enabled pair: u_s = m_s = self_max).  upper = min(upper, u),
+ *     upper_s = min(upper_s, u_s), lo = m - guard, lo_s = m_s - guard.  Witness (not with BRACKET): u < margin or u_s < self_margin
+ *     ends the segment BLOCKED, both lowers lowered by this evaluation's lo and lo_s.  A node is a LEAF when the leaf test of
+ *     mir_certify_path holds for (lo, upper, margin) AND for (lo_s, upper_s, self_margin).  max_depth, DEPTH, the dyadic successor
+ *     and the budget (an evaluation is a configuration) are as there.
+ *   5., 6. BUDGET and NOT_FINITE as there, both lowers -INFINITY; any of the N + E centres not finite ends the segment NOT_FINITE; a
+ *     grasp that is not finite (or a given quaternion of squared norm < 1e-30) makes every segment of the row NOT_FINITE.
+ *   7. Status, in this order: NOT_FINITE; BUDGET; BLOCKED: upper < margin || upper_s < self_margin; DEPTH; CLEAR: lower >= margin &&
+ *     lower_s >= self_margin; else UNDECIDED.  With sq NULL the self half of every conjunction is absent.
+ *   8. MIR_PLAN_IGNORE_COLLISION: CLEAR with lower = upper = max_distance and lower_s = upper_s = self_max.
+ * Identity.  mir_certify_path_carry with sq NULL and no probe on C returns the bytes of mir_certify_path; so does
+ *   mir_certify_path_self with an all-zero mask and n_extra = 0 in the scene outputs, the leaves and the stats.
+ * Outputs: those of mir_certify_path, plus seg_self_lower, seg_self_upper (R, K-1), row_self_lower, row_self_upper (R), each nullable.
+ * Every loop is bounded by K, nbody, N + E, max_depth or max_evaluations; no input can keep a wave running.
+ * Refusals, none of which launches anything, in this order:
+ *   a. those of mir_certify_path's own query ("null argument" ... "tol <= guard (the bracket could never close)");
+ *   b. _self with sq NULL: "null self query"; _carry with sq and cq both NULL: "neither a MirSelfQuery nor a MirCarryQuery
+ *      (mir_certify_path judges the scene test alone)"; sq NULL with a self output: "seg_self_lower / seg_self_upper / row_self_lower /
+ *      row_self_upper without a MirSelfQuery"; cq NULL with grasp: "grasp without a MirCarryQuery"; with grasp_used: "grasp_used without
+ *      a MirCarryQuery";
+ *   c. everything mir_path_clearance_self / _carry refuses (the self query first, then the plan query, the rows, the probes, the dofs,
+ *      the carry query);
+ *   d. MIR_E_CAPACITY: "rows x max(num_points x n_dofs, 3 max_leaves) beyond 2^31 - 1"; then the LDS of a row, F + 4 N + 4 (N + E), plus
+ *      16 (N + E) with sq, with F = 24864 bytes fixed, beyond 65536: "the speed bounds and the sphere list do not fit 64 KB of LDS
+ *      (n_probes, n_probes + n_extra)" (with at most 1024 probes per call it always fits today).
+ *   n_rows == 0, or every output NULL, returns MIR_OK without a launch.
+ * What it does not do.  mir_plan_path does not use this rule for its own edges.  The lever is the chain at full stretch, not the
+ *   configuration's.  Link geoms other than spheres do not enter the pair test.
+ * (Added entry points: MIR_VERSION and every struct and other entry point stay as they are.) */
+int mir_certify_path_self(MirHandle h, const MirCertQuery* q, const MirPlanQuery* pq, const MirSelfQuery* sq, const float* probes,
+                          const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows,
+                          const float* qpos_start /* (R,nq) nullable */, const float* paths /* (R,K,D) */, float* seg_lower /* (R,K-1) */,
+                          float* seg_upper /* (R,K-1) */, float* seg_self_lower /* (R,K-1) */, float* seg_self_upper /* (R,K-1) */,
+                          int32_t* seg_status /* (R,K-1) */, float* row_lower /* (R) */, float* row_upper /* (R) */,
+                          float* row_self_lower /* (R) */, float* row_self_upper /* (R) */, int32_t* row_status /* (R) */,
+                          int32_t* row_first /* (R) */, int32_t* leaves /* (R,max_leaves,3) nullable */, int32_t* stats /* (R,4) nullable */,
+                          void* stream);
+int mir_certify_path_carry(MirHandle h, const MirCertQuery* q, const MirPlanQuery* pq, const MirSelfQuery* sq /* nullable */,
+                           const MirCarryQuery* cq /* nullable */, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+                           const int64_t* env_idx, int32_t n_rows, const float* qpos_start /* (R,nq) nullable */,
+                           const float* grasp /* (R,7) nullable */, const float* paths /* (R,K,D) */, float* seg_lower, float* seg_upper,
+                           float* seg_self_lower, float* seg_self_upper, int32_t* seg_status, float* row_lower, float* row_upper,
+                           float* row_self_lower, float* row_self_upper, int32_t* row_status, int32_t* row_first,
+                           float* grasp_used /* (R,7) nullable */, int32_t* leaves, int32_t* stats, void* stream);
 
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
