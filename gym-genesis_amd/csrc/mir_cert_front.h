@@ -78,6 +78,7 @@ CERT_HD bool cert_leaf(float lo, float upper, float margin, float tol, bool brac
 }
 
 // the status of a segment (step 7); `budget` and `not_finite` as steps 5 and 6 set them, `depth`: a node at max_depth failed both tests
+// (the scene test alone: certrel_status() of mir_certrel_front.h with self == false, which is what the kernel calls)
 CERT_HD int cert_status(bool not_finite, bool budget, bool depth, float lower, float upper, float margin) {
   if (not_finite) return MIR_CERT_NOT_FINITE;
   if (budget) return MIR_CERT_BUDGET;

@@ -1,9 +1,9 @@
 // mir_certrel_front.h — the host-side checks of mir_certify_path_self / mir_certify_path_carry and the scalar part of the relative-motion
-// rule (mir_certrel.hip; include/mirigid.h, "certified clearance: self and carried object"): plain C++, no HIP in it, so that
+// rule (mir_cert.hip, the instantiations with SELF or CARRY; include/mirigid.h, "certified clearance: self and carried object"): plain C++, no HIP in it, so that
 // tests/certrel_host.cpp builds it with g++ (`make certrel-host`) and tests/test_certrel_cpu.py walks every refusal and compares the
 // branch sums, the pair speed bound and the LCA table with the NumPy port without a device.  The kernel calls the same scalar functions
 // (CERT_HD makes them device functions under hipcc); certrel_branch() below is the same walk over arrays, for the host.
-// It stands on mir_cert_front.h (the bisection, the leaf tests, the chain recurrences), which keeps its text.
+// It stands on mir_cert_front.h (the bisection, the leaf tests, the chain recurrences).
 // Every product stands in a statement of its own, so that no build fuses it with the sum behind it.
 // A refusal is `refuse(code, text)`: the caller's, which names the entry point.  The order of the checks and their texts are part of
 // the interface.
@@ -86,7 +86,8 @@ CERT_HD float certrel_pair_bound(float s, float self_max, float hw, float v) {
   return cap - reach;
 }
 
-// the status of a segment with both tests (self: a MirSelfQuery was given); the order of mir_certify_path
+// the status of a segment with both tests (self: a MirSelfQuery was given); the order of mir_certify_path: without `self` it is
+// cert_status().  The one the kernel calls, in every instantiation
 CERT_HD int certrel_status(bool not_finite, bool budget, bool depth, float lower, float upper, float margin, bool self, float lower_s, float upper_s,
                            float self_margin) {
   if (not_finite) return MIR_CERT_NOT_FINITE;

@@ -1266,7 +1266,7 @@ int mir_certify_path(MirHandle h, const MirCertQuery* q, const MirPlanQuery* pq,
 
 /* ---- certified clearance: self and carried object -----------------------------------------------------------------
  * `robot.certify_sweep(path, self_collision=True, attached_entity=cube, ...)`: mir_certify_path with the two tests it left sampled.
- * For R rows ONE launch (mir_certrel.hip, one wave64 per row) brackets, per segment, the continuous minimum of the scene clearance
+ * For R rows ONE launch (mir_cert.hip, one wave64 per row) brackets, per segment, the continuous minimum of the scene clearance
  * (exactly as mir_certify_path, the carried body's spheres included) AND of the self clearance of mir_path_clearance_self / _carry:
  * the lowest s_ij = |x_i - x_j| - (r_i + r_j) over the enabled pairs of the N + E spheres, capped at self_max = sq->max_distance.
  * Why it holds.  Take sphere i on link a (local centre c_i) and sphere j on link b, D = x_i - x_j.

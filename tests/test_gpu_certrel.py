@@ -300,7 +300,9 @@ def test_a_given_grasp_against_the_one_from_the_start_row():
 
 def test_identities_with_the_scene_only_entry_point():
     """e. byte for byte against mir_certify_path: _carry without a self query and without a probe on the carried body; _self with an
-    all-zero mask and no extra sphere (scene outputs, leaves, stats)"""
+    all-zero mask and no extra sphere (scene outputs, leaves, stats); the same on the budget, depth and nan inputs of tests/cert_cases.py,
+    so that BUDGET, DEPTH and NOT_FINITE cross the three instantiations too"""
+    zero = dict(link_mask=np.zeros(32, np.uint32), n_extra=0, self_margin=0.0, max_distance=1.0)
     for name in ("carry_under", "carry_clear"):
         c, sc = rc.case(name), _scene(name)
         n = c["n_arm"]
@@ -310,13 +312,36 @@ def test_identities_with_the_scene_only_entry_point():
         for k in plain:
             assert carry[k].tobytes() == plain[k].tobytes(), (name, k)
         assert np.isposinf(carry["seg_self_lower"]).all() and np.isfinite(carry["grasp"]).all()
-        zero = dict(link_mask=np.zeros(32, np.uint32), n_extra=0, self_margin=0.0, max_distance=1.0)
         own = {k: v.cpu().numpy() for k, v in sc.certify_path(paths=c["paths"], self_model=zero, **kw).items()}
         for k in SCENE_KEYS:
             assert own[k].tobytes() == plain[k].tobytes(), (name, k)
         assert np.array_equal(own["seg_status"], plain["seg_status"])
         done = plain["seg_status"] != S.CERT_BLOCKED
         assert (own["seg_self_upper"] == 1.0).all() and (own["seg_self_lower"][done] == np.float32(1.0) - np.float32(rc.GUARD)).all()
+    # BUDGET, DEPTH and NOT_FINITE with their -inf lowers, on the inputs of tests/cert_cases.py: the carried body is the cube on the floor,
+    # which no probe sits on (its geom skipped in all three calls), the self model an all-zero mask
+    import cert_cases
+
+    from gym_genesis.backend.lib import MirScene
+
+    sb = cert_cases.case("budget")["sb"]
+    sc = MirScene(cert_cases.case("budget")["spec"], B)
+    cube = carry_cases.EntityView(sc, sb, "cube", ())
+    want = {"budget": S.CERT_BUDGET, "depth": S.CERT_DEPTH, "nan": S.CERT_NOT_FINITE}
+    for name in want:
+        c = cert_cases.case(name)
+        sc.set_state(qpos=c["q"], qvel=np.zeros((B, sc.nv), np.float32))
+        kw = dict(probes=c["probes"], links=c["links"], dof_qadr=c["qadr"], skip_geoms=c["skip"] | cube._own_geoms(), max_leaves=MAX_LEAVES, **c["par"])
+        plain = {k: v.cpu().numpy() for k, v in sc.certify_path(paths=c["paths"], **kw).items()}
+        assert (plain["seg_status"] == want[name]).any(), (name, plain["seg_status"])
+        assert name == "depth" or np.isneginf(plain["seg_lower"][plain["seg_status"] == want[name]]).all()
+        carry = {k: v.cpu().numpy() for k, v in sc.certify_path(paths=c["paths"], carry=dict(body=sb.body_index("cube"), link=sb.body_index("hand")), **kw).items()}
+        for k in plain:
+            assert carry[k].tobytes() == plain[k].tobytes(), (name, k)
+        own = {k: v.cpu().numpy() for k, v in sc.certify_path(paths=c["paths"], self_model=zero, **kw).items()}
+        for k in SCENE_KEYS + ("seg_status", "row_status", "row_first"):
+            assert own[k].tobytes() == plain[k].tobytes(), (name, k)
+        assert np.isneginf(own["seg_self_lower"][np.isin(plain["seg_status"], (S.CERT_BUDGET, S.CERT_NOT_FINITE))]).all()
 
 
 def test_addressing():
