@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirCartQuery, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirBlendQuery, MirCarryQuery, MirCertQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_blend_query, make_carry_query, make_cart_query, make_cert_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
+from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirCartQuery, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirBlendQuery, MirOptQuery, MirCarryQuery, MirCertQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_blend_query, make_opt_query, make_carry_query, make_cart_query, make_cert_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -176,6 +176,10 @@ def load_library() -> C.CDLL:
     lib.mir_blend_path.argtypes = [vp, C.POINTER(MirBlendQuery), C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp,
                                    vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_blend_path.restype = C.c_int
+    lib.mir_opt_query_sizeof.restype = C.c_int
+    lib.mir_optimize_path.argtypes = [vp, C.POINTER(MirOptQuery), C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp,
+                                      vp, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_optimize_path.restype = C.c_int
     lib.mir_cert_query_sizeof.restype = C.c_int
     lib.mir_certify_path.argtypes = [vp, C.POINTER(MirCertQuery), C.POINTER(MirPlanQuery), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_certify_path.restype = C.c_int
@@ -214,6 +218,8 @@ def load_library() -> C.CDLL:
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCartQuery (rebuild the library)")
     if lib.mir_blend_query_sizeof() != C.sizeof(MirBlendQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirBlendQuery (rebuild the library)")
+    if lib.mir_opt_query_sizeof() != C.sizeof(MirOptQuery):
+        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirOptQuery (rebuild the library)")
     if lib.mir_cert_query_sizeof() != C.sizeof(MirCertQuery):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCertQuery (rebuild the library)")
     if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
@@ -1287,6 +1293,47 @@ class MirScene(StepHelpers):
                                                 _ptr(qpos_start), _ptr(poly), _ptr(n_poly), _ptr(out["points"]), _ptr(out["n_points"]), _ptr(out["status"]),
                                                 _ptr(out.get("path")), _ptr(out["blend_len"]), _ptr(out["stats"]), self._stream()))
             self.blend_launches = self.__dict__.get("blend_launches", 0) + 1
+        return out
+
+    def optimize_path(self, probes, links, dof_qadr, paths, env_idx=None, qpos_start=None, smooth_weight=None, obstacle_weight=None,
+                      activation=None, step=None, max_iterations=None, max_halvings=None, ftol=None, ignore_collision: bool = False,
+                      resolution: float = 0.05, margin: float = 0.0, max_distance: float = 1.0, skip_geoms=0, self_model=None, carry=None,
+                      grad0: bool = False) -> dict:
+        """mir_optimize_path: for the envs `env_idx` (None: all), ONE launch takes each row's joint path `paths` (R, K, D) -- 3 <= K <= 128
+        waypoints over the planned dofs `dof_qadr`, the layout plan_path()["path"] and blend_path()["path"] have -- as a seed and moves
+        its interior waypoints by covariant gradient descent (CHOMP's update) with a backtracking line search on U = `smooth_weight` S +
+        `obstacle_weight` O: S the discrete integral of |q'|^2, O the sum over the interior waypoints and the spheres of a cost that is
+        zero from `activation` metres beyond `margin` outwards, quadratic in that band and linear inside the margin (include/mirigid.h
+        has the rule).  `step`: the first step length of every iteration, halved up to `max_halvings` times while U does not fall;
+        `max_iterations`; `ftol`: the relative decrease of U below which a row has converged.  None: spec.OPT_DEFAULTS.  The result is
+        swept like an edge of plan_path() (the sphere model, `resolution`, `margin`, `skip_geoms`, `self_model` and `carry` =
+        dict(body, link) exactly as in path_clearance(); the grasp is taken from the start row, `qpos_start` (R, nq) or the current
+        state): a row whose result does not pass returns its input, bit for bit.  The ends never move.
+        -> dict of fresh device tensors: path (R, K, D), status (R,) int32 (spec.OPT_STATUS), cost (R, 4): S and O of the input, S and O
+        of what the descent reached, stats (R, 6) int32: iterations, accepted steps, halvings, configurations evaluated in the descent,
+        configurations checked in the sweep, stop (spec.OPT_STOP), min_d (R,): the lowest distance beyond the margin of a sphere at an
+        interior waypoint of `path`; with `grad0` also grad0 (R, K, D): the gradient of U at the input (a test hook).  The call changes
+        nothing a later call can see."""
+        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
+        D = int(qa.shape[0])
+        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
+        paths = torch.as_tensor(paths, device=self.device).to(torch.float32).contiguous()
+        if paths.dim() != 3 or paths.shape[0] != R or paths.shape[2] != D:
+            raise ValueError(f"paths must be ({R}, K, {D}), got {tuple(paths.shape)}")
+        K = int(paths.shape[1])
+        q = make_opt_query(K, smooth_weight, obstacle_weight, activation, step, max_iterations, max_halvings, ftol)
+        pq = make_plan_query(N, D, ignore_collision=ignore_collision, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
+        cq = None if carry is None else make_carry_query(carry["body"], carry["link"])
+        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        out = {"path": new(K, D), "status": new(dtype=torch.int32), "cost": new(4), "stats": new(6, dtype=torch.int32), "min_d": new()}
+        if grad0:
+            out["grad0"] = new(K, D)
+        if R > 0:   # (without rows there is nothing to point at)
+            self._check(self.lib.mir_optimize_path(self.h, C.byref(q), C.byref(pq), None if sq is None else C.byref(sq), None if cq is None else C.byref(cq),
+                                                   _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p), qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
+                                                   _ptr(qpos_start), _ptr(paths), K, _ptr(out["path"]), _ptr(out["status"]), _ptr(out["cost"]),
+                                                   _ptr(out["stats"]), _ptr(out["min_d"]), _ptr(out.get("grad0")), self._stream()))
+            self.opt_launches = self.__dict__.get("opt_launches", 0) + 1
         return out
 
     def retime_path(self, paths, vmax, amax, dt, num_samples: int = 0, max_path_speed=None, extra=None, velocity: bool = False) -> dict:

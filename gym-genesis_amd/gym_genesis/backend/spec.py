@@ -659,6 +659,44 @@ def make_blend_query(num_nodes: int, max_deviation: float = 0.05, blend_points: 
     return q
 
 
+OPT_STATUS = {0: "OK", 48: "BLOCKED", 49: "BLOCKED_SELF", 50: "NOT_FINITE", 51: "NO_MOTION", 52: "OUT_OF_LIMITS"}   # mir_optimize_path
+OPT_BLOCKED, OPT_BLOCKED_SELF, OPT_NOT_FINITE, OPT_NO_MOTION, OPT_OUT_OF_LIMITS = range(48, 53)
+OPT_STOP = {0: "NONE", 1: "ITERATIONS", 2: "CONVERGED", 3: "STALLED"}
+OPT_STOP_NONE, OPT_STOP_ITERATIONS, OPT_STOP_CONVERGED, OPT_STOP_STALLED = range(4)
+# the defaults of optimize_path: parameters, chosen on the float64 reference (Trajectory optimisation, "the defaults")
+OPT_DEFAULTS = dict(smooth_weight=1.0, obstacle_weight=5.0, activation=0.05, step=0.25, max_iterations=50, max_halvings=6, ftol=1e-4)
+
+
+class MirOptQuery(C.Structure):
+    """include/mirigid.h: MirOptQuery (mir_optimize_path)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("num_waypoints", C.c_int32),
+        ("max_iterations", C.c_int32),
+        ("max_halvings", C.c_int32),
+        ("flags", C.c_uint32),
+        ("smooth_weight", C.c_float),
+        ("obstacle_weight", C.c_float),
+        ("step", C.c_float),
+        ("activation", C.c_float),
+        ("ftol", C.c_float),
+    ]
+
+
+def make_opt_query(num_waypoints: int, smooth_weight=None, obstacle_weight=None, activation=None, step=None, max_iterations=None,
+                   max_halvings=None, ftol=None) -> MirOptQuery:
+    """None: the value of OPT_DEFAULTS"""
+    given = dict(smooth_weight=smooth_weight, obstacle_weight=obstacle_weight, activation=activation, step=step, max_iterations=max_iterations,
+                 max_halvings=max_halvings, ftol=ftol)
+    v = {k: OPT_DEFAULTS[k] if x is None else x for k, x in given.items()}
+    q = MirOptQuery()
+    q.struct_size = C.sizeof(MirOptQuery)
+    q.num_waypoints, q.max_iterations, q.max_halvings, q.flags = int(num_waypoints), int(v["max_iterations"]), int(v["max_halvings"]), 0
+    q.smooth_weight, q.obstacle_weight, q.step = float(v["smooth_weight"]), float(v["obstacle_weight"]), float(v["step"])
+    q.activation, q.ftol = float(v["activation"]), float(v["ftol"])
+    return q
+
+
 CERT_STATUS = {0: "CLEAR", 1: "UNDECIDED", 2: "DEPTH", 3: "BUDGET", 4: "BLOCKED", 5: "NOT_FINITE"}   # mir_certify_path, by severity
 CERT_CLEAR, CERT_UNDECIDED, CERT_DEPTH, CERT_BUDGET, CERT_BLOCKED, CERT_NOT_FINITE = range(6)
 CERT_BRACKET = 1

@@ -1172,6 +1172,58 @@ class EntityView:
             detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
         return detail if return_detail else detail["path"]
 
+    # ---- trajectory optimisation (MirScene.optimize_path / mir_optimize_path): the planner's path as a seed, a shorter, smoother path
+    # further from the scene as the result.  The name and the arguments are this package's own: parity with Genesis, MoveIt's CHOMP /
+    # TrajOpt and cuRobo is unpinned.
+    def optimize_path(self, path, margin=0.0, resolution=0.05, smooth_weight=1.0, obstacle_weight=5.0, activation=0.05, step=0.25,
+                      max_iterations=50, max_halvings=6, ftol=1e-4, envs_idx=None, qpos_start=None, with_entity=None, ignore_entities=(),
+                      self_collision=None, self_margin=0.0, attached_entity=None, ee_link_name=None, grasp_pose=None, attached_links=None,
+                      ignore_collision=False, return_detail=False):
+        """``robot.optimize_path(path)`` -> (W, R, n): the joint path `path` ((W, R, n) as plan_path() and blend_path(num_waypoints=)
+        return it, 3 <= W <= 128) with its interior waypoints moved down the covariant gradient of `smooth_weight` x smoothness +
+        `obstacle_weight` x an obstacle cost of the entity's sphere model against the static scene, in the same layout -- so it goes into
+        retime_path, get_path_clearance, certify_path and control_dofs_position unchanged.  ONE launch for all rows
+        (MirScene.optimize_path / mir_optimize_path, where the rule is written down).  The obstacle cost starts `activation` metres
+        beyond `margin`; every iteration starts at step length `step` and halves it up to `max_halvings` times while the cost does not
+        fall; at most `max_iterations` iterations, fewer when the relative decrease falls below `ftol` (the defaults are spec.OPT_DEFAULTS,
+        chosen on the float64 reference: DESIGN.md, Trajectory optimisation; None takes them too).  The
+        result is swept like an edge of plan_path() (every `resolution` per joint; `margin`, `ignore_collision`, `with_entity`,
+        `ignore_entities`, `self_collision`, `self_margin`, `attached_entity`, `ee_link_name`, `attached_links` mean what they mean
+        there; the carried object's grasp is where the object is at the start: `grasp_pose` must be None), and a row that does not pass
+        comes back as its input, bit for bit.  The ends never move; a row without motion (a failed plan) comes back as it is.
+        return_detail=True -> a dict with path, valid (R,) = status is OK, status (R,) int32 (spec.OPT_STATUS), cost (R, 4): S and O
+        of the input, S and O reached, stats (R, 6): iterations, accepted steps, halvings, configurations evaluated, configurations
+        swept, stop (spec.OPT_STOP), and min_d (R,).  On an unbatched task every result comes without its env axis.
+        What it does not do: no self-collision term in the cost (the sweep alone tests it); the cost looks at the waypoints only; no
+        velocity, acceleration or torque limits (retime_path); fixed ends; no restarts; a BLOCKED row is not repaired."""
+        if grasp_pose is not None:
+            raise NotImplementedError("optimize_path: the grasp is taken from where the attached entity is at the start (mir_optimize_path has "
+                                      "no grasp rows); grasp_pose must be None")
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "optimize_path", self_collision, self_margin, attached_entity,
+                                  ee_link_name, None, attached_links)
+        if getattr(self._mir, "optimize_path", None) is None:
+            raise NotImplementedError("this scene has no trajectory optimisation (MirScene.optimize_path / mir_optimize_path)")
+        one = bool(self.__dict__.get("unbatched"))
+        p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
+        if one and p.dim() == 2:
+            p = p[:, None]
+        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != len(self._qcols) or p.shape[0] < 3:
+            raise ValueError(f"path must be (W >= 3, {R}, {len(self._qcols)}), got {tuple(p.shape)}")
+        if "carry" in args:
+            args["carry"] = dict(body=args["carry"]["body"], link=args["carry"]["link"])
+        from ..backend.spec import OPT_DEFAULTS
+
+        eps = OPT_DEFAULTS["activation"] if activation is None else float(activation)
+        r = self._mir.optimize_path(paths=p.permute(1, 0, 2).contiguous(), smooth_weight=smooth_weight, obstacle_weight=obstacle_weight,
+                                    activation=activation, step=step, max_iterations=max_iterations, max_halvings=max_halvings, ftol=ftol,
+                                    ignore_collision=bool(ignore_collision), resolution=float(resolution), margin=float(margin),
+                                    max_distance=max(1.0, 2.0 * (float(margin) + eps)), **args)
+        detail = {"path": r["path"].permute(1, 0, 2).contiguous(), "valid": r["status"] == 0, "status": r["status"], "cost": r["cost"],
+                  "stats": r["stats"], "min_d": r["min_d"]}
+        if one:   # (an unbatched task: no env axis anywhere)
+            detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
+        return detail if return_detail else detail["path"]
+
     # ---- time parameterisation (MirScene.retime_path / mir_retime_path): what stands between plan_path and control_dofs_position.
     # get_dofs_force_range is a Genesis name (RigidEntity); retime_path is this package's own: parity with Genesis is unpinned.
     def get_dofs_force_range(self, dofs_idx_local=None):

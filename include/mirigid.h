@@ -1342,6 +1342,99 @@ int mir_certify_path_carry(MirHandle h, const MirCertQuery* q, const MirPlanQuer
                            float* row_self_lower, float* row_self_upper, int32_t* row_status, int32_t* row_first,
                            float* grasp_used /* (R,7) nullable */, int32_t* leaves, int32_t* stats, void* stream);
 
+/* ---- trajectory optimisation: a joint path moved down the gradient of smoothness plus an obstacle cost, in one launch ----------
+ * `robot.optimize_path(path)`: mir_plan_path returns a path that is feasible and nothing more, mir_blend_path rounds its corners towards
+ * the obstacle it went round, mir_certify_path can only say BLOCKED.  For R rows ONE launch (mir_opt.hip, one wave64 per row) takes
+ * each row's joint path as a seed and moves its interior waypoints by covariant gradient descent (the update of CHOMP: Ratliff,
+ * Zucker, Bagnell, Srinivasa 2009) with a backtracking line search, sweeps the result with the planner's edge rule and returns it --
+ * or, where the sweep blocks, the input.  It reads the scene's state like mir_path_clearance and writes nothing a later call can see.
+ * Inputs.  paths (R, K, D), 3 <= K <= MIR_PLAN_MAX_POLY, the layout mir_plan_path and mir_blend_path(num_waypoints) return; xi =
+ *   (q_0 .. q_{K-1}), n = K - 2 interior waypoints.  probes, probe_link, dof_qadr, pq->skip_geoms, margin, max_distance, resolution,
+ *   flags, rows, env_idx, clamping and qpos_start are those of mir_path_clearance (pq->n_probes = N; with sq the E extra probes follow);
+ *   sq and cq as in mir_blend_path: the carried body's grasp comes from the start row.  w_s = smooth_weight, w_o = obstacle_weight
+ *   (MIR_PLAN_IGNORE_COLLISION: w_o counts as 0, nothing is evaluated and the sweep passes), eps = activation, alpha_0 = step.
+ *   Constants from the host, rounded once from double: km1 = K - 1, hk = (K - 1) / 2, ik = 1 / (K - 1), r_i = i / (i + 1), i = 1 .. n (the
+ *   reciprocal pivots of tridiag(-1, 2, -1): its pivots are (i + 1) / i).  x / y below is the refined division of the planner's edge
+ *   rule (1 / y, one Newton step on the quotient).  Every line below is one float32 rounding unless it says otherwise.
+ * 1. Checks on the input, in this order: a value of the row's path that is not finite: NOT_FINITE.  Every waypoint compares equal to
+ *   the first in every dof (a failed plan): NO_MOTION.  An interior waypoint with a dof outside [lo_j, hi_j]: OUT_OF_LIMITS.  All
+ *   three return the input; cost, stats and grad0 are zero, min_d is +infinity (as it is with MIR_PLAN_IGNORE_COLLISION, where nothing is
+ *   evaluated).  Waypoints are not compacted.
+ * 2. Cost of a path, U = w_s S + w_o O.
+ *   S: per dof j, s_j = sum over i = 0 .. K-2, ascending, of e e with e = q_{i+1,j} - q_{i,j}; ss = sum of s_j, j ascending; S = hk ss.
+ *   O: at each interior waypoint i = 1 .. K-2, ascending: the forward kinematics of clear(q_i) (mir_path_clearance), then per probe
+ *   p < N the winner of mir_signed_distance's minimum over the unskipped geoms, b_ip = signed distance - radius_p; a probe counts when
+ *   it has a winner with b_ip <= max_distance; d_ip = b_ip - margin; c(d) = eps / 2 - d for d < 0; ((d - eps)(d - eps)) / (2 eps) for
+ *   0 <= d <= eps; 0 above, and 0 for a probe that does not count.  The probes are summed in chunks of 64, a chunk by the butterfly
+ *   v_l <- v_l + v_{l xor 32}, then xor 16, 8, 4, 2, 1 (absent probes are 0), chunk sums added ascending to a running sum that passes
+ *   from waypoint to waypoint: oo.  O = ik oo.  U = (w_s S) + (w_o O).  A geom record, grasp or probe centre that is not finite
+ *   makes O +infinity.
+ * 3. Gradient at interior waypoint i, dof j: g_ij = w_s (km1 (((q_i + q_i) - q_{i-1}) - q_{i+1})) + w_o (ik G_ij), with G_ij the sum
+ *   over the probes, in the order of O's sum but per waypoint, of c'(d_ip) (n_ip . J_pj): c'(d) = -1 for d < 0, (d - eps) / eps for
+ *   0 <= d <= eps, else 0; n_ip = the winner's outward normal turned into the world by the winner's frame; J_pj = a_j x (c_p - o_j)
+ *   for a revolute planned joint j on the chain from the world to probe p's link, a_j for a prismatic one, 0 off the chain; a_j = the
+ *   joint's axis turned by the world rotation of its body, o_j = the world position of its body, c_p the probe's world centre, all at
+ *   q_i.  A probe of the carried body takes the chain of the attach link.  (The products inside n . J are the compiler's to fuse.)
+ * 4. Covariant step.  M = km1 tridiag(-1, 2, -1) on the interior waypoints; delta = M^-1 g per dof by the Thomas recurrence:
+ *   y_1 = g_1, y_i = g_i + (r_{i-1} y_{i-1}); x_n = r_n y_n, x_i = r_i (y_i + x_{i+1}); delta_i = ik x_i.  Candidate: q'_i = q_i -
+ *   (alpha delta_i) at the interior waypoints.  With w_o = 0 and alpha w_s = 1 the candidate is the straight line between the ends at
+ *   equal spacing, up to rounding.
+ * 5. Line search, per iteration: alpha = alpha_0; a candidate is rejected when an interior waypoint leaves [lo, hi] (it is then not
+ *   evaluated), when U(xi') is not finite or when not U(xi') < U(xi); a rejection halves alpha (alpha <- 0.5 alpha), at most
+ *   max_halvings times (max_halvings + 1 candidates).  No candidate accepted: the row stops, stop = STALLED.  The pass that gives
+ *   U(xi') leaves the gradient at xi'.
+ * 6. Stop.  An accepted step with U(xi) - U(xi') < ftol U(xi): stop = CONVERGED.  max_iterations iterations (each accepted or stalled)
+ *   done: stop = ITERATIONS (also for max_iterations = 0).
+ * 7. Validation.  The configuration q_0, then edge(q_i, q_{i+1}), i = 0 .. K-2, of what the descent reached, by the rule of
+ *   mir_plan_path: clear(q) with the scene test at margin first, then (sq) the self test at self_margin, the carried body riding along
+ *   (cq); the first sample that fails ends it: BLOCKED (scene) or BLOCKED_SELF, and path_out holds the INPUT's bits.  All clear: OK,
+ *   and path_out holds xi.  The end waypoints always hold the input's bits.  The cost has no self term.
+ * Outputs.  path_out (R, K, D); status (R): MIR_PLAN_OK or MIR_OPT_*; cost (R, 4), nullable: S and O of the input, S and O of what the
+ *   descent reached (also where the sweep then blocked); stats (R, 6), nullable: iterations, accepted steps, halvings, configurations
+ *   evaluated in the descent (n per pass, the input's pass included), configurations checked in the sweep, stop (MIR_OPT_STOP_*);
+ *   min_d (R), nullable: the lowest d_ip over the interior waypoints and the probes of the path that path_out holds (max_distance -
+ *   margin for a probe that does not count); grad0 (R, K, D), nullable: g at the INPUT path, zero rows at the ends -- a test hook that
+ *   pins the kernel's arithmetic; it costs one store per value.
+ * LDS: the fixed part of mir_path_clearance + 3 K 64 bytes + (sq) 16 (N + E) bytes must fit 64 KB, else MIR_E_CAPACITY.
+ * MIR_E_INVALID, besides everything mir_path_clearance(_self, _carry) refuses: a NULL q, pq, paths, path_out or status; struct_size !=
+ *   sizeof(MirOptQuery); K outside 3 .. MIR_PLAN_MAX_POLY; an unknown flag bit; a weight, step, activation or ftol that is not finite;
+ *   smooth_weight <= 0; obstacle_weight < 0; step <= 0; activation <= 0; ftol < 0; negative max_iterations or max_halvings;
+ *   max_distance < margin + activation.  None of them launches anything; n_rows = 0 returns MIR_OK.
+ * What it does not do.  No self-collision term in the cost (the sweep alone tests it).  The obstacle cost is collocated at the
+ *   waypoints: between them only the sweep looks, as coarsely as the edge rule.  No workspace-velocity weighting of the obstacle cost.
+ *   No velocity, acceleration or torque limits (mir_retime_path).  The ends are fixed; no goal set, no pose goal, no restarts; a BLOCKED
+ *   row is not repaired; the planner does not call it.  Parity with MoveIt's CHOMP, TrajOpt and cuRobo is unpinned.
+ * (Added struct and entry point: MIR_VERSION and every other struct and entry point stay as they are.) */
+#define MIR_OPT_BLOCKED 48
+#define MIR_OPT_BLOCKED_SELF 49
+#define MIR_OPT_NOT_FINITE 50
+#define MIR_OPT_NO_MOTION 51
+#define MIR_OPT_OUT_OF_LIMITS 52
+#define MIR_OPT_STOP_NONE 0 /* no descent ran (a check of 1. failed) */
+#define MIR_OPT_STOP_ITERATIONS 1
+#define MIR_OPT_STOP_CONVERGED 2
+#define MIR_OPT_STOP_STALLED 3
+typedef struct MirOptQuery {
+  int32_t  struct_size;     /* = sizeof(MirOptQuery) */
+  int32_t  num_waypoints;   /* K: 3 .. MIR_PLAN_MAX_POLY */
+  int32_t  max_iterations;  /* >= 0 */
+  int32_t  max_halvings;    /* >= 0 halvings of alpha per iteration */
+  uint32_t flags;           /* 0; unknown bits are MIR_E_INVALID */
+  float    smooth_weight;   /* w_s > 0 */
+  float    obstacle_weight; /* w_o >= 0 */
+  float    step;            /* alpha_0 > 0 */
+  float    activation;      /* eps > 0, m: the distance beyond the margin at which the obstacle cost starts */
+  float    ftol;            /* >= 0: relative decrease of U below which the row has converged */
+} MirOptQuery;
+int mir_opt_query_sizeof(void);
+int mir_optimize_path(MirHandle h, const MirOptQuery* q, const MirPlanQuery* pq, const MirSelfQuery* sq /* nullable */,
+                      const MirCarryQuery* cq /* nullable */, const float* probes /* (N+E,4) device */,
+                      const int32_t* probe_link /* (N+E) HOST, nullable */, const int32_t* dof_qadr /* (D) HOST */,
+                      const int64_t* env_idx /* device, nullable */, int32_t n_rows, const float* qpos_start /* (R,nq) nullable */,
+                      const float* paths /* (R,K,D) */, int32_t K /* = q->num_waypoints */, float* path_out /* (R,K,D) */,
+                      int32_t* status /* (R) */, float* cost /* (R,4) nullable */, int32_t* stats /* (R,6) nullable */,
+                      float* min_d /* (R) nullable */, float* grad0 /* (R,K,D) nullable */, void* stream);
+
 /* ---- cameras / pixels (BASELINE.json configs[4]) ---------------------------------
  * scene.add_camera(res=(W,H), pos, lookat, fov)   gym_genesis/tasks/franka/cube_pick.py:56-63
  * cam.set_pose(pos, lookat) + cam.render()[0]      gym_genesis/tasks/franka/cube_pick.py:166-176,
