@@ -212,12 +212,6 @@ __global__ __launch_bounds__(64) void mir_blend_kernel(BlendArgs a) {
   }
 }
 
-using BlendKernel = void (*)(BlendArgs);
-BlendKernel blend_kernel(bool self, bool carry) {
-  if (carry) return self ? mir_blend_kernel<true, true> : mir_blend_kernel<false, true>;
-  return self ? mir_blend_kernel<true, false> : mir_blend_kernel<false, false>;
-}
-
 }  // namespace
 
 extern "C" int mir_blend_query_sizeof(void) { return (int)sizeof(MirBlendQuery); }
@@ -231,9 +225,8 @@ extern "C" int mir_blend_path(MirHandle h, const MirBlendQuery* q, const MirPlan
   const BlendCall bc{h != nullptr, q, pq, probes, dof_qadr, poly, points, n_points, status, path};
   int rc;
   if ((rc = blend_check(bc, refuse)) != MIR_OK) return rc;
-  PlanCall c{};
-  c.who = who; c.h = h; c.q = pq; c.sq = sq; c.self = sq != nullptr; c.cq = cq; c.carry = cq != nullptr; c.stream = stream;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call(who, h, pq, sq, sq != nullptr, cq, cq != nullptr, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr,
+                               nullptr, stream);
   BlendArgs a;
   memset(&a, 0, sizeof a);
   long long R = 0;
@@ -244,7 +237,6 @@ extern "C" int mir_blend_path(MirHandle h, const MirBlendQuery* q, const MirPlan
   a.delta = q->max_deviation;
   a.poly = poly; a.n_poly = n_poly;
   a.points = points; a.path = path; a.blend_len = blend_len; a.n_points = n_points; a.status = status; a.stats = stats;
-  DeviceGuard guard(h->device);  // (the table's allocation, too)
-  if ((rc = fill_dist_tab(h, who, a.p.t)) != MIR_OK) return rc;
-  return launch_rows<64>(h, blend_kernel(c.self, c.carry), R, stream, a, c.self ? 16 * (size_t)a.p.NS : 0);
+  const auto kernel = pick_self_carry(c.self, c.carry, [](auto S, auto C) { return mir_blend_kernel<decltype(S)::value, decltype(C)::value>; });
+  return plan_launch(c, kernel, R, a, a.p, 0);
 }

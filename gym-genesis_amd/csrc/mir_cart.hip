@@ -309,12 +309,6 @@ __global__ __launch_bounds__(64) void mir_cart_kernel(CartArgs a) {
   }
 }
 
-using CartKernel = void (*)(CartArgs);
-CartKernel cart_kernel(bool self, bool carry) {
-  if (carry) return self ? mir_cart_kernel<true, true> : mir_cart_kernel<false, true>;
-  return self ? mir_cart_kernel<true, false> : mir_cart_kernel<false, false>;
-}
-
 }  // namespace
 
 extern "C" int mir_cart_query_sizeof(void) { return (int)sizeof(MirCartQuery); }
@@ -328,9 +322,8 @@ extern "C" int mir_cartesian_path(MirHandle h, const MirCartQuery* q, const MirP
   const CartCall cc{h != nullptr, q, pq, probes, dof_qadr, target_pos, points, n_points, fraction, status, path};
   int rc;
   if ((rc = cart_check(cc, refuse)) != MIR_OK) return rc;
-  PlanCall c{};
-  c.who = who; c.h = h; c.q = pq; c.sq = sq; c.self = sq != nullptr; c.cq = cq; c.carry = cq != nullptr; c.stream = stream;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call(who, h, pq, sq, sq != nullptr, cq, cq != nullptr, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr,
+                               nullptr, stream);
   CartArgs a;
   memset(&a, 0, sizeof a);
   long long R = 0;
@@ -368,7 +361,6 @@ extern "C" int mir_cartesian_path(MirHandle h, const MirCartQuery* q, const MirP
   a.max_pos_step = q->max_pos_step; a.max_rot_step = q->max_rot_step; a.jump = q->jump_threshold;
   a.target_pos = target_pos; a.target_quat = target_quat;
   a.points = points; a.fraction = fraction; a.path = path; a.n_points = n_points; a.status = status; a.stats = stats;
-  DeviceGuard guard(h->device);  // (the table's allocation, too)
-  if ((rc = fill_dist_tab(h, who, a.p.t)) != MIR_OK) return rc;
-  return launch_rows<64>(h, cart_kernel(c.self, c.carry), R, stream, a, c.self ? 16 * (size_t)a.p.NS : 0);
+  const auto kernel = pick_self_carry(c.self, c.carry, [](auto S, auto C) { return mir_cart_kernel<decltype(S)::value, decltype(C)::value>; });
+  return plan_launch(c, kernel, R, a, a.p, 0);
 }

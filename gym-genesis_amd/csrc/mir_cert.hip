@@ -474,10 +474,7 @@ int cert_entry(const char* who, CertForm form, MirHandle h, const MirCertQuery* 
     if ((rc = certrel_check(rc2, refuse)) != MIR_OK) return rc;
   }
   const bool self = sq != nullptr, carry = cq != nullptr;
-  PlanCall c{};
-  c.who = who; c.h = h; c.q = pq; c.sq = sq; c.self = self; c.cq = cq; c.carry = carry; c.stream = stream;
-  c.grasp = grasp; c.grasp_used = o.grasp_used;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call(who, h, pq, sq, self, cq, carry, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, grasp, o.grasp_used, stream);
   CertArgs a;
   memset(&a, 0, sizeof a);
   long long R = 0;
@@ -505,11 +502,11 @@ int cert_entry(const char* who, CertForm form, MirHandle h, const MirCertQuery* 
     }
     certrel_lca_table(h->nbody, MIR_MAX_BODY, parent, depth, carry ? a.p.carry_body : -1, carry ? a.p.carry_link : -1, a.lca);
   }
-  DeviceGuard guard(h->device);  // (the table's allocation, too)
-  if ((rc = fill_dist_tab(h, who, a.p.t)) != MIR_OK) return rc;
-  void (*const kernel)(CertArgs) = self ? (carry ? mir_cert_kernel<true, true> : mir_cert_kernel<true, false>)
-                                        : (carry ? mir_cert_kernel<false, true> : mir_cert_kernel<false, false>);
-  return launch_rows<64>(h, kernel, R, stream, a, self || carry ? (size_t)certrel_lds_bytes(0, a.p.N, a.p.NS, self) : 0);
+  // (carry in the place of self and back: the four instantiations are then emitted in the order this file always had them, <true, true>,
+  // <true, false>, <false, true>, <false, false>, and the code object keeps its bytes)
+  const auto kernel = pick_self_carry(carry, self, [](auto C, auto S) { return mir_cert_kernel<decltype(S)::value, decltype(C)::value>; });
+  // (the speed bounds of certrel_lds_bytes; the sphere list, its last term, is what plan_launch adds)
+  return plan_launch(c, kernel, R, a, a.p, self || carry ? (size_t)certrel_lds_bytes(0, a.p.N, a.p.NS, false) : 0);
 }
 
 }  // namespace

@@ -273,12 +273,6 @@ __global__ __launch_bounds__(64) void mir_opt_kernel(OptArgs a) {
   }
 }
 
-using OptKernel = void (*)(OptArgs);
-OptKernel opt_kernel(bool self, bool carry) {
-  if (carry) return self ? mir_opt_kernel<true, true> : mir_opt_kernel<false, true>;
-  return self ? mir_opt_kernel<true, false> : mir_opt_kernel<false, false>;
-}
-
 }  // namespace
 
 extern "C" int mir_opt_query_sizeof(void) { return (int)sizeof(MirOptQuery); }
@@ -292,9 +286,8 @@ extern "C" int mir_optimize_path(MirHandle h, const MirOptQuery* q, const MirPla
   const OptCall oc{h != nullptr, q, pq, probes, dof_qadr, paths, path_out, status, K};
   int rc;
   if ((rc = opt_check(oc, refuse)) != MIR_OK) return rc;
-  PlanCall c{};
-  c.who = who; c.h = h; c.q = pq; c.sq = sq; c.self = sq != nullptr; c.cq = cq; c.carry = cq != nullptr; c.stream = stream;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call(who, h, pq, sq, sq != nullptr, cq, cq != nullptr, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start, nullptr,
+                               nullptr, stream);
   OptArgs a;
   memset(&a, 0, sizeof a);
   long long R = 0;
@@ -325,7 +318,6 @@ extern "C" int mir_optimize_path(MirHandle h, const MirOptQuery* q, const MirPla
   }
   if (c.carry) a.chain[cq->body] = a.chain[cq->link];
   a.paths = paths; a.path_out = path_out; a.status = status; a.cost = cost; a.stats = stats; a.min_d = min_d; a.grad0 = grad0;
-  DeviceGuard guard(h->device);  // (the table's allocation, too)
-  if ((rc = fill_dist_tab(h, who, a.p.t)) != MIR_OK) return rc;
-  return launch_rows<64>(h, opt_kernel(c.self, c.carry), R, stream, a, (size_t)3 * K * OPT_STRIDE * sizeof(float) + (c.self ? 16 * (size_t)a.p.NS : 0));
+  const auto kernel = pick_self_carry(c.self, c.carry, [](auto S, auto C) { return mir_opt_kernel<decltype(S)::value, decltype(C)::value>; });
+  return plan_launch(c, kernel, R, a, a.p, (size_t)3 * K * OPT_STRIDE * sizeof(float));
 }

@@ -54,7 +54,7 @@
 
 #include "mir_self_body.h"
 
-#include "mir_plan_row.h"  // (PlanArgs, PlanLds, div_refined, PlanRow, plan_setup, PlanCall, plan_front: shared with mir_cart.hip)
+#include "mir_plan_row.h"  // (PlanArgs, PlanLds, div_refined, PlanRow, plan_setup, PlanCall, plan_front and the launch: shared with mir_cart.hip)
 
 namespace {
 
@@ -288,30 +288,19 @@ __global__ __launch_bounds__(64) void mir_path_clear_kernel(PlanArgs a) {
   }
 }
 
-// ---- host (the call description PlanCall and plan_front, which every entry point shares: mir_plan_row.h)
-// the instantiation of either kernel that serves a call
-using PlanKernel = void (*)(PlanArgs);
-PlanKernel plan_kernel(bool self, bool carry) {
-  if (carry) return self ? mir_plan_kernel<true, true> : mir_plan_kernel<false, true>;
-  return self ? mir_plan_kernel<true, false> : mir_plan_kernel<false, false>;
-}
-PlanKernel path_clear_kernel(bool self, bool carry) {
-  if (carry) return self ? mir_path_clear_kernel<true, true> : mir_path_clear_kernel<false, true>;
-  return self ? mir_path_clear_kernel<true, false> : mir_path_clear_kernel<false, false>;
-}
-
+// ---- host (the call description PlanCall with plan_call, plan_front, pick_self_carry and plan_launch, which every entry point
+// shares: mir_plan_row.h)
 int plan_entry(const PlanCall& c, const float* qpos_goal, float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats) {
   if (!qpos_goal || !path || !status) return query_error(MIR_E_INVALID, c.who, "null argument");
   PlanArgs a;
   long long R = 0;
-  int rc = plan_front(c, true, a, R);
+  const int rc = plan_front(c, true, a, R);
   if (rc != MIR_OK || R == 0) return rc;
   a.W = c.q->num_waypoints; a.max_nodes = c.q->max_nodes; a.max_iter = c.q->max_iterations; a.smooth = c.q->smooth_passes; a.seed = c.q->seed;
   a.step = c.q->step; a.goal = qpos_goal; a.path = path; a.status = status; a.poly = poly; a.n_poly = n_poly; a.stats = stats;
   const size_t trees = (size_t)2 * (size_t)a.max_nodes * (4 * (size_t)a.D + 2);
-  DeviceGuard guard(c.h->device);  // (the table's allocation, too)
-  if ((rc = fill_dist_tab(c.h, c.who, a.t)) != MIR_OK) return rc;
-  return launch_rows<64>(c.h, plan_kernel(c.self, c.carry), R, c.stream, a, trees + (c.self ? 16 * (size_t)a.NS : 0));
+  const auto kernel = pick_self_carry(c.self, c.carry, [](auto S, auto C) { return mir_plan_kernel<decltype(S)::value, decltype(C)::value>; });
+  return plan_launch(c, kernel, R, a, a, trees);
 }
 
 int path_clear_entry(const PlanCall& c, const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min, float* row_self_min,
@@ -321,44 +310,42 @@ int path_clear_entry(const PlanCall& c, const float* paths, int32_t K, float* se
   if (!c.self && (seg_self_min || row_self_min)) return query_error(MIR_E_INVALID, c.who, "seg_self_min / row_self_min without a MirSelfQuery");
   PlanArgs a;
   long long R = 0;
-  int rc = plan_front(c, false, a, R);
+  const int rc = plan_front(c, false, a, R);
   if (rc != MIR_OK || R == 0 || (!seg_min && !seg_self_min && !row_min && !row_self_min && !row_first_blocked && !c.grasp_used)) return rc;
   a.K = K; a.goal = paths; a.seg_min = seg_min; a.row_min = row_min; a.first_blocked = row_first_blocked;
   a.seg_self_min = seg_self_min; a.row_self_min = row_self_min;
-  DeviceGuard guard(c.h->device);  // (the table's allocation, too)
-  if ((rc = fill_dist_tab(c.h, c.who, a.t)) != MIR_OK) return rc;
-  return launch_rows<64>(c.h, path_clear_kernel(c.self, c.carry), R, c.stream, a, c.self ? 16 * (size_t)a.NS : 0);
+  const auto kernel = pick_self_carry(c.self, c.carry, [](auto S, auto C) { return mir_path_clear_kernel<decltype(S)::value, decltype(C)::value>; });
+  return plan_launch(c, kernel, R, a, a, 0);
 }
 
 }  // namespace
 
 extern "C" int mir_plan_query_sizeof(void) { return (int)sizeof(MirPlanQuery); }
 extern "C" int mir_self_query_sizeof(void) { return (int)sizeof(MirSelfQuery); }
+extern "C" int mir_carry_query_sizeof(void) { return (int)sizeof(MirCarryQuery); }
 
+// (the _self forms: self with a possibly null sq, their refusal; the _carry forms: a null sq is "no self test")
 extern "C" int mir_plan_path(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
                              const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal, float* path,
                              int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
-  PlanCall c{};
-  c.who = "mir_plan_path"; c.h = h; c.q = q; c.stream = stream;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call("mir_plan_path", h, q, nullptr, false, nullptr, false, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start,
+                               nullptr, nullptr, stream);
   return plan_entry(c, qpos_goal, path, status, poly, n_poly, stats);
 }
 
 extern "C" int mir_plan_path_self(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const float* probes, const int32_t* probe_link,
                                   const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* qpos_goal,
                                   float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats, void* stream) {
-  PlanCall c{};
-  c.who = "mir_plan_path_self"; c.h = h; c.q = q; c.sq = sq; c.self = true; c.stream = stream;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call("mir_plan_path_self", h, q, sq, true, nullptr, false, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start,
+                               nullptr, nullptr, stream);
   return plan_entry(c, qpos_goal, path, status, poly, n_poly, stats);
 }
 
 extern "C" int mir_path_clearance(MirHandle h, const MirPlanQuery* q, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
                                   const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* paths, int32_t K,
                                   float* seg_min, float* row_min, int32_t* row_first_blocked, void* stream) {
-  PlanCall c{};
-  c.who = "mir_path_clearance"; c.h = h; c.q = q; c.stream = stream;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call("mir_path_clearance", h, q, nullptr, false, nullptr, false, probes, probe_link, dof_qadr, env_idx, n_rows,
+                               qpos_start, nullptr, nullptr, stream);
   return path_clear_entry(c, paths, K, seg_min, /*seg_self_min*/ nullptr, row_min, /*row_self_min*/ nullptr, row_first_blocked);
 }
 
@@ -366,22 +353,17 @@ extern "C" int mir_path_clearance_self(MirHandle h, const MirPlanQuery* q, const
                                        const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
                                        const float* paths, int32_t K, float* seg_min, float* seg_self_min, float* row_min, float* row_self_min,
                                        int32_t* row_first_blocked, void* stream) {
-  PlanCall c{};
-  c.who = "mir_path_clearance_self"; c.h = h; c.q = q; c.sq = sq; c.self = true; c.stream = stream;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call("mir_path_clearance_self", h, q, sq, true, nullptr, false, probes, probe_link, dof_qadr, env_idx, n_rows,
+                               qpos_start, nullptr, nullptr, stream);
   return path_clear_entry(c, paths, K, seg_min, seg_self_min, row_min, row_self_min, row_first_blocked);
 }
-
-extern "C" int mir_carry_query_sizeof(void) { return (int)sizeof(MirCarryQuery); }
 
 extern "C" int mir_plan_path_carry(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq, const MirCarryQuery* cq, const float* probes,
                                    const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
                                    const float* grasp, const float* qpos_goal, float* path, int32_t* status, float* poly, int32_t* n_poly,
                                    int32_t* stats, float* grasp_used, void* stream) {
-  PlanCall c{};
-  c.who = "mir_plan_path_carry"; c.h = h; c.q = q; c.sq = sq; c.self = sq != nullptr; c.cq = cq; c.carry = true; c.stream = stream;
-  c.grasp = grasp; c.grasp_used = grasp_used;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call("mir_plan_path_carry", h, q, sq, sq != nullptr, cq, true, probes, probe_link, dof_qadr, env_idx, n_rows, qpos_start,
+                               grasp, grasp_used, stream);
   return plan_entry(c, qpos_goal, path, status, poly, n_poly, stats);
 }
 
@@ -389,9 +371,7 @@ extern "C" int mir_path_clearance_carry(MirHandle h, const MirPlanQuery* q, cons
                                         const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows,
                                         const float* qpos_start, const float* grasp, const float* paths, int32_t K, float* seg_min, float* seg_self_min,
                                         float* row_min, float* row_self_min, int32_t* row_first_blocked, float* grasp_used, void* stream) {
-  PlanCall c{};
-  c.who = "mir_path_clearance_carry"; c.h = h; c.q = q; c.sq = sq; c.self = sq != nullptr; c.cq = cq; c.carry = true; c.stream = stream;
-  c.grasp = grasp; c.grasp_used = grasp_used;
-  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  const PlanCall c = plan_call("mir_path_clearance_carry", h, q, sq, sq != nullptr, cq, true, probes, probe_link, dof_qadr, env_idx, n_rows,
+                               qpos_start, grasp, grasp_used, stream);
   return path_clear_entry(c, paths, K, seg_min, seg_self_min, row_min, row_self_min, row_first_blocked);
 }

@@ -1,9 +1,12 @@
 // mir_plan_row.h — the row machinery of the planner, shared by mir_plan.hip (mir_plan_path, mir_path_clearance and their _self / _carry
-// forms) and mir_cart.hip (mir_cartesian_path): the kernel arguments and the fixed LDS of a row, the refined division, PlanRow<SELF,
-// CARRY> with clear(q) and edge(a, b), the row set-up, and on the host the call description with the checks and argument filling every
-// entry point shares (plan_front).  mir_plan.hip's header comment says what each part does.  Needs mir_dev.h with G = 16, mir_query.h,
-// mir_sphere_front.h and mir_self_body.h in front of it.  Inside no namespace.
+// forms), mir_cart.hip, mir_blend.hip, mir_opt.hip and mir_cert.hip: the kernel arguments and the fixed LDS of a row, the refined division,
+// PlanRow<SELF, CARRY> with clear(q) and edge(a, b), the row set-up, and on the host what every entry point shares: the call description
+// and its filling (PlanCall, plan_call), the checks and the argument filling (plan_front), the choice of the instantiation
+// (pick_self_carry) and the launch (plan_launch).  mir_plan.hip's header comment says what each part does.  Needs mir_dev.h with G = 16,
+// mir_query.h, mir_sphere_front.h and mir_self_body.h in front of it.  Inside no namespace.
 #pragma once
+
+#include <type_traits>
 
 namespace {
 
@@ -59,6 +62,7 @@ __device__ __forceinline__ float div_refined(float x, float y) {
 
 // what a row carries through its launch (wave-uniform but for `lane`)
 enum { SELF_LIST = 0, SELF_IGNORED = 1, SELF_BLOCKED = 2 };  // what the last clearance() left for self_clearance()
+constexpr size_t SELF_SPHERE_BYTES = 16;  // an entry of the sphere list of the self test: (centre, radius)
 template <bool SELF, bool CARRY>
 struct PlanRow {
   static constexpr bool carry = CARRY;
@@ -247,6 +251,37 @@ struct PlanCall {
   void* stream;
 };
 
+// the call of an entry point from the arguments every one of them receives (grasp, grasp_used: null but for the carry forms)
+PlanCall plan_call(const char* who, MirHandle h, const MirPlanQuery* pq, const MirSelfQuery* sq, bool self, const MirCarryQuery* cq, bool carry,
+                   const float* probes, const int32_t* probe_link, const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows,
+                   const float* qpos_start, const float* grasp, float* grasp_used, void* stream) {
+  PlanCall c{};
+  c.who = who; c.h = h; c.q = pq; c.sq = sq; c.self = self; c.cq = cq; c.carry = carry; c.stream = stream;
+  c.grasp = grasp; c.grasp_used = grasp_used;
+  c.probes = probes; c.probe_link = probe_link; c.dof_qadr = dof_qadr; c.env_idx = env_idx; c.n_rows = n_rows; c.qpos_start = qpos_start;
+  return c;
+}
+
+// the <SELF, CARRY> instantiation that serves a call: `kernel` names the template,
+//   [](auto S, auto C) { return mir_plan_kernel<decltype(S)::value, decltype(C)::value>; }
+template <class Kernel>
+auto pick_self_carry(bool self, bool carry, Kernel kernel) {
+  using T = std::true_type;
+  using F = std::false_type;
+  if (carry) return self ? kernel(T{}, T{}) : kernel(F{}, T{});
+  return self ? kernel(T{}, F{}) : kernel(F{}, F{});
+}
+
+// the launch every entry point ends with: the distance table into `p` (the PlanArgs inside `a`), one wave64 per row, the caller's
+// dynamic LDS with the sphere list of the self test behind it
+template <class Args>
+int plan_launch(const PlanCall& c, void (*kernel)(Args), long long R, Args& a, PlanArgs& p, size_t lds) {
+  DeviceGuard guard(c.h->device);  // (the table's allocation, too)
+  const int rc = fill_dist_tab(c.h, c.who, p.t);
+  if (rc != MIR_OK) return rc;
+  return launch_rows<64>(c.h, kernel, R, c.stream, a, lds + (c.self ? SELF_SPHERE_BYTES * (size_t)p.NS : 0));
+}
+
 // what the two kinds of entry point share.  Fills `a` but for the outputs and the table; every refusal launches nothing.  The self
 // query is checked here, the carry query too (behind the refusals of the entry point it extends).
 int plan_front(const PlanCall& c, bool planner, PlanArgs& a, long long& R) {
@@ -323,7 +358,7 @@ int plan_front(const PlanCall& c, bool planner, PlanArgs& a, long long& R) {
     a.carry_body = cb; a.carry_link = cl;
   }
   if (planner) {
-    const size_t lds = sizeof(PlanLds) + (size_t)2 * (size_t)q->max_nodes * (4 * (size_t)D + 2) + (self ? 16 * (size_t)NS : 0);
+    const size_t lds = sizeof(PlanLds) + (size_t)2 * (size_t)q->max_nodes * (4 * (size_t)D + 2) + (self ? SELF_SPHERE_BYTES * (size_t)NS : 0);
     if (q->max_nodes > 0xfffe || lds > 65536)
       return query_error(MIR_E_CAPACITY, who, self ? "the two trees and the sphere list do not fit 64 KB of LDS (max_nodes x n_dofs, n_probes + n_extra)"
                                                     : "the two trees do not fit 64 KB of LDS (max_nodes x n_dofs)");

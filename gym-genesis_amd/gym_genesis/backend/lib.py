@@ -194,36 +194,13 @@ def load_library() -> C.CDLL:
         getattr(lib, name).restype = C.c_int
     if lib.mir_spec_sizeof() != C.sizeof(MirSceneSpec) or lib.mir_version() != MIR_VERSION or lib.mir_visual_sizeof() != C.sizeof(MirVisualSpec):
         raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec (rebuild the library)")
-    if lib.mir_kin_query_sizeof() != C.sizeof(MirKinQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirKinQuery (rebuild the library)")
-    if lib.mir_acc_query_sizeof() != C.sizeof(MirAccQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirAccQuery (rebuild the library)")
-    if lib.mir_dyn_query_sizeof() != C.sizeof(MirDynQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirDynQuery (rebuild the library)")
-    if lib.mir_task_query_sizeof() != C.sizeof(MirTaskQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirTaskQuery (rebuild the library)")
-    if lib.mir_ray_query_sizeof() != C.sizeof(MirRayQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRayQuery (rebuild the library)")
-    if lib.mir_dist_query_sizeof() != C.sizeof(MirDistQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirDistQuery (rebuild the library)")
-    if lib.mir_plan_query_sizeof() != C.sizeof(MirPlanQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirPlanQuery (rebuild the library)")
-    if lib.mir_self_query_sizeof() != C.sizeof(MirSelfQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirSelfQuery (rebuild the library)")
-    if lib.mir_carry_query_sizeof() != C.sizeof(MirCarryQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCarryQuery (rebuild the library)")
-    if lib.mir_retime_query_sizeof() != C.sizeof(MirRetimeQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirRetimeQuery (rebuild the library)")
-    if lib.mir_cart_query_sizeof() != C.sizeof(MirCartQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCartQuery (rebuild the library)")
-    if lib.mir_blend_query_sizeof() != C.sizeof(MirBlendQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirBlendQuery (rebuild the library)")
-    if lib.mir_opt_query_sizeof() != C.sizeof(MirOptQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirOptQuery (rebuild the library)")
-    if lib.mir_cert_query_sizeof() != C.sizeof(MirCertQuery):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirCertQuery (rebuild the library)")
-    if lib.mir_ik_multi_sizeof() != C.sizeof(MirIkMulti):
-        raise MirError("libmirigid.so ABI mismatch with gym_genesis.backend.spec: MirIkMulti (rebuild the library)")
+    for fn, struct in (("mir_kin_query_sizeof", MirKinQuery), ("mir_acc_query_sizeof", MirAccQuery), ("mir_dyn_query_sizeof", MirDynQuery),
+                       ("mir_task_query_sizeof", MirTaskQuery), ("mir_ray_query_sizeof", MirRayQuery), ("mir_dist_query_sizeof", MirDistQuery),
+                       ("mir_plan_query_sizeof", MirPlanQuery), ("mir_self_query_sizeof", MirSelfQuery), ("mir_carry_query_sizeof", MirCarryQuery),
+                       ("mir_retime_query_sizeof", MirRetimeQuery), ("mir_cart_query_sizeof", MirCartQuery), ("mir_blend_query_sizeof", MirBlendQuery),
+                       ("mir_opt_query_sizeof", MirOptQuery), ("mir_cert_query_sizeof", MirCertQuery), ("mir_ik_multi_sizeof", MirIkMulti)):
+        if getattr(lib, fn)() != C.sizeof(struct):
+            raise MirError(f"libmirigid.so ABI mismatch with gym_genesis.backend.spec: {struct.__name__} (rebuild the library)")
     _lib = lib
     _bind_fast(lib)
     return lib
@@ -393,6 +370,52 @@ class StepHelpers:
         raise NotImplementedError
 
 
+class _SphereCall:
+    """What plan_path, path_clearance, certify_path, cartesian_path, blend_path and optimize_path of MirScene share.  The constructor: the
+    sphere model, the planned dofs and the rows on the device (MirScene._plan_front), D, the self query with N.  collision(), once the
+    method has checked what is its own: the MirPlanQuery from the collision keywords and the carry query.  Then new() allocates (R, ...)
+    outputs, head() is the argument list every C entry point starts with, symbol() picks among a call's three entry points."""
+
+    def __init__(self, scene, probes, links, dof_qadr, env_idx, qpos_start, self_model=None):
+        self.scene = scene
+        self.p, self.lk, self.qa, self.idx, self.R, self.qpos_start = scene._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
+        self.D, self.N, self.sq, self.cq = int(self.qa.shape[0]), int(self.p.shape[0]), None, None
+        self.grasp_used, self.grasp_in, self.grasp_out = None, (), ()
+        self.new = scene._row_alloc(self.R)
+        self.self_model(self_model)
+
+    def self_model(self, self_model) -> None:
+        if self_model is not None:
+            self.sq, self.N = self.scene._self_query(self_model, int(self.p.shape[0]))
+
+    def collision(self, carry=None, grasp_rows: bool = False, **plan) -> None:
+        self.pq = make_plan_query(self.N, self.D, **plan)
+        self.carry(carry, grasp_rows)
+
+    def carry(self, carry, grasp_rows: bool) -> None:
+        """carry = dict(body, link, grasp=None) or None.  With `grasp_rows` the entry point takes the rows' grasp and returns the one each row
+        used (grasp_in, grasp_out: its two pointers as tuples, empty without a carried body); without, the grasp is the start row's."""
+        if carry is not None and grasp_rows:
+            self.cq, grasp, self.grasp_used = self.scene._carry_query(carry, self.R)
+            self.grasp_in, self.grasp_out = (_ptr(grasp),), (_ptr(self.grasp_used),)
+        elif carry is not None:
+            self.cq = make_carry_query(carry["body"], carry["link"])
+
+    def head(self, q=None, sq: bool = True, cq: bool = True) -> tuple:
+        """(h, q?, pq, sq?, cq?, probes, links, dof_qadr, env_idx, R, qpos_start): q, the method's own query, where it has one; sq / cq
+        (null without a self model / a carried body) where the entry point takes them"""
+        ref = lambda x: None if x is None else C.byref(x)  # noqa: E731
+        return (self.scene.h, *(() if q is None else (C.byref(q),)), C.byref(self.pq), *((ref(self.sq),) if sq else ()),
+                *((ref(self.cq),) if cq else ()), _ptr(self.p), None if self.lk is None else self.lk.ctypes.data_as(C.c_void_p),
+                self.qa.ctypes.data_as(C.c_void_p), _ptr(self.idx), self.R, _ptr(self.qpos_start))
+
+    def symbol(self, base: str, q=None):
+        """-> (the entry point, its head, form): base + "_carry" with a carried body (sq may be null), base + "_self" with a self model
+        alone, else base, which takes neither query"""
+        form = "_carry" if self.cq is not None else "_self" if self.sq is not None else ""
+        return getattr(self.scene.lib, base + form), self.head(q, sq=form != "", cq=form == "_carry"), form
+
+
 class MirScene(StepHelpers):
     """A compiled, batched scene living on one GPU (``scene.build(n_envs=B)``)."""
 
@@ -429,6 +452,22 @@ class MirScene(StepHelpers):
         if _raw_stream is not None:
             return _raw_stream(self.device.index)  # int; the c_void_p argtype converts it
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def _launched(self, what: str) -> None:
+        """counts a launch in self.<what>_launches"""
+        key = what + "_launches"
+        self.__dict__[key] = self.__dict__.get(key, 0) + 1
+
+    def _row_alloc(self, R: int):
+        """-> new(*shape, dtype=torch.float32): a fresh (R, *shape) device tensor"""
+        return lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)
+
+    def _rows_kd(self, t, name: str, R: int, D: int, kmin: int = 0):
+        """`t` (the `paths` / `poly` / `target_pos` of a path method) as a float32 device tensor (R, K >= kmin, D) -> (t, K)"""
+        t = torch.as_tensor(t, device=self.device).to(torch.float32).contiguous()
+        if t.dim() != 3 or t.shape[0] != R or t.shape[2] != D or t.shape[1] < kmin:
+            raise ValueError(f"{name} must be ({R}, {f'K >= {kmin}' if kmin > 0 else 'K'}, {D}), got {tuple(t.shape)}")
+        return t, int(t.shape[1])
 
     def _f32(self, t, *cols: int) -> torch.Tensor:
         """Accept torch (any device) or NumPy, return a contiguous f32 device tensor (B, *cols)."""
@@ -764,7 +803,7 @@ class MirScene(StepHelpers):
             out["jac"] = new(6, max(nd, 0))
         self._check(self.lib.mir_link_kinematics(self.h, C.byref(q), _ptr(idx), R, _ptr(out.get("pos")), _ptr(out.get("quat")), _ptr(out.get("vel")),
                                                  _ptr(out.get("jac")), self._stream()))
-        self.link_kinematics_launches = self.__dict__.get("link_kinematics_launches", 0) + 1
+        self._launched("link_kinematics")
         return out
 
     def link_accelerations(self, links, local_points=None, quat_offsets=None, env_idx=None, qacc=None, acc: bool = True,
@@ -801,7 +840,7 @@ class MirScene(StepHelpers):
         self._check(self.lib.mir_link_accelerations(self.h, C.byref(q), _ptr(idx), R, _ptr(qacc), _ptr(out.get("acc")), _ptr(out.get("bias_acc")),
                                                     _ptr(out.get("imu")), self._stream()))
         if out and R > 0:
-            self.link_accelerations_launches = self.__dict__.get("link_accelerations_launches", 0) + 1
+            self._launched("link_accelerations")
         return out
 
     def dynamics(self, env_idx=None, dof0: int = 0, n_dofs: Optional[int] = None, qpos=None, qvel=None, qacc=None, mass: bool = True,
@@ -843,7 +882,7 @@ class MirScene(StepHelpers):
                                           _ptr(out.get("bias")), _ptr(out.get("gravity")), _ptr(out.get("tau")), _ptr(out.get("ctrl_force")),
                                           self._stream()))
         if out and R > 0 and n > 0:
-            self.dynamics_launches = self.__dict__.get("dynamics_launches", 0) + 1
+            self._launched("dynamics")
         return out
 
     def task_dynamics(self, links=(), local_points=None, env_idx=None, dof0: int = 0, n_dofs: Optional[int] = None, qpos=None, x=None,
@@ -897,7 +936,7 @@ class MirScene(StepHelpers):
         self._check(self.lib.mir_task_dynamics(self.h, C.byref(q), _ptr(idx), R, _ptr(qpos), _ptr(x), _ptr(out.get("minv")), _ptr(out.get("solve")),
                                                _ptr(out.get("lambda_inv")), _ptr(out.get("lambda")), _ptr(out.get("jbar")), self._stream()))
         if R > 0 and any(v.numel() for v in out.values()):
-            self.task_dynamics_launches = self.__dict__.get("task_dynamics_launches", 0) + 1
+            self._launched("task_dynamics")
         return out
 
     def raycast(self, dirs, link: int = 0, pos_offset=(0.0, 0.0, 0.0), quat_offset=(1.0, 0.0, 0.0, 0.0), min_range: float = 0.0,
@@ -933,7 +972,7 @@ class MirScene(StepHelpers):
             out["normal"] = torch.empty((R, N, 3), dtype=torch.float32, device=self.device)
         self._check(self.lib.mir_raycast(self.h, C.byref(q), _ptr(d), _ptr(idx), R, _ptr(out.get("distance")), _ptr(out.get("points")),
                                          _ptr(out.get("geom")), _ptr(out.get("normal")), self._stream()))
-        self.raycast_launches = self.__dict__.get("raycast_launches", 0) + 1
+        self._launched("raycast")
         return out
 
     def _sphere_probes(self, probes, links, n_extra=None):
@@ -979,7 +1018,7 @@ class MirScene(StepHelpers):
         N = int(p.shape[0])
         q = make_dist_query(N, max_distance, skip_geoms)
         idx, R, qpos = self._sphere_qrows(env_idx, qpos)
-        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        new = self._row_alloc(R)
         out = {"distance": new(N)}
         if geom:
             out["geom"] = new(N, dtype=torch.int32)
@@ -993,7 +1032,7 @@ class MirScene(StepHelpers):
                                                  _ptr(qpos), _ptr(out["distance"]), _ptr(out.get("geom")), _ptr(out.get("closest")),
                                                  _ptr(out.get("normal")), _ptr(out.get("row_min")), _ptr(out.get("row_argmin")), self._stream()))
         if R > 0:
-            self.distance_launches = self.__dict__.get("distance_launches", 0) + 1
+            self._launched("distance")
         return out
 
     def self_distance(self, probes, links, link_mask, env_idx=None, qpos=None, max_distance: float = 1.0, n_extra: int = 0,
@@ -1009,7 +1048,7 @@ class MirScene(StepHelpers):
         NS = int(p.shape[0])
         sq = make_self_query(link_mask, n_extra, 0.0, max_distance)
         idx, R, qpos = self._sphere_qrows(env_idx, qpos)
-        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        new = self._row_alloc(R)
         out = {"distance": new(NS)}
         if other:
             out["other"] = new(NS, dtype=torch.int32)
@@ -1019,7 +1058,7 @@ class MirScene(StepHelpers):
                                                _ptr(idx), R, _ptr(qpos), _ptr(out["distance"]), _ptr(out.get("other")), _ptr(out.get("row_min")),
                                                _ptr(out.get("row_pair")), self._stream()))
         if R > 0:
-            self.self_launches = self.__dict__.get("self_launches", 0) + 1
+            self._launched("self")
         return out
 
     @staticmethod
@@ -1061,32 +1100,24 @@ class MirScene(StepHelpers):
         transform per row, `grasp` (R, 7) = its position xyz and quaternion wxyz in the link's frame (None: the kernel takes it from
         the start row), and the probes whose link is `body` ride on it; the body's own geoms must be in `skip_geoms`.  With or
         without `self_model`.  The result gains grasp (R, 7): the transform each row used."""
-        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
-        D = int(qa.shape[0])
-        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
+        s = _SphereCall(self, probes, links, dof_qadr, env_idx, qpos_start, self_model)
+        R, D, new = s.R, s.D, s.new
         goal = torch.as_tensor(qpos_goal, device=self.device).to(torch.float32).contiguous()
         if tuple(goal.shape) != (R, D):
             raise ValueError(f"qpos_goal must be ({R}, {D}), got {tuple(goal.shape)}")
-        q = make_plan_query(N, D, num_waypoints, max_nodes, max_iterations, smooth_passes, ignore_collision, seed, resolution, step,
-                            margin, max_distance, skip_geoms)
+        s.collision(carry, True, num_waypoints=num_waypoints, max_nodes=max_nodes, max_iterations=max_iterations, smooth_passes=smooth_passes,
+                    ignore_collision=ignore_collision, seed=seed, resolution=resolution, step=step, margin=margin, max_distance=max_distance,
+                    skip_geoms=skip_geoms)
         W = max(int(num_waypoints), 0)
-        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
         out = {"path": new(W, D), "status": new(dtype=torch.int32), "poly": new(PLAN_MAX_POLY, D), "n_poly": new(dtype=torch.int32),
                "stats": new(4, dtype=torch.int32)}
-        lkp = None if lk is None else lk.ctypes.data_as(C.c_void_p)
-        if carry is not None:
-            cq, grasp, out["grasp"] = self._carry_query(carry, R)
-            self._check(self.lib.mir_plan_path_carry(self.h, C.byref(q), None if sq is None else C.byref(sq), C.byref(cq), _ptr(p), lkp,
-                                                     qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(grasp), _ptr(goal),
-                                                     _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]),
-                                                     _ptr(out["stats"]), _ptr(out["grasp"]), self._stream()))
-        else:
-            fn, head = (self.lib.mir_plan_path, (self.h, C.byref(q))) if sq is None else (self.lib.mir_plan_path_self, (self.h, C.byref(q), C.byref(sq)))
-            self._check(fn(*head, _ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
-                           _ptr(qpos_start), _ptr(goal), _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]),
-                           _ptr(out["stats"]), self._stream()))
+        fn, head, form = s.symbol("mir_plan_path")
+        if form == "_carry":
+            out["grasp"] = s.grasp_used
+        self._check(fn(*head, *s.grasp_in, _ptr(goal), _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]),
+                       _ptr(out["stats"]), *s.grasp_out, self._stream()))
         if R > 0:
-            self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
+            self._launched("plan")
         return out
 
     def path_clearance(self, probes, links, dof_qadr, paths, env_idx=None, qpos_start=None, resolution: float = 0.05, margin: float = 0.0,
@@ -1097,39 +1128,21 @@ class MirScene(StepHelpers):
         int32: the first segment whose minimum is < margin, -1: none.  Everything else as plan_path().  With `self_model`
         (mir_path_clearance_self): also seg_self_min (R, K-1) and row_self_min (R,), and row_first_blocked counts either test.  With
         `carry` (as in plan_path(): mir_path_clearance_carry) the carried body's probes ride along, and the result gains grasp (R, 7)."""
-        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
-        D = int(qa.shape[0])
-        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
-        paths = torch.as_tensor(paths, device=self.device).to(torch.float32).contiguous()
-        if paths.dim() != 3 or paths.shape[0] != R or paths.shape[2] != D or paths.shape[1] < 2:
-            raise ValueError(f"paths must be ({R}, K >= 2, {D}), got {tuple(paths.shape)}")
-        K = int(paths.shape[1])
-        q = make_plan_query(N, D, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
-        out = {"seg_min": torch.empty((R, K - 1), dtype=torch.float32, device=self.device),
-               "row_min": torch.empty((R,), dtype=torch.float32, device=self.device),
-               "row_first_blocked": torch.empty((R,), dtype=torch.int32, device=self.device)}
-        if sq is not None:
-            out["seg_self_min"] = torch.empty((R, K - 1), dtype=torch.float32, device=self.device)
-            out["row_self_min"] = torch.empty((R,), dtype=torch.float32, device=self.device)
-        lkp = None if lk is None else lk.ctypes.data_as(C.c_void_p)
-        if carry is not None:
-            cq, grasp, out["grasp"] = self._carry_query(carry, R)
-            self._check(self.lib.mir_path_clearance_carry(self.h, C.byref(q), None if sq is None else C.byref(sq), C.byref(cq), _ptr(p), lkp,
-                                                          qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(grasp), _ptr(paths), K,
-                                                          _ptr(out["seg_min"]), _ptr(out.get("seg_self_min")), _ptr(out["row_min"]),
-                                                          _ptr(out.get("row_self_min")), _ptr(out["row_first_blocked"]), _ptr(out["grasp"]),
-                                                          self._stream()))
-        elif sq is None:
-            self._check(self.lib.mir_path_clearance(self.h, C.byref(q), _ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start),
-                                                    _ptr(paths), K, _ptr(out["seg_min"]), _ptr(out["row_min"]), _ptr(out["row_first_blocked"]),
-                                                    self._stream()))
-        else:
-            self._check(self.lib.mir_path_clearance_self(self.h, C.byref(q), C.byref(sq), _ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
-                                                         _ptr(qpos_start), _ptr(paths), K, _ptr(out["seg_min"]), _ptr(out["seg_self_min"]),
-                                                         _ptr(out["row_min"]), _ptr(out["row_self_min"]), _ptr(out["row_first_blocked"]),
-                                                         self._stream()))
+        s = _SphereCall(self, probes, links, dof_qadr, env_idx, qpos_start, self_model)
+        R, new = s.R, s.new
+        paths, K = self._rows_kd(paths, "paths", R, s.D, kmin=2)
+        s.collision(carry, True, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
+        out = {"seg_min": new(K - 1), "row_min": new(), "row_first_blocked": new(dtype=torch.int32)}
+        if s.sq is not None:
+            out["seg_self_min"], out["row_self_min"] = new(K - 1), new()
+        fn, head, form = s.symbol("mir_path_clearance")
+        if form == "_carry":
+            out["grasp"] = s.grasp_used
+        so = lambda k: (_ptr(out.get(k)),) if form else ()  # noqa: E731  (the plain entry point has no self outputs)
+        self._check(fn(*head, *s.grasp_in, _ptr(paths), K, _ptr(out["seg_min"]), *so("seg_self_min"), _ptr(out["row_min"]), *so("row_self_min"),
+                       _ptr(out["row_first_blocked"]), *s.grasp_out, self._stream()))
         if R > 0:
-            self.plan_launches = self.__dict__.get("plan_launches", 0) + 1
+            self._launched("plan")
         return out
 
     def certify_path(self, probes, links, dof_qadr, paths, env_idx=None, qpos_start=None, margin: float = 0.0, tol: float = 0.002,
@@ -1152,17 +1165,12 @@ class MirScene(StepHelpers):
         row_upper (R,), row_status, row_first (R,) int32 (the first segment that is not CLEAR, -1: none), stats (R, 4) int32:
         evaluations, leaves, deepest level, segments finished; with max_leaves > 0 also leaves (R, max_leaves, 3) int32: segment, level,
         index, -1 behind the row's count.  The call changes nothing a later call can see."""
-        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
-        D = int(qa.shape[0])
-        paths = torch.as_tensor(paths, device=self.device).to(torch.float32).contiguous()
-        if paths.dim() != 3 or paths.shape[0] != R or paths.shape[2] != D or paths.shape[1] < 2:
-            raise ValueError(f"paths must be ({R}, K >= 2, {D}), got {tuple(paths.shape)}")
-        K = int(paths.shape[1])
+        s = _SphereCall(self, probes, links, dof_qadr, env_idx, qpos_start)
+        R, new, i32 = s.R, s.new, torch.int32
+        paths, K = self._rows_kd(paths, "paths", R, s.D, kmin=2)
         q = make_cert_query(K, tol, guard, max_depth, max_evaluations, bracket, max_leaves)
-        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
-        pq = make_plan_query(N, D, ignore_collision=ignore_collision, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
-        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
-        i32 = torch.int32
+        s.self_model(self_model)   # (behind the two above: the order of this method's errors)
+        s.collision(ignore_collision=ignore_collision, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
         out = {"seg_lower": new(K - 1), "seg_upper": new(K - 1), "seg_status": new(K - 1, dtype=i32), "row_lower": new(), "row_upper": new(),
                "row_status": new(dtype=i32), "row_first": new(dtype=i32), "stats": new(4, dtype=i32)}
         if int(max_leaves) > 0:
@@ -1172,37 +1180,20 @@ class MirScene(StepHelpers):
                 if carry is None:
                     raise ValueError("grasp belongs to carry, which is None")
                 carry = {**carry, "grasp": grasp}
-            if sq is not None:
-                out.update(seg_self_lower=new(K - 1), seg_self_upper=new(K - 1), row_self_lower=new(), row_self_upper=new())
-            else:
-                inf = lambda *shape: torch.full((R, *shape), float("inf"), dtype=torch.float32, device=self.device)  # noqa: E731
-                out.update(seg_self_lower=inf(K - 1), seg_self_upper=inf(K - 1), row_self_lower=inf(), row_self_upper=inf())
-            cq, g = None, None
-            if carry is not None:
-                cq, g, out["grasp"] = self._carry_query(carry, R)
-            else:
-                out["grasp"] = torch.full((R, 7), float("nan"), dtype=torch.float32, device=self.device)
-            if R > 0:
-                lkp = None if lk is None else lk.ctypes.data_as(C.c_void_p)
-                so = [_ptr(out[k]) if sq is not None else None for k in ("seg_self_lower", "seg_self_upper", "row_self_lower", "row_self_upper")]
-                head = (self.h, C.byref(q), C.byref(pq), None if sq is None else C.byref(sq))
-                front = (_ptr(p), lkp, qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start))
-                outs = (_ptr(out["seg_lower"]), _ptr(out["seg_upper"]), so[0], so[1], _ptr(out["seg_status"]), _ptr(out["row_lower"]),
-                        _ptr(out["row_upper"]), so[2], so[3], _ptr(out["row_status"]), _ptr(out["row_first"]))
-                tail = (_ptr(out.get("leaves")), _ptr(out["stats"]), self._stream())
-                if cq is None:
-                    self._check(self.lib.mir_certify_path_self(*head, *front, _ptr(paths), *outs, *tail))
-                else:
-                    self._check(self.lib.mir_certify_path_carry(*head, C.byref(cq), *front, _ptr(g), _ptr(paths), *outs, _ptr(out["grasp"]), *tail))
-                self.cert_launches = self.__dict__.get("cert_launches", 0) + 1
-            return out
+            inf = lambda *shape: torch.full((R, *shape), float("inf"), dtype=torch.float32, device=self.device)  # noqa: E731
+            mk = new if s.sq is not None else inf
+            out.update(seg_self_lower=mk(K - 1), seg_self_upper=mk(K - 1), row_self_lower=mk(), row_self_upper=mk())
+            s.carry(carry, True)
+            out["grasp"] = s.grasp_used if carry is not None else torch.full((R, 7), float("nan"), dtype=torch.float32, device=self.device)
         if R > 0:   # (without rows there is nothing to point at)
-            self._check(self.lib.mir_certify_path(self.h, C.byref(q), C.byref(pq), _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p),
-                                                  qa.ctypes.data_as(C.c_void_p), _ptr(idx), R, _ptr(qpos_start), _ptr(paths), _ptr(out["seg_lower"]),
-                                                  _ptr(out["seg_upper"]), _ptr(out["seg_status"]), _ptr(out["row_lower"]), _ptr(out["row_upper"]),
-                                                  _ptr(out["row_status"]), _ptr(out["row_first"]), _ptr(out.get("leaves")), _ptr(out["stats"]),
-                                                  self._stream()))
-            self.cert_launches = self.__dict__.get("cert_launches", 0) + 1
+            fn, head, form = s.symbol("mir_certify_path", q)
+            # (the plain entry point has no self outputs; without a self model the other two get none either: the +inf stay)
+            so = lambda k: (_ptr(out[k]) if s.sq is not None else None,) if form else ()  # noqa: E731
+            self._check(fn(*head, *s.grasp_in, _ptr(paths), _ptr(out["seg_lower"]), _ptr(out["seg_upper"]), *so("seg_self_lower"),
+                           *so("seg_self_upper"), _ptr(out["seg_status"]), _ptr(out["row_lower"]), _ptr(out["row_upper"]), *so("row_self_lower"),
+                           *so("row_self_upper"), _ptr(out["row_status"]), _ptr(out["row_first"]), *s.grasp_out, _ptr(out.get("leaves")),
+                           _ptr(out["stats"]), self._stream()))
+            self._launched("cert")
         return out
 
     def cartesian_path(self, probes, links, dof_qadr, link_body: int, target_pos, target_quat=None, env_idx=None, qpos_start=None,
@@ -1221,13 +1212,9 @@ class MirScene(StepHelpers):
         repeated), n_points (R,) int32, fraction (R,) = accepted samples / all samples, status (R,) int32 (spec.CART_STATUS), stats
         (R, 4) int32: IK iterations, configurations checked, samples S, the segment that failed or -1; with num_waypoints = W >= 2 also
         path (R, W, D): the points resampled at equal steps of their index.  The call changes nothing a later call can see."""
-        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
-        D = int(qa.shape[0])
-        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
-        tp = torch.as_tensor(target_pos, device=self.device).to(torch.float32).contiguous()
-        if tp.dim() != 3 or tp.shape[0] != R or tp.shape[2] != 3 or tp.shape[1] < 1:
-            raise ValueError(f"target_pos must be ({R}, K >= 1, 3), got {tuple(tp.shape)}")
-        K = int(tp.shape[1])
+        s = _SphereCall(self, probes, links, dof_qadr, env_idx, qpos_start, self_model)
+        R, D, new = s.R, s.D, s.new
+        tp, K = self._rows_kd(target_pos, "target_pos", R, 3, kmin=1)
         tq = None
         if target_quat is not None:
             tq = torch.as_tensor(target_quat, device=self.device).to(torch.float32).contiguous()
@@ -1235,20 +1222,17 @@ class MirScene(StepHelpers):
                 raise ValueError(f"target_quat must be ({R}, {K}, 4), got {tuple(tq.shape)}")
         P, W = int(max_points), int(num_waypoints)
         q = make_cart_query(link_body, K, P, W, max_pos_step, max_rot_step, jump_threshold)
-        pq = make_plan_query(N, D, ignore_collision=ignore_collision, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
-        cq = None if carry is None else make_carry_query(carry["body"], carry["link"])
+        s.collision(carry, False, ignore_collision=ignore_collision, resolution=resolution, margin=margin, max_distance=max_distance,
+                    skip_geoms=skip_geoms)
         o = self._ik_options(ik_options)
-        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
         out = {"points": new(max(P, 0), D), "n_points": new(dtype=torch.int32), "fraction": new(), "status": new(dtype=torch.int32),
                "stats": new(4, dtype=torch.int32)}
         if W > 0:
             out["path"] = new(W, D)
         if R > 0:   # (without rows there is nothing to point at)
-            self._check(self.lib.mir_cartesian_path(self.h, C.byref(q), C.byref(pq), None if sq is None else C.byref(sq), None if cq is None else C.byref(cq),
-                                                    _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p), qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
-                                                    _ptr(qpos_start), _ptr(tp), _ptr(tq), C.byref(o), _ptr(out["points"]), _ptr(out["n_points"]),
+            self._check(self.lib.mir_cartesian_path(*s.head(q), _ptr(tp), _ptr(tq), C.byref(o), _ptr(out["points"]), _ptr(out["n_points"]),
                                                     _ptr(out["fraction"]), _ptr(out["status"]), _ptr(out.get("path")), _ptr(out["stats"]), self._stream()))
-            self.cart_launches = self.__dict__.get("cart_launches", 0) + 1
+            self._launched("cart")
         return out
 
     def blend_path(self, probes, links, dof_qadr, poly, n_poly=None, env_idx=None, qpos_start=None, max_deviation: float = 0.05,
@@ -1266,13 +1250,9 @@ class MirScene(StepHelpers):
         accepted half-length at each input node, stats (R, 4) int32: nodes kept, corners blended, corners left sharp, configurations
         checked; with num_waypoints = W >= 2 also path (R, W, D): the points resampled at equal arc length.  A row that fails holds its
         first node everywhere.  The call changes nothing a later call can see."""
-        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
-        D = int(qa.shape[0])
-        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
-        poly = torch.as_tensor(poly, device=self.device).to(torch.float32).contiguous()
-        if poly.dim() != 3 or poly.shape[0] != R or poly.shape[2] != D:
-            raise ValueError(f"poly must be ({R}, K, {D}), got {tuple(poly.shape)}")
-        K = int(poly.shape[1])
+        s = _SphereCall(self, probes, links, dof_qadr, env_idx, qpos_start, self_model)
+        R, D, new = s.R, s.D, s.new
+        poly, K = self._rows_kd(poly, "poly", R, D)
         if n_poly is not None:
             n_poly = torch.as_tensor(n_poly, device=self.device).to(torch.int32).contiguous()
             if tuple(n_poly.shape) != (R,):
@@ -1280,19 +1260,16 @@ class MirScene(StepHelpers):
         W = int(num_waypoints)
         q = make_blend_query(K, max_deviation, blend_points, max_shrinks, max_points, W)
         P = int(q.max_points)
-        pq = make_plan_query(N, D, ignore_collision=ignore_collision, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
-        cq = None if carry is None else make_carry_query(carry["body"], carry["link"])
-        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        s.collision(carry, False, ignore_collision=ignore_collision, resolution=resolution, margin=margin, max_distance=max_distance,
+                    skip_geoms=skip_geoms)
         out = {"points": new(max(P, 0), D), "n_points": new(dtype=torch.int32), "status": new(dtype=torch.int32), "blend_len": new(PLAN_MAX_POLY),
                "stats": new(4, dtype=torch.int32)}
         if W > 0:
             out["path"] = new(W, D)
         if R > 0:   # (without rows there is nothing to point at)
-            self._check(self.lib.mir_blend_path(self.h, C.byref(q), C.byref(pq), None if sq is None else C.byref(sq), None if cq is None else C.byref(cq),
-                                                _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p), qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
-                                                _ptr(qpos_start), _ptr(poly), _ptr(n_poly), _ptr(out["points"]), _ptr(out["n_points"]), _ptr(out["status"]),
+            self._check(self.lib.mir_blend_path(*s.head(q), _ptr(poly), _ptr(n_poly), _ptr(out["points"]), _ptr(out["n_points"]), _ptr(out["status"]),
                                                 _ptr(out.get("path")), _ptr(out["blend_len"]), _ptr(out["stats"]), self._stream()))
-            self.blend_launches = self.__dict__.get("blend_launches", 0) + 1
+            self._launched("blend")
         return out
 
     def optimize_path(self, probes, links, dof_qadr, paths, env_idx=None, qpos_start=None, smooth_weight=None, obstacle_weight=None,
@@ -1314,26 +1291,19 @@ class MirScene(StepHelpers):
         configurations checked in the sweep, stop (spec.OPT_STOP), min_d (R,): the lowest distance beyond the margin of a sphere at an
         interior waypoint of `path`; with `grad0` also grad0 (R, K, D): the gradient of U at the input (a test hook).  The call changes
         nothing a later call can see."""
-        p, lk, qa, idx, R, qpos_start = self._plan_front(probes, links, dof_qadr, env_idx, qpos_start)
-        D = int(qa.shape[0])
-        sq, N = (None, int(p.shape[0])) if self_model is None else self._self_query(self_model, int(p.shape[0]))
-        paths = torch.as_tensor(paths, device=self.device).to(torch.float32).contiguous()
-        if paths.dim() != 3 or paths.shape[0] != R or paths.shape[2] != D:
-            raise ValueError(f"paths must be ({R}, K, {D}), got {tuple(paths.shape)}")
-        K = int(paths.shape[1])
+        s = _SphereCall(self, probes, links, dof_qadr, env_idx, qpos_start, self_model)
+        R, D, new = s.R, s.D, s.new
+        paths, K = self._rows_kd(paths, "paths", R, D)
         q = make_opt_query(K, smooth_weight, obstacle_weight, activation, step, max_iterations, max_halvings, ftol)
-        pq = make_plan_query(N, D, ignore_collision=ignore_collision, resolution=resolution, margin=margin, max_distance=max_distance, skip_geoms=skip_geoms)
-        cq = None if carry is None else make_carry_query(carry["body"], carry["link"])
-        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        s.collision(carry, False, ignore_collision=ignore_collision, resolution=resolution, margin=margin, max_distance=max_distance,
+                    skip_geoms=skip_geoms)
         out = {"path": new(K, D), "status": new(dtype=torch.int32), "cost": new(4), "stats": new(6, dtype=torch.int32), "min_d": new()}
         if grad0:
             out["grad0"] = new(K, D)
         if R > 0:   # (without rows there is nothing to point at)
-            self._check(self.lib.mir_optimize_path(self.h, C.byref(q), C.byref(pq), None if sq is None else C.byref(sq), None if cq is None else C.byref(cq),
-                                                   _ptr(p), None if lk is None else lk.ctypes.data_as(C.c_void_p), qa.ctypes.data_as(C.c_void_p), _ptr(idx), R,
-                                                   _ptr(qpos_start), _ptr(paths), K, _ptr(out["path"]), _ptr(out["status"]), _ptr(out["cost"]),
+            self._check(self.lib.mir_optimize_path(*s.head(q), _ptr(paths), K, _ptr(out["path"]), _ptr(out["status"]), _ptr(out["cost"]),
                                                    _ptr(out["stats"]), _ptr(out["min_d"]), _ptr(out.get("grad0")), self._stream()))
-            self.opt_launches = self.__dict__.get("opt_launches", 0) + 1
+            self._launched("opt")
         return out
 
     def retime_path(self, paths, vmax, amax, dt, num_samples: int = 0, max_path_speed=None, extra=None, velocity: bool = False) -> dict:
@@ -1361,7 +1331,7 @@ class MirScene(StepHelpers):
                 ex = [None] * 4
         T = int(num_samples)
         q = make_retime_query(D, K, vmax, amax, dt, T, max_path_speed, E)
-        new = lambda *shape, dtype=torch.float32: torch.empty((R, *shape), dtype=dtype, device=self.device)  # noqa: E731
+        new = self._row_alloc(R)
         out = {"x": new(K), "t": new(K), "duration": new(), "status": new(dtype=torch.int32), "n_samples": new(dtype=torch.int32)}
         if T > 0:
             out["samples"] = new(T, D)
@@ -1371,7 +1341,7 @@ class MirScene(StepHelpers):
             self._check(self.lib.mir_retime_path(self.h, C.byref(q), R, _ptr(paths), *(_ptr(e) for e in ex), _ptr(out["x"]), _ptr(out["t"]),
                                                  _ptr(out["duration"]), _ptr(out["status"]), _ptr(out["n_samples"]), _ptr(out.get("samples")),
                                                  _ptr(out.get("sample_vel")), self._stream()))
-            self.retime_launches = self.__dict__.get("retime_launches", 0) + 1
+            self._launched("retime")
         return out
 
     def render(self, cam: MirCameraSpec, vis: MirVisualSpec, mode: int = 0, env_offset: Optional[torch.Tensor] = None,
@@ -1570,6 +1540,6 @@ class MirScene(StepHelpers):
         if n > 0:   # (no rows: nothing to launch, and an empty tensor has no address to pass)
             self._check(self.lib.mir_inverse_kinematics_multilink(self.h, C.byref(q), _ptr(p), _ptr(qq), _ptr(iq), C.byref(o), _ptr(out), _ptr(err),
                                                                   _ptr(iters), _ptr(sample), self._stream()))
-            self.ik_multilink_launches = self.__dict__.get("ik_multilink_launches", 0) + 1
+            self._launched("ik_multilink")
         res = (out,) + ((err,) if return_error else ()) + (({"iters": iters, "sample": sample},) if return_info else ())
         return res if len(res) > 1 else out

@@ -850,16 +850,13 @@ class EntityView:
 
     def _plan_args(self, envs_idx, qpos_start, with_entity, ignore_entities, who, self_collision=None, self_margin=0.0, attached_entity=None,
                    ee_link_name=None, grasp_pose=None, attached_links=None):
-        mir = self._mir
-        if getattr(mir, "plan_path", None) is None:
-            raise NotImplementedError("this scene has no motion planning (MirScene.plan_path / mir_plan_path)")
+        self._need("plan_path", "motion planning")
         if not self.dof_idx:
             raise NotImplementedError(f"{who}: an entity without scalar joints")
         _, lk, dev_probes, own = self._clearance_model()
         extra = {}
         if self._self_on(self_collision):
-            if getattr(mir, "self_distance", None) is None:
-                raise NotImplementedError("this scene has no self-collision queries (MirScene.self_distance / mir_self_distance)")
+            self._need("self_distance", "self-collision queries")
             dev_probes, lk, extra["self_model"] = self._self_args(self_margin)
         idx, R, kw = self._state_rows(envs_idx, who, qpos=qpos_start)
         args = dict(probes=dev_probes, links=lk, dof_qadr=self._qcols, env_idx=idx, qpos_start=kw.get("qpos"),
@@ -871,6 +868,42 @@ class EntityView:
         elif ee_link_name is not None or grasp_pose is not None or attached_links is not None:
             raise ValueError(f"{who}: ee_link_name, grasp_pose and attached_links belong to attached_entity, which is None")
         return args, R
+
+    def _need(self, method: str, what: str) -> None:
+        """refuses a scene whose backend has no MirScene.<method>"""
+        if getattr(self._mir, method, None) is None:
+            raise NotImplementedError(f"this scene has no {what} (MirScene.{method} / mir_{method})")
+
+    def _plan_args_grasp_at_start(self, who, entry, grasp_pose, envs_idx, qpos_start, with_entity, ignore_entities, self_collision, self_margin,
+                                  attached_entity, ee_link_name, attached_links):
+        """_plan_args() for a method whose entry point has no grasp rows: `grasp_pose` is refused, carry = dict(body, link) alone"""
+        if grasp_pose is not None:
+            raise NotImplementedError(f"{who}: the grasp is taken from where the attached entity is at the start ({entry} has no grasp rows); "
+                                      "grasp_pose must be None")
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, who, self_collision, self_margin, attached_entity, ee_link_name,
+                                  None, attached_links)
+        if "carry" in args:
+            args["carry"] = dict(body=args["carry"]["body"], link=args["carry"]["link"])
+        return args, R
+
+    def _path_rows(self, path, R: int, kmin: int, name: str, axis: int, letter: str = "K") -> torch.Tensor:
+        """`path` as float32 device rows (R, K, n), K >= kmin.  axis: where its K stands -- 0: (K, R, n), the layout plan_path() returns;
+        1: (R, K, n), blend_path's poly.  An unbatched task may leave the env axis out."""
+        n = len(self._qcols)
+        p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
+        if self.__dict__.get("unbatched") and p.dim() == 2:
+            p = p.unsqueeze(1 - axis)
+        if p.dim() != 3 or p.shape[1 - axis] != R or p.shape[2] != n or p.shape[axis] < kmin:
+            k = f"{letter} >= {kmin}" if kmin > 0 else letter
+            raise ValueError(f"{name} must be ({f'{R}, {k}' if axis else f'{k}, {R}'}, {n}), got {tuple(p.shape)}")
+        return (p if axis else p.permute(1, 0, 2)).contiguous()
+
+    def _drop_env_axis(self, detail: dict, axis1=("path",)) -> dict:
+        """on an unbatched task (no env axis anywhere): every entry of `detail` without it -- axis 1 of those named in `axis1`, axis 0 of the
+        others"""
+        if not self.__dict__.get("unbatched"):
+            return detail
+        return {k: (v[:, 0] if k in axis1 else v[0]) for k, v in detail.items()}
 
     def plan_path(self, qpos_goal, qpos_start=None, timeout=None, smooth_path=True, num_waypoints=100, ignore_collision=False,
                   planner="RRTConnect", envs_idx=None, return_valid_mask=False, resolution=0.05, step=0.3, margin=0.0, max_nodes=256,
@@ -910,18 +943,14 @@ class EntityView:
         r = self._mir.plan_path(qpos_goal=goal, num_waypoints=int(num_waypoints), max_nodes=int(max_nodes), max_iterations=int(max_iterations),
                                 smooth_passes=64 if smooth_path else 0, ignore_collision=bool(ignore_collision), seed=int(seed),
                                 resolution=float(resolution), step=float(step), margin=float(margin), max_distance=max(1.0, 2.0 * float(margin)), **args)
-        one = bool(self.__dict__.get("unbatched"))
-        path = r["path"].permute(1, 0, 2).contiguous()
-        valid = r["status"] == 0
-        detail = {"path": path, "valid": valid, "status": r["status"], "poly": r["poly"], "n_poly": r["n_poly"], "stats": r["stats"]}
+        detail = {"path": r["path"].permute(1, 0, 2).contiguous(), "valid": r["status"] == 0, "status": r["status"], "poly": r["poly"],
+                  "n_poly": r["n_poly"], "stats": r["stats"]}
         if "grasp" in r:
             detail["grasp"] = r["grasp"]
-        if one:   # (an unbatched task: no env axis anywhere)
-            detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
-            path, valid = detail["path"], detail["valid"]
+        detail = self._drop_env_axis(detail)
         if return_detail:
             return detail
-        return (path, valid) if return_valid_mask else path
+        return (detail["path"], detail["valid"]) if return_valid_mask else detail["path"]
 
     def get_path_clearance(self, path, envs_idx=None, qpos_start=None, resolution=0.05, margin=0.0, with_entity=None, ignore_entities=(),
                            max_distance: float = 1.0, return_detail: bool = False, self_collision=None, self_margin=0.0, attached_entity=None,
@@ -939,20 +968,14 @@ class EntityView:
         self_clearance, which is then reported whether or not `self_collision` is on; the detail gains grasp (R, 7)."""
         args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "get_path_clearance", self_collision, self_margin,
                                   attached_entity, ee_link_name, grasp_pose, attached_links)
-        p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
-        if self.__dict__.get("unbatched") and p.dim() == 2:
-            p = p[:, None]
-        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != len(self._qcols) or p.shape[0] < 2:
-            raise ValueError(f"path must be (K >= 2, {R}, {len(self._qcols)}), got {tuple(p.shape)}")
-        r = self._mir.path_clearance(paths=p.permute(1, 0, 2).contiguous(), resolution=float(resolution), margin=float(margin),
+        r = self._mir.path_clearance(paths=self._path_rows(path, R, 2, "path", 0), resolution=float(resolution), margin=float(margin),
                                      max_distance=max(float(max_distance), 2.0 * float(margin)), **args)
         out = {"clearance": r["row_min"], "seg_min": r["seg_min"], "first_blocked": r["row_first_blocked"]}
         if "self_model" in args:
             out["self_clearance"], out["self_seg_min"] = r["row_self_min"], r["seg_self_min"]
         if "grasp" in r:
             out["grasp"] = r["grasp"]
-        if self.__dict__.get("unbatched"):
-            out = {k: v[0] for k, v in out.items()}
+        out = self._drop_env_axis(out, ())
         if return_detail or "self_model" not in args:
             return out if return_detail else out["clearance"]
         return torch.minimum(out["clearance"] - float(margin), out["self_clearance"] - float(self_margin)) + float(margin)
@@ -987,23 +1010,34 @@ class EntityView:
         if self_collision or attached_entity is not None:
             raise ValueError("certify_path: the self and carried-object tests are sampled only (get_path_clearance); the certified rule "
                              "covers the sphere model against the static scene -- certify_sweep() certifies all three")
-        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "certify_path", False)
-        if getattr(self._mir, "certify_path", None) is None:
-            raise NotImplementedError("this scene has no certified clearance (MirScene.certify_path / mir_certify_path)")
-        p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
-        if self.__dict__.get("unbatched") and p.dim() == 2:
-            p = p[:, None]
-        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != len(self._qcols) or p.shape[0] < 2:
-            raise ValueError(f"path must be (K >= 2, {R}, {len(self._qcols)}), got {tuple(p.shape)}")
-        r = self._mir.certify_path(paths=p.permute(1, 0, 2).contiguous(), margin=float(margin), tol=float(tol), guard=float(guard),
-                                   max_depth=int(max_depth), max_evaluations=int(max_evaluations), bracket=bool(bracket),
-                                   max_leaves=int(max_leaves), max_distance=max(float(max_distance), 2.0 * float(margin)), **args)
+        return self._certify("certify_path", False, path, margin, tol, guard, max_depth, max_evaluations, bracket, max_leaves, max_distance,
+                             return_detail, envs_idx, qpos_start, with_entity, ignore_entities)
+
+    def _certify(self, who, sweep: bool, path, margin, tol, guard, max_depth, max_evaluations, bracket, max_leaves, max_distance, return_detail,
+                 envs_idx, qpos_start, with_entity, ignore_entities, self_collision=False, self_margin=0.0, attached_entity=None,
+                 ee_link_name=None, grasp_pose=None, attached_links=None):
+        """certify_sweep(), and certify_path(): that without a self model and a carried object, and (`sweep` False) without their keys"""
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, who, self_collision, self_margin, attached_entity,
+                                  ee_link_name, grasp_pose, attached_links)
+        self._need("certify_path", "certified clearance")
+        rows = self._path_rows(path, R, 2, "path", 0)
+        K = int(rows.shape[1])
+        r = self._mir.certify_path(paths=rows, margin=float(margin), tol=float(tol), guard=float(guard), max_depth=int(max_depth),
+                                   max_evaluations=int(max_evaluations), bracket=bool(bracket), max_leaves=int(max_leaves),
+                                   max_distance=max(float(max_distance), 2.0 * float(margin)), **args)
         out = {"status": r["row_status"], "first": r["row_first"], "lower": r["row_lower"], "upper": r["row_upper"], "seg_lower": r["seg_lower"],
                "seg_upper": r["seg_upper"], "seg_status": r["seg_status"], "stats": r["stats"]}
+        if sweep:
+            dev = self._mir.device
+            inf = lambda *shape: torch.full((R, *shape), float("inf"), dtype=torch.float32, device=dev)  # noqa: E731
+            out.update({"self_lower": r["row_self_lower"] if "row_self_lower" in r else inf(),
+                        "self_upper": r["row_self_upper"] if "row_self_upper" in r else inf(),
+                        "seg_self_lower": r["seg_self_lower"] if "seg_self_lower" in r else inf(K - 1),
+                        "seg_self_upper": r["seg_self_upper"] if "seg_self_upper" in r else inf(K - 1),
+                        "grasp": r["grasp"] if "grasp" in r else torch.full((R, 7), float("nan"), dtype=torch.float32, device=dev)})
         if "leaves" in r:
             out["leaves"] = r["leaves"]
-        if self.__dict__.get("unbatched"):
-            out = {k: v[0] for k, v in out.items()}
+        out = self._drop_env_axis(out, ())
         return out if return_detail else out["status"]
 
     def path_is_certified_clear(self, path, margin: float = 0.0, **kwargs) -> torch.Tensor:
@@ -1027,32 +1061,9 @@ class EntityView:
         get_path_clearance().  return_detail=True: the dict of certify_path() plus self_lower, self_upper (R,), seg_self_lower,
         seg_self_upper (R, K-1) (+inf when neither a self model nor a carried object is in play) and grasp (R, 7) (NaN without a carried
         object).  Without self test and carried object this is certify_path()."""
-        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "certify_sweep", self_collision, self_margin, attached_entity,
-                                  ee_link_name, grasp_pose, attached_links)
-        if getattr(self._mir, "certify_path", None) is None:
-            raise NotImplementedError("this scene has no certified clearance (MirScene.certify_path / mir_certify_path)")
-        p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
-        if self.__dict__.get("unbatched") and p.dim() == 2:
-            p = p[:, None]
-        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != len(self._qcols) or p.shape[0] < 2:
-            raise ValueError(f"path must be (K >= 2, {R}, {len(self._qcols)}), got {tuple(p.shape)}")
-        K = int(p.shape[0])
-        r = self._mir.certify_path(paths=p.permute(1, 0, 2).contiguous(), margin=float(margin), tol=float(tol), guard=float(guard),
-                                   max_depth=int(max_depth), max_evaluations=int(max_evaluations), bracket=bool(bracket),
-                                   max_leaves=int(max_leaves), max_distance=max(float(max_distance), 2.0 * float(margin)), **args)
-        dev = self._mir.device
-        inf = lambda *shape: torch.full((R, *shape), float("inf"), dtype=torch.float32, device=dev)  # noqa: E731
-        out = {"status": r["row_status"], "first": r["row_first"], "lower": r["row_lower"], "upper": r["row_upper"], "seg_lower": r["seg_lower"],
-               "seg_upper": r["seg_upper"], "seg_status": r["seg_status"], "stats": r["stats"],
-               "self_lower": r["row_self_lower"] if "row_self_lower" in r else inf(), "self_upper": r["row_self_upper"] if "row_self_upper" in r else inf(),
-               "seg_self_lower": r["seg_self_lower"] if "seg_self_lower" in r else inf(K - 1),
-               "seg_self_upper": r["seg_self_upper"] if "seg_self_upper" in r else inf(K - 1),
-               "grasp": r["grasp"] if "grasp" in r else torch.full((R, 7), float("nan"), dtype=torch.float32, device=dev)}
-        if "leaves" in r:
-            out["leaves"] = r["leaves"]
-        if self.__dict__.get("unbatched"):
-            out = {k: v[0] for k, v in out.items()}
-        return out if return_detail else out["status"]
+        return self._certify("certify_sweep", True, path, margin, tol, guard, max_depth, max_evaluations, bracket, max_leaves, max_distance,
+                             return_detail, envs_idx, qpos_start, with_entity, ignore_entities, self_collision, self_margin, attached_entity,
+                             ee_link_name, grasp_pose, attached_links)
 
     def sweep_is_certified_clear(self, path, **kwargs) -> torch.Tensor:
         """(R,) bool: certify_sweep(path, ...) is CLEAR -- proven clear of the scene, of itself and with what it carries along the
@@ -1084,13 +1095,9 @@ class EntityView:
         and stats (R, 4).  On an unbatched task every result comes without its env axis.
         What it does not do: no escape from a blocked line (that is plan_path's job), no null-space objective, one link, no axis
         masks; clearance between two samples is as coarse as the planner's edge rule."""
-        if grasp_pose is not None:
-            raise NotImplementedError("plan_cartesian_path: the grasp is taken from where the attached entity is at the start (mir_cartesian_path "
-                                      "has no grasp rows); grasp_pose must be None")
-        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "plan_cartesian_path", self_collision, self_margin,
-                                  attached_entity, ee_link_name, None, attached_links)
-        if getattr(self._mir, "cartesian_path", None) is None:
-            raise NotImplementedError("this scene has no Cartesian paths (MirScene.cartesian_path / mir_cartesian_path)")
+        args, R = self._plan_args_grasp_at_start("plan_cartesian_path", "mir_cartesian_path", grasp_pose, envs_idx, qpos_start, with_entity,
+                                                 ignore_entities, self_collision, self_margin, attached_entity, ee_link_name, attached_links)
+        self._need("cartesian_path", "Cartesian paths")
         dev = self._mir.device
         p = torch.as_tensor(pos, device=dev).to(torch.float32)
         if p.dim() <= 2:
@@ -1102,8 +1109,6 @@ class EntityView:
         if quat is not None:
             q = torch.as_tensor(quat, device=dev).to(torch.float32)
             q = q.reshape(1, 1, 4).expand(R, K, 4) if q.numel() == 4 else q.reshape(R, K, 4)
-        if "carry" in args:
-            args["carry"] = dict(body=args["carry"]["body"], link=args["carry"]["link"])
         W = None if num_waypoints is None else int(num_waypoints)
         r = self._mir.cartesian_path(link_body=self._link_body(link), target_pos=p.contiguous(), target_quat=None if q is None else q.contiguous(),
                                      max_pos_step=float(max_step), max_rot_step=float(max_rot_step), jump_threshold=float(jump_threshold),
@@ -1112,8 +1117,7 @@ class EntityView:
         path = (r["points"] if W is None else r["path"]).permute(1, 0, 2).contiguous()
         detail = {"path": path, "fraction": r["fraction"], "valid": r["status"] == 0, "status": r["status"], "points": r["points"],
                   "n_points": r["n_points"], "stats": r["stats"]}
-        if self.__dict__.get("unbatched"):   # (an unbatched task: no env axis anywhere)
-            detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
+        detail = self._drop_env_axis(detail)
         if return_detail:
             return detail
         return (detail["path"], detail["fraction"]) if return_fraction else detail["path"]
@@ -1143,33 +1147,21 @@ class EntityView:
         checked.  On an unbatched task every result comes without its env axis ((K, n) is accepted for poly).
         What it does not do: a reversal is still a stop; no jerk limit; the straight remainders of the input's segments are not checked
         again (the input was checked by whoever made it; get_path_clearance answers for the result)."""
-        if grasp_pose is not None:
-            raise NotImplementedError("blend_path: the grasp is taken from where the attached entity is at the start (mir_blend_path has no "
-                                      "grasp rows); grasp_pose must be None")
-        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "blend_path", self_collision, self_margin, attached_entity,
-                                  ee_link_name, None, attached_links)
-        if getattr(self._mir, "blend_path", None) is None:
-            raise NotImplementedError("this scene has no corner blending (MirScene.blend_path / mir_blend_path)")
-        one = bool(self.__dict__.get("unbatched"))
-        p = torch.as_tensor(poly, device=self._mir.device).to(torch.float32)
-        if one and p.dim() == 2:
-            p = p[None]
-        if p.dim() != 3 or p.shape[0] != R or p.shape[2] != len(self._qcols):
-            raise ValueError(f"poly must be ({R}, K, {len(self._qcols)}), got {tuple(p.shape)}")
+        args, R = self._plan_args_grasp_at_start("blend_path", "mir_blend_path", grasp_pose, envs_idx, qpos_start, with_entity, ignore_entities,
+                                                 self_collision, self_margin, attached_entity, ee_link_name, attached_links)
+        self._need("blend_path", "corner blending")
+        rows = self._path_rows(poly, R, 0, "poly", 1)
         if n_poly is not None:
             n_poly = torch.as_tensor(n_poly, device=self._mir.device).to(torch.int32).reshape(-1)
-        if "carry" in args:
-            args["carry"] = dict(body=args["carry"]["body"], link=args["carry"]["link"])
         W = None if num_waypoints is None else int(num_waypoints)
-        r = self._mir.blend_path(poly=p.contiguous(), n_poly=n_poly, max_deviation=float(max_deviation), blend_points=int(blend_points),
+        r = self._mir.blend_path(poly=rows, n_poly=n_poly, max_deviation=float(max_deviation), blend_points=int(blend_points),
                                  max_shrinks=int(max_shrinks), max_points=None if max_points is None else int(max_points),
                                  num_waypoints=0 if W is None else W, ignore_collision=bool(ignore_collision), resolution=float(resolution),
                                  margin=float(margin), max_distance=max(1.0, 2.0 * float(margin)), **args)
         path = (r["points"] if W is None else r["path"]).permute(1, 0, 2).contiguous()
         detail = {"path": path, "valid": (r["status"] == 0) | (r["status"] == 32), "status": r["status"], "points": r["points"],
                   "n_points": r["n_points"], "blend_len": r["blend_len"], "stats": r["stats"]}
-        if one:   # (an unbatched task: no env axis anywhere)
-            detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
+        detail = self._drop_env_axis(detail)
         return detail if return_detail else detail["path"]
 
     # ---- trajectory optimisation (MirScene.optimize_path / mir_optimize_path): the planner's path as a seed, a shorter, smoother path
@@ -1196,32 +1188,20 @@ class EntityView:
         swept, stop (spec.OPT_STOP), and min_d (R,).  On an unbatched task every result comes without its env axis.
         What it does not do: no self-collision term in the cost (the sweep alone tests it); the cost looks at the waypoints only; no
         velocity, acceleration or torque limits (retime_path); fixed ends; no restarts; a BLOCKED row is not repaired."""
-        if grasp_pose is not None:
-            raise NotImplementedError("optimize_path: the grasp is taken from where the attached entity is at the start (mir_optimize_path has "
-                                      "no grasp rows); grasp_pose must be None")
-        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "optimize_path", self_collision, self_margin, attached_entity,
-                                  ee_link_name, None, attached_links)
-        if getattr(self._mir, "optimize_path", None) is None:
-            raise NotImplementedError("this scene has no trajectory optimisation (MirScene.optimize_path / mir_optimize_path)")
-        one = bool(self.__dict__.get("unbatched"))
-        p = torch.as_tensor(path, device=self._mir.device).to(torch.float32)
-        if one and p.dim() == 2:
-            p = p[:, None]
-        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != len(self._qcols) or p.shape[0] < 3:
-            raise ValueError(f"path must be (W >= 3, {R}, {len(self._qcols)}), got {tuple(p.shape)}")
-        if "carry" in args:
-            args["carry"] = dict(body=args["carry"]["body"], link=args["carry"]["link"])
+        args, R = self._plan_args_grasp_at_start("optimize_path", "mir_optimize_path", grasp_pose, envs_idx, qpos_start, with_entity,
+                                                 ignore_entities, self_collision, self_margin, attached_entity, ee_link_name, attached_links)
+        self._need("optimize_path", "trajectory optimisation")
+        rows = self._path_rows(path, R, 3, "path", 0, letter="W")
         from ..backend.spec import OPT_DEFAULTS
 
         eps = OPT_DEFAULTS["activation"] if activation is None else float(activation)
-        r = self._mir.optimize_path(paths=p.permute(1, 0, 2).contiguous(), smooth_weight=smooth_weight, obstacle_weight=obstacle_weight,
+        r = self._mir.optimize_path(paths=rows, smooth_weight=smooth_weight, obstacle_weight=obstacle_weight,
                                     activation=activation, step=step, max_iterations=max_iterations, max_halvings=max_halvings, ftol=ftol,
                                     ignore_collision=bool(ignore_collision), resolution=float(resolution), margin=float(margin),
                                     max_distance=max(1.0, 2.0 * (float(margin) + eps)), **args)
         detail = {"path": r["path"].permute(1, 0, 2).contiguous(), "valid": r["status"] == 0, "status": r["status"], "cost": r["cost"],
                   "stats": r["stats"], "min_d": r["min_d"]}
-        if one:   # (an unbatched task: no env axis anywhere)
-            detail = {k: (v[:, 0] if k == "path" else v[0]) for k, v in detail.items()}
+        detail = self._drop_env_axis(detail)
         return detail if return_detail else detail["path"]
 
     # ---- time parameterisation (MirScene.retime_path / mir_retime_path): what stands between plan_path and control_dofs_position.
@@ -1299,23 +1279,18 @@ class EntityView:
         waypoints of the refined path, K' = (K - 1) r + 1.  On an unbatched task (num_envs = 0) every result comes without its env axis.
         Not done: corners are not blended (a dof's velocity changes at a kink within one sample), no jerk limit, rest at both ends."""
         mir = self._mir
-        if getattr(mir, "retime_path", None) is None:
-            raise NotImplementedError("this scene has no time parameterisation (MirScene.retime_path / mir_retime_path)")
+        self._need("retime_path", "time parameterisation")
         n = len(self._qcols)
         if not n:
             raise NotImplementedError("retime_path: an entity without scalar joints")
         one = bool(self.__dict__.get("unbatched"))
         idx = _env_index(mir, envs_idx)
         R = mir.num_envs if idx is None else int(idx.numel())
-        p = torch.as_tensor(path, device=mir.device).to(torch.float32)
-        if one and p.dim() == 2:
-            p = p[:, None]
-        if p.dim() != 3 or p.shape[1] != R or p.shape[2] != n or p.shape[0] < 2:
-            raise ValueError(f"path must be (K >= 2, {R}, {n}), got {tuple(p.shape)}")
+        rows = self._path_rows(path, R, 2, "path", 0)   # (R, K, n)
         r = int(refine)
         if r < 1:
             raise ValueError(f"refine must be >= 1, got {refine}")
-        if p.shape[0] == 2 and r == 1:
+        if rows.shape[1] == 2 and r == 1:
             raise ValueError("a path of two waypoints cannot be timed (rest to rest needs three): pass refine >= 2 to split its segment")
 
         def limit(v, name):
@@ -1329,7 +1304,6 @@ class EntityView:
         dt = float(self._b.opt["dt"] if dt is None else dt)
         if not (np.isfinite(dt) and dt > 0.0):
             raise ValueError(f"dt must be finite and > 0, got {dt}")
-        rows = p.permute(1, 0, 2).contiguous()   # (R, K, n)
         if r > 1:
             f = (torch.arange(r, dtype=torch.float32, device=mir.device) / float(r))[None, None, :, None]
             a, b = rows[:, :-1, None, :], rows[:, 1:, None, :]
@@ -1353,9 +1327,7 @@ class EntityView:
             return samples[:, 0] if one else samples
         detail = {"samples": samples, "velocity": res["sample_vel"].permute(1, 0, 2).contiguous(), "valid": res["status"] <= 1,
                   "status": res["status"], "duration": res["duration"], "n_samples": res["n_samples"], "t": res["t"], "x": res["x"]}
-        if one:
-            detail = {k: (v[:, 0] if k in ("samples", "velocity") else v[0]) for k, v in detail.items()}
-        return detail
+        return self._drop_env_axis(detail, ("samples", "velocity"))
 
     def get_carried_clearance(self, qpos=None, attached_entity=None, ee_link_name=None, grasp_pose=None, attached_links=None, envs_idx=None,
                               with_entity=None, ignore_entities=(), max_distance: float = 1.0, self_collision=None) -> dict:
@@ -1372,7 +1344,7 @@ class EntityView:
         q = self.get_dofs_position(envs_idx=envs_idx) if qpos is None else self._entity_rows(qpos, R, "qpos")
         r = self._mir.path_clearance(paths=torch.stack([q, q], 1).contiguous(), max_distance=float(max_distance), **args)
         out = {"clearance": r["row_min"], "self_clearance": r["row_self_min"]}
-        return {k: v[0] for k, v in out.items()} if self.__dict__.get("unbatched") else out
+        return self._drop_env_axis(out, ())
 
     def get_link(self, name: str) -> LinkView:
         return LinkView(self._mir, self._b.body_index(name), name)
