@@ -58,16 +58,7 @@
 
 namespace {
 
-// ---- random numbers: u(env, c, j) in [0, 1), keyed by the env index
-__device__ __forceinline__ uint32_t plan_mix(uint32_t x) {
-  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
-  return x;
-}
-__device__ __forceinline__ float plan_u(uint32_t seed, uint32_t env, uint32_t c, uint32_t j) {
-  const uint32_t x = plan_mix(plan_mix(plan_mix(seed ^ env) ^ c) ^ j);
-  return (float)(x >> 8) * 5.9604644775390625e-8f;  // 2^-24
-}
-
+// (the random numbers u(env, c, j): plan_u of mir_plan_row.h)
 extern __shared__ float plan_dyn[];
 
 template <bool SELF, bool CARRY>

@@ -53,6 +53,16 @@ struct PlanLds {
   float cum[MIR_PLAN_MAX_POLY];
 };
 
+// random numbers of the planner: u(env, c, j) in [0, 1), keyed by the env index (mir_plan.hip, mir_goal.hip)
+__device__ __forceinline__ uint32_t plan_mix(uint32_t x) {
+  x ^= x >> 16; x *= 0x85EBCA6Bu; x ^= x >> 13; x *= 0xC2B2AE35u; x ^= x >> 16;
+  return x;
+}
+__device__ __forceinline__ float plan_u(uint32_t seed, uint32_t env, uint32_t c, uint32_t j) {
+  const uint32_t x = plan_mix(plan_mix(plan_mix(seed ^ env) ^ c) ^ j);
+  return (float)(x >> 8) * 5.9604644775390625e-8f;  // 2^-24
+}
+
 // x / y with one refinement of the quotient (x >= 0, y > 0): within an ulp of the exact quotient whatever the division flags of the build
 __device__ __forceinline__ float div_refined(float x, float y) {
   const float r = 1.0f / y;

@@ -13,7 +13,7 @@ from typing import Optional
 import numpy as np
 import torch
 
-from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirCartQuery, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirBlendQuery, MirOptQuery, MirCarryQuery, MirCertQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_blend_query, make_opt_query, make_carry_query, make_cart_query, make_cert_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
+from .spec import PLAN_MAX_POLY, IK_DEFAULTS, IK_INIT_BY_ENV, IK_POS_BY_ENV, IK_QUAT_BY_ENV, IK_QUAT_ONE, MIR_VERSION, MirCameraSpec, MirCartQuery, MirDims, MirIkMulti, MirIkOptions, MirIkRows, MirAccQuery, MirBlendQuery, MirOptQuery, MirCarryQuery, MirGoalQuery, MirPoseGoalQuery, MirCertQuery, MirDistQuery, MirDynQuery, MirKinQuery, MirPlanQuery, MirRayQuery, MirRetimeQuery, MirSceneSpec, MirSelfQuery, MirTaskQuery, MirVisualSpec, make_acc_query, make_blend_query, make_opt_query, make_carry_query, make_goal_query, make_pose_goal_query, make_cart_query, make_cert_query, make_dist_query, make_dyn_query, make_ik_multi, make_kin_query, make_plan_query, make_ray_query, make_retime_query, make_self_query, make_task_query  # noqa: F401
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.normpath(os.path.join(_HERE, "..", "..", "csrc", "libmirigid.so"))
@@ -161,6 +161,14 @@ def load_library() -> C.CDLL:
     lib.mir_plan_path_carry.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp, vp, i32, vp, vp, vp, vp, vp,
                                         vp, vp, vp, vp, vp]
     lib.mir_plan_path_carry.restype = C.c_int
+    lib.mir_goal_query_sizeof.restype = C.c_int
+    lib.mir_plan_path_goals.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), C.POINTER(MirGoalQuery), vp, vp, vp,
+                                        vp, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    lib.mir_plan_path_goals.restype = C.c_int
+    lib.mir_pose_goal_query_sizeof.restype = C.c_int
+    lib.mir_plan_path_pose.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), C.POINTER(MirPoseGoalQuery), vp, vp, vp,
+                                       vp, i32, vp, vp, vp, vp, C.POINTER(MirIkOptions)] + [vp] * 12
+    lib.mir_plan_path_pose.restype = C.c_int
     lib.mir_path_clearance_carry.argtypes = [vp, C.POINTER(MirPlanQuery), C.POINTER(MirSelfQuery), C.POINTER(MirCarryQuery), vp, vp, vp, vp, i32, vp, vp, vp,
                                              i32, vp, vp, vp, vp, vp, vp, vp]
     lib.mir_path_clearance_carry.restype = C.c_int
@@ -197,6 +205,7 @@ def load_library() -> C.CDLL:
     for fn, struct in (("mir_kin_query_sizeof", MirKinQuery), ("mir_acc_query_sizeof", MirAccQuery), ("mir_dyn_query_sizeof", MirDynQuery),
                        ("mir_task_query_sizeof", MirTaskQuery), ("mir_ray_query_sizeof", MirRayQuery), ("mir_dist_query_sizeof", MirDistQuery),
                        ("mir_plan_query_sizeof", MirPlanQuery), ("mir_self_query_sizeof", MirSelfQuery), ("mir_carry_query_sizeof", MirCarryQuery),
+                       ("mir_goal_query_sizeof", MirGoalQuery), ("mir_pose_goal_query_sizeof", MirPoseGoalQuery),
                        ("mir_retime_query_sizeof", MirRetimeQuery), ("mir_cart_query_sizeof", MirCartQuery), ("mir_blend_query_sizeof", MirBlendQuery),
                        ("mir_opt_query_sizeof", MirOptQuery), ("mir_cert_query_sizeof", MirCertQuery), ("mir_ik_multi_sizeof", MirIkMulti)):
         if getattr(lib, fn)() != C.sizeof(struct):
@@ -1116,6 +1125,90 @@ class MirScene(StepHelpers):
             out["grasp"] = s.grasp_used
         self._check(fn(*head, *s.grasp_in, _ptr(goal), _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]),
                        _ptr(out["stats"]), *s.grasp_out, self._stream()))
+        if R > 0:
+            self._launched("plan")
+        return out
+
+    def plan_path_goals(self, probes, links, dof_qadr, qpos_goals, n_goals=None, env_idx=None, qpos_start=None, num_waypoints: int = 100,
+                        max_nodes: int = 256, max_iterations: int = 2000, smooth_passes: int = 64, ignore_collision: bool = False, seed: int = 0,
+                        resolution: float = 0.05, step: float = 0.3, margin: float = 0.0, max_distance: float = 1.0, skip_geoms=0,
+                        self_model=None, carry=None) -> dict:
+        """mir_plan_path_goals: plan_path() to a SET of goal configurations per row, in ONE launch.  `qpos_goals` (R, G, D), G = 1 ..
+        spec.PLAN_MAX_GOALS; `n_goals` (R,) integers, None: G for every row -- the entries at or behind a row's count are never read.
+        Every goal is judged (limits, then the collision tests of the call); the direct edge is tried to the valid ones, nearest to the
+        start first; otherwise RRT-Connect runs with the goal tree started from all valid goals, and the plan ends at whichever goal the
+        trees meet through (include/mirigid.h has the rule).  Everything else, `self_model` and `carry` included, as plan_path().
+        -> the dict of plan_path() plus goal_index (R,) int32: the goal the plan ends at, -1 for a row without a plan, and goal_status
+        (R, G) int32: spec.PLAN_STATUS per goal, -1 behind the row's count (and for every goal of a row whose start is refused).  A row
+        without a valid goal has status NO_VALID_GOAL (spec.PLAN_GOAL_STATUS names the row statuses).  With one valid goal per row the result is that of plan_path() bit for bit."""
+        s = _SphereCall(self, probes, links, dof_qadr, env_idx, qpos_start, self_model)
+        R, D, new = s.R, s.D, s.new
+        goals = torch.as_tensor(qpos_goals, device=self.device).to(torch.float32).contiguous()
+        if goals.dim() != 3 or goals.shape[0] != R or goals.shape[2] != D:
+            raise ValueError(f"qpos_goals must be ({R}, G, {D}), got {tuple(goals.shape)}")
+        NG = int(goals.shape[1])
+        gq = make_goal_query(NG)
+        if n_goals is not None:
+            n_goals = torch.as_tensor(n_goals, device=self.device).to(torch.int32).contiguous()
+            if tuple(n_goals.shape) != (R,):
+                raise ValueError(f"n_goals must be ({R},), got {tuple(n_goals.shape)}")
+        s.collision(carry, True, num_waypoints=num_waypoints, max_nodes=max_nodes, max_iterations=max_iterations, smooth_passes=smooth_passes,
+                    ignore_collision=ignore_collision, seed=seed, resolution=resolution, step=step, margin=margin, max_distance=max_distance,
+                    skip_geoms=skip_geoms)
+        W, i32 = max(int(num_waypoints), 0), torch.int32
+        out = {"path": new(W, D), "status": new(dtype=i32), "poly": new(PLAN_MAX_POLY, D), "n_poly": new(dtype=i32), "stats": new(4, dtype=i32),
+               "goal_index": new(dtype=i32), "goal_status": new(NG, dtype=i32)}
+        if s.cq is not None:
+            out["grasp"] = s.grasp_used
+        head = s.head()  # (h, pq, sq, cq, ...: the goal query stands behind the carry query)
+        self._check(self.lib.mir_plan_path_goals(*head[:4], C.byref(gq), *head[4:], *(s.grasp_in or (None,)), _ptr(goals), _ptr(n_goals),
+                                                 _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]), _ptr(out["stats"]),
+                                                 *(s.grasp_out or (None,)), _ptr(out["goal_index"]), _ptr(out["goal_status"]), self._stream()))
+        if R > 0:
+            self._launched("plan")
+        return out
+
+    def plan_path_pose(self, probes, links, dof_qadr, link_body: int, target_pos, target_quat=None, max_goals: int = 4, max_samples: int = 16,
+                       dedup: float = 0.0, env_idx=None, qpos_start=None, num_waypoints: int = 100, max_nodes: int = 256,
+                       max_iterations: int = 2000, smooth_passes: int = 64, ignore_collision: bool = False, seed: int = 0,
+                       resolution: float = 0.05, step: float = 0.3, margin: float = 0.0, max_distance: float = 1.0, skip_geoms=0,
+                       self_model=None, carry=None, **ik_options) -> dict:
+        """mir_plan_path_pose: plan_path_goals() whose goal set is made inside the launch -- up to `max_goals` inverse-kinematics
+        solutions of the pose `target_pos` (R, 3) / `target_quat` ((R, 4) wxyz; None: position only) of the body `link_body`, from up
+        to `max_samples` seeds (the start, then random draws inside the joint limits, deterministic in `seed`), each kept when it
+        converged (`ik_options`: those of inverse_kinematics()), lies inside the limits, is clear by the collision tests of the call
+        and differs from every kept one by `dedup` (0: `resolution`) in some joint; then the goal-set planner on the kept ones, with no
+        host decision in between (include/mirigid.h has the rule).  Everything else as plan_path_goals().
+        -> its dict plus goals (R, G, D): the kept configurations, zeros behind them, n_goals (R,) int32 and goal_stats (R, 4) int32:
+        samples tried, samples converged, converged but in collision or outside the limits, IK iterations.  A row that keeps no goal has
+        status NO_VALID_GOAL; a target that is not finite, spec.CART_NOT_FINITE."""
+        s = _SphereCall(self, probes, links, dof_qadr, env_idx, qpos_start, self_model)
+        R, D, new = s.R, s.D, s.new
+        tp = torch.as_tensor(target_pos, device=self.device).to(torch.float32).contiguous()
+        if tuple(tp.shape) != (R, 3):
+            raise ValueError(f"target_pos must be ({R}, 3), got {tuple(tp.shape)}")
+        tq = None
+        if target_quat is not None:
+            tq = torch.as_tensor(target_quat, device=self.device).to(torch.float32).contiguous()
+            if tuple(tq.shape) != (R, 4):
+                raise ValueError(f"target_quat must be ({R}, 4), got {tuple(tq.shape)}")
+        NG = int(max_goals)
+        gq = make_pose_goal_query(link_body, NG, max_samples, dedup)
+        s.collision(carry, True, num_waypoints=num_waypoints, max_nodes=max_nodes, max_iterations=max_iterations, smooth_passes=smooth_passes,
+                    ignore_collision=ignore_collision, seed=seed, resolution=resolution, step=step, margin=margin, max_distance=max_distance,
+                    skip_geoms=skip_geoms)
+        o = self._ik_options(ik_options)
+        W, i32, G_ = max(int(num_waypoints), 0), torch.int32, max(NG, 0)
+        out = {"path": new(W, D), "status": new(dtype=i32), "poly": new(PLAN_MAX_POLY, D), "n_poly": new(dtype=i32), "stats": new(4, dtype=i32),
+               "goal_index": new(dtype=i32), "goal_status": new(G_, dtype=i32), "goals": new(G_, D), "n_goals": new(dtype=i32),
+               "goal_stats": new(4, dtype=i32)}
+        if s.cq is not None:
+            out["grasp"] = s.grasp_used
+        head = s.head()
+        self._check(self.lib.mir_plan_path_pose(*head[:4], C.byref(gq), *head[4:], *(s.grasp_in or (None,)), _ptr(tp), _ptr(tq), C.byref(o),
+                                                _ptr(out["path"]), _ptr(out["status"]), _ptr(out["poly"]), _ptr(out["n_poly"]), _ptr(out["stats"]),
+                                                *(s.grasp_out or (None,)), _ptr(out["goal_index"]), _ptr(out["goal_status"]), _ptr(out["goals"]),
+                                                _ptr(out["n_goals"]), _ptr(out["goal_stats"]), self._stream()))
         if R > 0:
             self._launched("plan")
         return out

@@ -476,6 +476,9 @@ PLAN_STATUS = ("OK", "GOAL_OUT_OF_LIMITS", "START_IN_COLLISION", "GOAL_IN_COLLIS
                "START_IN_SELF_COLLISION", "GOAL_IN_SELF_COLLISION")
 (PLAN_OK, PLAN_GOAL_OUT_OF_LIMITS, PLAN_START_IN_COLLISION, PLAN_GOAL_IN_COLLISION, PLAN_NODE_LIMIT, PLAN_ITERATION_LIMIT,
  PLAN_PATH_TOO_LONG, PLAN_START_IN_SELF_COLLISION, PLAN_GOAL_IN_SELF_COLLISION) = range(9)
+PLAN_MAX_GOALS = 8  # MIR_PLAN_MAX_GOALS: goal configurations per row of mir_plan_path_goals
+PLAN_NO_VALID_GOAL = 9  # MIR_PLAN_NO_VALID_GOAL: the one row status mir_plan_path_goals adds
+PLAN_GOAL_STATUS = PLAN_STATUS + ("NO_VALID_GOAL",)  # the row statuses of mir_plan_path_goals by value (a goal's own status is one of PLAN_STATUS)
 
 
 class MirPlanQuery(C.Structure):
@@ -552,6 +555,45 @@ def make_carry_query(body: int, link: int) -> MirCarryQuery:
     q = MirCarryQuery()
     q.struct_size = C.sizeof(MirCarryQuery)
     q.body, q.link, q.flags = int(body), int(link), 0
+    return q
+
+
+class MirGoalQuery(C.Structure):
+    """include/mirigid.h: MirGoalQuery (mir_plan_path_goals)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("max_goals", C.c_int32),
+        ("flags", C.c_uint32),
+        ("_pad", C.c_int32),
+    ]
+
+
+def make_goal_query(max_goals: int) -> MirGoalQuery:
+    """max_goals: G, the goal configurations per row (1 .. PLAN_MAX_GOALS, below the planner's max_nodes)"""
+    q = MirGoalQuery()
+    q.struct_size = C.sizeof(MirGoalQuery)
+    q.max_goals, q.flags = int(max_goals), 0
+    return q
+
+
+class MirPoseGoalQuery(C.Structure):
+    """include/mirigid.h: MirPoseGoalQuery (mir_plan_path_pose)"""
+    _fields_ = [
+        ("struct_size", C.c_int32),
+        ("link", C.c_int32),
+        ("max_goals", C.c_int32),
+        ("max_samples", C.c_int32),
+        ("flags", C.c_uint32),
+        ("dedup", C.c_float),
+    ]
+
+
+def make_pose_goal_query(link: int, max_goals: int = 4, max_samples: int = 16, dedup: float = 0.0) -> MirPoseGoalQuery:
+    """link: the body whose pose is the goal; max_goals: G kept IK solutions at most (1 .. PLAN_MAX_GOALS); max_samples: IK seeds tried at
+    most; dedup: two kept goals differ by at least this much in some joint (0: the planner's resolution)"""
+    q = MirPoseGoalQuery()
+    q.struct_size = C.sizeof(MirPoseGoalQuery)
+    q.link, q.max_goals, q.max_samples, q.flags, q.dedup = int(link), int(max_goals), int(max_samples), 0, float(dedup)
     return q
 
 

@@ -952,6 +952,92 @@ class EntityView:
             return detail
         return (detail["path"], detail["valid"]) if return_valid_mask else detail["path"]
 
+    def plan_path_to_goals(self, qpos_goals, n_goals=None, qpos_start=None, timeout=None, smooth_path=True, num_waypoints=100,
+                           ignore_collision=False, planner="RRTConnect", envs_idx=None, return_valid_mask=False, resolution=0.05, step=0.3,
+                           margin=0.0, max_nodes=256, max_iterations=2000, seed=0, with_entity=None, ignore_entities=(), return_detail=False,
+                           self_collision=None, self_margin=0.0, attached_entity=None, ee_link_name=None, grasp_pose=None, attached_links=None):
+        """``robot.plan_path_to_goals(qpos_goals=[q_a, q_b])`` -> (W, R, n): plan_path() to whichever of several goal configurations can be
+        reached -- two grasp approaches, the symmetric grasps of a cube, several inverse-kinematics solutions of one pose.  `qpos_goals`
+        (G, R, n), G = 1 .. 8, in the layout of a stack of plan_path() goals ((G, n) on an unbatched task); `n_goals` (R,): how many
+        of a row's goals count (None: all G; the entries behind a row's count are never read).  ONE launch (MirScene.plan_path_goals /
+        mir_plan_path_goals, where the rule is written down): every goal is judged like plan_path()'s; the straight edge is tried to the
+        valid ones, nearest to the start first; otherwise RRT-Connect grows its goal tree from all valid goals at once and the plan ends at
+        the goal the trees meet through.  A row without a valid goal has status 9 (NO_VALID_GOAL; spec.PLAN_GOAL_STATUS) and, like every row without a plan,
+        holds its start W times.  Every other keyword means what it means in plan_path(), and the result has plan_path()'s layout;
+        return_detail gains goal_index (R,): the goal the plan ends at (-1: no plan) and goal_status (R, G): spec.PLAN_STATUS per goal,
+        -1 where a goal was not judged.  With one valid goal the result is plan_path()'s bit for bit.
+        NOTE: a row status of this method can be 9, which spec.PLAN_STATUS (nine names, as it always had) does not hold: name row
+        statuses with spec.PLAN_GOAL_STATUS[status]; goal_status entries are 0 .. 8 and spec.PLAN_STATUS names them."""
+        if planner != "RRTConnect":
+            raise NotImplementedError(f"planner {planner!r}: only 'RRTConnect' is implemented")
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "plan_path_to_goals", self_collision, self_margin, attached_entity,
+                                  ee_link_name, grasp_pose, attached_links)
+        goals = self._path_rows(qpos_goals, R, 1, "qpos_goals", 0, "G")
+        if n_goals is not None:
+            n_goals = torch.as_tensor(n_goals, device=self._mir.device).to(torch.int32).reshape(-1)
+        r = self._mir.plan_path_goals(qpos_goals=goals, n_goals=n_goals, num_waypoints=int(num_waypoints), max_nodes=int(max_nodes),
+                                      max_iterations=int(max_iterations), smooth_passes=64 if smooth_path else 0,
+                                      ignore_collision=bool(ignore_collision), seed=int(seed), resolution=float(resolution), step=float(step),
+                                      margin=float(margin), max_distance=max(1.0, 2.0 * float(margin)), **args)
+        detail = {"path": r["path"].permute(1, 0, 2).contiguous(), "valid": r["status"] == 0, "status": r["status"], "poly": r["poly"],
+                  "n_poly": r["n_poly"], "stats": r["stats"], "goal_index": r["goal_index"], "goal_status": r["goal_status"]}
+        if "grasp" in r:
+            detail["grasp"] = r["grasp"]
+        detail = self._drop_env_axis(detail)
+        if return_detail:
+            return detail
+        return (detail["path"], detail["valid"]) if return_valid_mask else detail["path"]
+
+    def plan_path_to_pose(self, link, pos, quat=None, max_goals=4, max_samples=16, dedup=None, qpos_start=None, timeout=None, smooth_path=True,
+                          num_waypoints=100, ignore_collision=False, planner="RRTConnect", envs_idx=None, return_valid_mask=False,
+                          resolution=0.05, step=0.3, margin=0.0, max_nodes=256, max_iterations=2000, seed=0, with_entity=None,
+                          ignore_entities=(), return_detail=False, self_collision=None, self_margin=0.0, attached_entity=None,
+                          ee_link_name=None, grasp_pose=None, attached_links=None, **ik_options):
+        """``robot.plan_path_to_pose(hand, pos=(R, 3), quat=(R, 4))`` -> (W, R, n): plan_path() to a POSE of `link` (a LinkView or a local
+        link index) instead of a goal configuration -- above the cube, at the cube, over the stack -- in ONE launch
+        (MirScene.plan_path_pose / mir_plan_path_pose, where the rule is written down).  The row's wave solves the inverse kinematics of
+        the pose from up to `max_samples` seeds (the start configuration, then random draws inside the joint limits; `ik_options`:
+        those of inverse_kinematics), keeps up to `max_goals` (<= 8) solutions that converged, lie inside the limits, are clear by the
+        collision tests of the call and differ from one another by `dedup` (None: `resolution`) in some joint, and runs the goal-set
+        planner of plan_path_to_goals() on them: nothing is decided on the host between the pose and the plan.  `quat` (R, 4) wxyz or
+        one quaternion for all; None: position only.  Dofs of the entity that are not on the chain to `link` (the fingers) keep their
+        start value.  Every other keyword means what it means in plan_path(); the result has plan_path()'s layout.  A row that keeps
+        no goal has status 9 (NO_VALID_GOAL; name row statuses with spec.PLAN_GOAL_STATUS, not spec.PLAN_STATUS), a target that is not
+        finite 17 (spec.CART_STATUS: NOT_FINITE).  return_detail gains goal_index (R,), goal_status (R, G), goals (R, G, n): the kept
+        configurations, n_goals (R,) and goal_stats (R, 4): samples tried, converged, converged but rejected, IK iterations --
+        converged = 0 tells "unreachable" from "every solution collides"."""
+        if planner != "RRTConnect":
+            raise NotImplementedError(f"planner {planner!r}: only 'RRTConnect' is implemented")
+        args, R = self._plan_args(envs_idx, qpos_start, with_entity, ignore_entities, "plan_path_to_pose", self_collision, self_margin, attached_entity,
+                                  ee_link_name, grasp_pose, attached_links)
+        self._need("plan_path_pose", "pose goals")
+        dev = self._mir.device
+        p = torch.as_tensor(pos, device=dev).to(torch.float32)
+        p = p.reshape(1, 3).expand(R, 3) if p.numel() == 3 else p
+        if tuple(p.shape) != (R, 3):
+            raise ValueError(f"pos must be ({R}, 3), got {tuple(p.shape)}")
+        q = None
+        if quat is not None:
+            q = torch.as_tensor(quat, device=dev).to(torch.float32)
+            q = q.reshape(1, 4).expand(R, 4) if q.numel() == 4 else q
+            if tuple(q.shape) != (R, 4):
+                raise ValueError(f"quat must be ({R}, 4) or (4,), got {tuple(q.shape)}")
+            q = q.contiguous()
+        r = self._mir.plan_path_pose(link_body=self._link_body(link), target_pos=p.contiguous(), target_quat=q, max_goals=int(max_goals),
+                                     max_samples=int(max_samples), dedup=0.0 if dedup is None else float(dedup), num_waypoints=int(num_waypoints),
+                                     max_nodes=int(max_nodes), max_iterations=int(max_iterations), smooth_passes=64 if smooth_path else 0,
+                                     ignore_collision=bool(ignore_collision), seed=int(seed), resolution=float(resolution), step=float(step),
+                                     margin=float(margin), max_distance=max(1.0, 2.0 * float(margin)), **args, **ik_options)
+        detail = {"path": r["path"].permute(1, 0, 2).contiguous(), "valid": r["status"] == 0, "status": r["status"], "poly": r["poly"],
+                  "n_poly": r["n_poly"], "stats": r["stats"], "goal_index": r["goal_index"], "goal_status": r["goal_status"], "goals": r["goals"],
+                  "n_goals": r["n_goals"], "goal_stats": r["goal_stats"]}
+        if "grasp" in r:
+            detail["grasp"] = r["grasp"]
+        detail = self._drop_env_axis(detail)
+        if return_detail:
+            return detail
+        return (detail["path"], detail["valid"]) if return_valid_mask else detail["path"]
+
     def get_path_clearance(self, path, envs_idx=None, qpos_start=None, resolution=0.05, margin=0.0, with_entity=None, ignore_entities=(),
                            max_distance: float = 1.0, return_detail: bool = False, self_collision=None, self_margin=0.0, attached_entity=None,
                            ee_link_name=None, grasp_pose=None, attached_links=None):

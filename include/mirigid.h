@@ -942,6 +942,100 @@ int mir_path_clearance_carry(MirHandle h, const MirPlanQuery* q, const MirSelfQu
                              float* row_self_min /* (R), NULL without sq */, int32_t* row_first_blocked /* (R) */,
                              float* grasp_used /* (R,7) nullable */, void* stream);
 
+/* ---- goal sets: planning to whichever of several goal configurations can be reached ----------------------
+ * `robot.plan_path_to_goals(qpos_goals)`: two grasp approaches, the symmetric grasps of a cube, several inverse-kinematics branches of
+ * one pose.  mir_plan_path_goals is mir_plan_path_carry with a SET of goals per row: ONE launch judges the goals, tries the direct edge
+ * to the valid ones and otherwise plans to whichever the trees meet through, with no host decision in between.  Every argument of
+ * mir_plan_path_carry keeps its meaning, but sq AND cq are nullable (neither: the scene test of mir_plan_path; grasp and grasp_used
+ * must be NULL without cq), so that this one entry point serves all four forms.
+ * Goals.  gq->max_goals = G, 1 .. MIR_PLAN_MAX_GOALS; qpos_goals (R, G, D); n_goals (R) int32, nullable: G for every row.  A row value
+ *   outside 0 .. G is clamped; the entries at or beyond the row's count are never read (a NaN there is harmless).
+ * Algorithm.  1. The start: its scene test fails: START_IN_COLLISION; with sq, its self test: START_IN_SELF_COLLISION (clear() of the
+ *   form the call selects; the goals are then not judged: every goal_status of the row is -1).  2. Each goal g < n_goals[r], g
+ *   ascending, gets goal_status[r, g]: a value that is not finite or outside [lo, hi] in a planned dof: GOAL_OUT_OF_LIMITS (nothing
+ *   is evaluated for it); its scene test fails (the carried body's spheres among the first N included): GOAL_IN_COLLISION; its self
+ *   test: GOAL_IN_SELF_COLLISION; otherwise MIR_PLAN_OK: the goal is valid.  These are the statuses mir_plan_path and its forms give the
+ *   same goal.  No valid goal (n_goals[r] = 0 included): the row ends with MIR_PLAN_NO_VALID_GOAL; as for every failed plan the arm
+ *   stays put.  3. edge(start, goal_g) is tried for the valid goals in ascending squared L2 distance from the start (summed j ascending
+ *   as in `nearest`; the lower g on a tie); the first edge that holds gives the polyline [start, goal_g], iterations = 0.  4. Otherwise
+ *   RRT-Connect exactly as step 4 of mir_plan_path, with one change: Tb starts as a FOREST, its first nodes are the valid goals in
+ *   ascending g, each without a parent.  nearest, extend, connect, NODE_LIMIT and ITERATION_LIMIT are unchanged (odd iterations extend
+ *   the forest from its nearest node, whichever root that hangs on).  5. The extraction walks Tb's parents to whichever root it reaches:
+ *   that root is the row's goal, the last node of the polyline and the last waypoint are its bits.  6., 7. Smoothing and resampling
+ *   unchanged (the smoothing never removes the last node).  With G = 1 and a valid goal every output is that of mir_plan_path /
+ *   _self / _carry bit for bit; the two differ only in the order of the refusals of a row: mir_plan_path looks at the goal's limits
+ *   before the start.  max_iterations must stay below 2^30: the counters from 0x40000000 on are kept for goal sampling.
+ * Outputs.  path, status, poly, n_poly, stats, grasp_used: those of mir_plan_path_carry; stats[2], the nodes of Tb, counts the roots
+ *   from the moment the trees are set up (1 before, as in mir_plan_path).  goal_index (R), nullable: the g the plan ends at, -1 for a
+ *   row that fails.  goal_status (R, G), nullable: as above, -1 behind n_goals[r].
+ * The trees live in LDS as for mir_plan_path (the same MIR_E_CAPACITY); the goals need no LDS of their own.
+ * MIR_E_INVALID, besides the refusals of mir_plan_path_carry with a nullable cq: a NULL gq or qpos_goals; struct_size !=
+ * sizeof(MirGoalQuery); an unknown flag bit; max_goals outside 1 .. 8; max_nodes <= max_goals; grasp or grasp_used without cq.  None of
+ * them launches anything.
+ * Not done (a goal given as a POSE of a link is mir_plan_path_pose, below): goal regions or orientation tolerances about an axis; a ranking of the goals other than by distance from the
+ * start; parity with Genesis (OMPL) or MoveIt, which is unpinned as for mir_plan_path.
+ * (Added struct, status and entry point: MIR_VERSION and every other struct and entry point stay as they are.) */
+#define MIR_PLAN_MAX_GOALS 8
+#define MIR_PLAN_NO_VALID_GOAL 9
+typedef struct MirGoalQuery {
+  int32_t  struct_size;  /* = sizeof(MirGoalQuery) */
+  int32_t  max_goals;    /* G: 1 .. MIR_PLAN_MAX_GOALS, < MirPlanQuery.max_nodes */
+  uint32_t flags;        /* 0; unknown bits are MIR_E_INVALID */
+  int32_t  _pad;
+} MirGoalQuery;
+int mir_goal_query_sizeof(void);
+int mir_plan_path_goals(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq /* nullable: no self test */,
+                        const MirCarryQuery* cq /* nullable: no carried body */, const MirGoalQuery* gq,
+                        const float* probes /* (N+E,4) device */, const int32_t* probe_link /* (N+E) HOST, nullable */,
+                        const int32_t* dof_qadr, const int64_t* env_idx, int32_t n_rows, const float* qpos_start,
+                        const float* grasp /* (R,7) device, nullable; NULL without cq */, const float* qpos_goals /* (R,G,D) */,
+                        const int32_t* n_goals /* (R) device, nullable: G */, float* path, int32_t* status, float* poly, int32_t* n_poly,
+                        int32_t* stats, float* grasp_used /* (R,7) nullable; NULL without cq */, int32_t* goal_index /* (R) nullable */,
+                        int32_t* goal_status /* (R,G) nullable */, void* stream);
+
+/* ---- pose goals: planning to a pose of a link ---------------------------------------------------------------
+ * `robot.plan_path_to_pose(link, pos, quat)`: mir_plan_path_pose is mir_plan_path_goals whose goal set is not read but MADE by the
+ * row's wave before the planner starts: inverse-kinematics solutions of the pose, sampled, judged and kept inside the same launch.
+ * Every argument of mir_plan_path_goals keeps its meaning but qpos_goals / n_goals, which are outputs here.
+ * Chain and options.  gq->link: the body whose pose is asked for; the chain world -> link, its moving joints (the planned dofs on it,
+ *   at least one, else MIR_E_INVALID) and opt (damping, pos_tol, rot_tol, max_iters, max_step, respect_joint_limit; NULL: the defaults)
+ *   are those of mir_cartesian_path.  target_pos (R, 3); target_quat (R, 4) wxyz, nullable: position only.  A target value that is
+ *   not finite or a quaternion with n2 < 1e-30: the row ends with MIR_CART_NOT_FINITE before anything is evaluated.
+ * Then the start checks of mir_plan_path_goals.  Then, for s = 0 .. max_samples - 1, until G = max_goals goals are kept:
+ *   seed: the start row's chain joints for s = 0; for s > 0 every moving LIMITED joint of the chain is lo + u(env, 0x40000000 | s,
+ *   j)(hi - lo), j its planned dof, u the planner's hash: the counters are disjoint from the iterations' (max_iterations < 2^30 is
+ *   required) and from 0x80000000 | s of the smoothing.  The iteration of mir_cartesian_path from that seed.  The candidate is the
+ *   planner's configuration with the chain's moving joints from the iteration and every other planned dof (the fingers) at its start
+ *   value.  It is kept when (a) the iteration converged within pos_tol / rot_tol, (b) every planned dof lies inside its limits, (c)
+ *   clear(candidate) holds with the scene, self and carried-object tests of the call, (d) max_j |candidate_j - kept_j| >= dedup for
+ *   every goal already kept (dedup = 0 in the query: the planner's resolution).  Sampling does not stop early once an edge would hold.
+ * The kept goals are Tb's first nodes, in the order kept; steps 3 - 7 of mir_plan_path_goals follow.  None kept: MIR_PLAN_NO_VALID_GOAL.
+ * Outputs.  Those of mir_plan_path_goals (goal_status: MIR_PLAN_OK for the kept goals, -1 behind them), plus, all nullable: goals
+ *   (R, G, D) the kept configurations, zeros behind them; n_goals (R); goal_stats (R, 4) int32: samples tried, samples converged,
+ *   converged but rejected by (b) or (c), IK iterations in total.  converged = 0 tells "unreachable" from "every solution collides".
+ * MIR_E_INVALID, besides the refusals of mir_plan_path_goals: a NULL gq or target_pos; struct_size; an unknown flag bit; max_samples
+ * outside 1 .. 2^30 - 1; dedup negative or not finite; max_iterations >= 2^30; the refusals of the chain and of opt as in
+ * mir_cartesian_path.  None of them launches anything.
+ * Not done: goal regions or orientation tolerances about an axis; one link; no ranking of the goals other than by distance from the
+ * start; sampling does not stop early; parity with Genesis / MoveIt is unpinned. */
+typedef struct MirPoseGoalQuery {
+  int32_t  struct_size;  /* = sizeof(MirPoseGoalQuery) */
+  int32_t  link;         /* the body whose pose is the goal */
+  int32_t  max_goals;    /* G: 1 .. MIR_PLAN_MAX_GOALS, < MirPlanQuery.max_nodes */
+  int32_t  max_samples;  /* >= 1 */
+  uint32_t flags;        /* 0 */
+  float    dedup;        /* >= 0; 0: MirPlanQuery.resolution */
+} MirPoseGoalQuery;
+struct MirIkOptions; /* (defined below, "batched inverse kinematics") */
+int mir_pose_goal_query_sizeof(void);
+int mir_plan_path_pose(MirHandle h, const MirPlanQuery* q, const MirSelfQuery* sq /* nullable */, const MirCarryQuery* cq /* nullable */,
+                       const MirPoseGoalQuery* gq, const float* probes, const int32_t* probe_link, const int32_t* dof_qadr,
+                       const int64_t* env_idx, int32_t n_rows, const float* qpos_start, const float* grasp /* nullable */,
+                       const float* target_pos /* (R,3) */, const float* target_quat /* (R,4) nullable */,
+                       const struct MirIkOptions* opt /* nullable */, float* path, int32_t* status, float* poly, int32_t* n_poly, int32_t* stats,
+                       float* grasp_used, int32_t* goal_index /* (R) */, int32_t* goal_status /* (R,G) */, float* goals /* (R,G,D) */,
+                       int32_t* n_goals /* (R) */, int32_t* goal_stats /* (R,4) */, void* stream);
+
 /* ---- time parameterisation: a joint path as targets at a chosen sample period, within velocity, acceleration and torque limits ----
  * mir_plan_path ends at geometry: W waypoints at equal arc length.  mir_retime_path says how long such a path takes and turns it into
  * targets: time-optimal path parameterisation by reachability analysis (TOPP-RA; Pham & Pham 2018) with the interpolation collocation
@@ -1402,7 +1496,7 @@ int mir_certify_path_carry(MirHandle h, const MirCertQuery* q, const MirPlanQuer
  *   max_distance < margin + activation.  None of them launches anything; n_rows = 0 returns MIR_OK.
  * What it does not do.  No self-collision term in the cost (the sweep alone tests it).  The obstacle cost is collocated at the
  *   waypoints: between them only the sweep looks, as coarsely as the edge rule.  No workspace-velocity weighting of the obstacle cost.
- *   No velocity, acceleration or torque limits (mir_retime_path).  The ends are fixed; no goal set, no pose goal, no restarts; a BLOCKED
+ *   No velocity, acceleration or torque limits (mir_retime_path).  The ends are fixed (a goal SET and a pose goal are the planner's: mir_plan_path_goals, mir_plan_path_pose), no restarts; a BLOCKED
  *   row is not repaired; the planner does not call it.  Parity with MoveIt's CHOMP, TrajOpt and cuRobo is unpinned.
  * (Added struct and entry point: MIR_VERSION and every other struct and entry point stay as they are.) */
 #define MIR_OPT_BLOCKED 48
